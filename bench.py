@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end frames/s of the per-frame ADAS path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--streams S] [--det yolov8n] [--lane ufldv2_res18]
+    python bench.py [--gpus N --steps K --warmup W] [--streams S] [--det yolov8n] [--lane ufldv2_res18] [--dump-outputs DIR]
 
 One "step" = one frame of each of S independent video streams through the whole hot path on one GPU:
 u8 camera frames (resident in HBM) -> letterbox / resize / normalise -> detector forward -> decode/letterbox/NMS -> ByteTrack
@@ -527,6 +527,54 @@ def idle_rank(SH, dist, args, stat_dev, pin):
     return 0
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pipe, L, PP, S, NSTREAMS, B, last_cam, t_cal, sharpen):
+    """What the timed path handed its caller after the last timed step, as float64 .npy files in out_dir (rank 0 only).
+
+    One row per item, the frame index f (frame b of stream s at f = b * NSTREAMS + s) first:
+      det.npy         NMS survivors   [f, keep (anchor), x, y, w, h, conf, class_id, x0, y0, x1, y1 (xyxy_int)]
+      candidates.npy  anchors over box_score [f, anchor, x, y, w, h, conf, class_id]
+      tracks.npy      tracker message [stream, frame b, tracked (1) / lost (0), track_id, state, is_activated, score, class_id,
+                      frame_id, start_frame, tracklet_len, t, l, w, h]  (B > 1: the message of every frame of the micro-batch)
+      lanes.npy       lane points     [f, lane, x, y];  lanes_detected.npy (S, 4)
+      input_sample.npy  4096 seeded pixels of the step's u8 camera frames (None: engine-seam inputs), and calibration.npy
+      [threshold, sharpen] of the synthetic detector: equal inputs between two runs are checked from these."""
+    os.makedirs(out_dir, exist_ok=True)
+    det, cand, trk, lanes, lane_det = [], [], [], [], np.zeros((S, 4))
+    for f in range(S):
+        d = PP.YoloPost.fetch(pipe.post, f)
+        for i in range(len(d["keep"])):
+            det.append([f, d["keep"][i], *d["xywh"][i], d["conf"][i], d["class_id"][i], *d["xyxy_int"][i]])
+        for i in range(len(d["cand_anchor"])):
+            cand.append([f, d["cand_anchor"][i], *d["cand_xywh"][i], d["cand_conf"][i], d["cand_cls"][i]])
+        pts, detected = pipe.decode.fetch(f)
+        lane_det[f] = detected
+        for li, lp in enumerate(pts):
+            lanes.extend([f, li, x, y] for x, y in lp)
+    for s_ in range(NSTREAMS):
+        for b in range(B):
+            hdr, tracked, lost = pipe.tracker.fetch(s_) if B == 1 else pipe.tracker.fetch_frame(s_, b)
+            for flag, recs in ((1, tracked), (0, lost)):
+                for r in recs:
+                    trk.append([s_, b, flag, r["track_id"], r["state"], r["is_activated"], r["score"], r["class_id"], r["frame_id"],
+                                r["start_frame"], r["tracklet_len"], *r["tlwh"]])
+    arrays = {"det": (det, 12), "candidates": (cand, 8), "tracks": (trk, 15), "lanes": (lanes, 4)}
+    out = {k: np.asarray(v, np.float64).reshape(-1, w) for k, (v, w) in arrays.items()}
+    out["lanes_detected"] = lane_det
+    out["calibration"] = np.asarray([t_cal, sharpen if sharpen is not None else 1.0], np.float64)
+    if last_cam is not None:
+        flat = last_cam.reshape(-1)
+        out["input_sample"] = flat[np.random.default_rng(0).choice(flat.size, 4096, replace=False)].astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "bytes": int(total), "files": sorted(k + ".npy" for k in out)}
+
+
 def timed_loop(one_step, steps, warmup, sync, barrier):
     for i in range(warmup):
         one_step(i)
@@ -565,6 +613,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="repeats of the --steps loop after the headline one (min / median / max reported)")
     ap.add_argument("--latency-steps", type=int, default=40, help="individually synchronised steps for the p50 / p99 step latency")
     ap.add_argument("--pool", type=int, default=2, help="distinct frame sets cycled through")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(detections, candidates, tracks, lanes) as float64 .npy files to DIR (rank 0), e.g. bench_outputs/")
     ap.add_argument("--hold", type=int, default=4, help="consecutive steps each frame set is shown for (a scene that changes "
                     "every HOLD frames: gives ByteTrack confirmed, lost and re-found tracks to maintain)")
     args = ap.parse_args()
@@ -715,6 +765,11 @@ def main():
     elapsed = timed_loop(stepper(pipe), args.steps, args.warmup, full_sync(pipe), barrier)
     local_elapsed = elapsed
     elapsed = SH.max_over_ranks(elapsed, dist, stat_dev)        # RCCL: clock + stats only, no data-path collective
+    dumped = None
+    if args.dump_outputs and rank == 0:       # the headline loop's last step, before the repeats below move the trackers on
+        last_set = ((args.steps - 1) // H) % P if args.steps > 0 else None
+        last_cam = h_cam[last_set] if from_frames and last_set is not None else None
+        dumped = dump_outputs(args.dump_outputs, pipe, L, PP, S, NSTREAMS, B, last_cam, t_cal, sd.sharpen)
     # ---- after the headline: the same loop REPEATS more times (box-to-box and run-to-run spread of `value`), then the step latency
     # distribution (every step synchronised: p50 / p99 of launch-to-completion, SURVEY 8e's per-rank statistics)
     rep_fps = []
@@ -1012,6 +1067,7 @@ def main():
                      "top_kernels": [{"kernel": k, "ms": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 else 0.0,
                                       "launches": v[2]} for k, v in top]},
         "host_ingest": host_ingest,
+        "dumped_outputs": dumped,
         "repeats": ({"n": len(rep_fps), "fps_min": round(min(rep_fps), 1), "fps_median": round(float(np.median(rep_fps)), 1),
                      "fps_max": round(max(rep_fps), 1), "what": "the --steps loop again after the headline one, same process (rank 0)"}
                     if rep_fps else None),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """TEST INFRASTRUCTURE -- INTEGRATION.md section A executed on the CPU: the REFERENCE's own detector classes on a swapped `coreEngine`.
 
-    python tests/integration_replay.py <fixture.npz> <out.json>         (run by tests/test_integration_replay.py in a fresh interpreter)
+    python tests/integration_replay.py <fixture.npz> <out.json>         (tests/golden/dropin_replay_ref.json: read by tests/test_integration_replay.py)
 
 The reference's YoloDetector / UltrafastLaneDetectorV2 (/root/reference, imported UNMODIFIED from where they lie) are constructed the
 way demo.py constructs them and fed the fixture's frame.  Their `from coreEngine import TensorRTEngine, OnnxEngine`

@@ -264,3 +264,32 @@ def test_detect_sink_needs_a_post_processor_of_the_same_head(tmp_path):
     p = PL.AdasPipeline(det_path, None, n_streams=2, precision="fp16", src_hw=(720, 1280), use_graph=False, head_layout=L.HEAD_V5)
     assert L.lib().adas_pipeline_detect_sink(p.h) == 1
     p.close()
+
+
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's results as float .npy files; two runs with the same arguments draw
+    the same inputs and write the same arrays, and the line's `steps` / `ms_per_step` are those of the --steps loop."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    runs = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        env = dict(os.environ, ADAS_MODEL_DIR=str(tmp_path / ("m%d" % i)))
+        os.makedirs(env["ADAS_MODEL_DIR"])
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--streams", "2",
+                              "--no-cpu-baseline", "--no-extras", "--repeats", "0", "--latency-steps", "8", "--dump-outputs", str(d)],
+                             env=env, capture_output=True, text=True, timeout=400)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 6 and r["ms_per_step"] > 0
+        assert abs(r["value"] - 6 * 2 / (6 * r["ms_per_step"] * 1e-3)) <= 1e-3 * r["value"]
+        files = sorted(os.listdir(d))
+        assert files == r["dumped_outputs"]["files"] and sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        runs.append({os.path.splitext(f)[0]: np.load(d / f) for f in files})
+    a, b = runs
+    assert a["det"].shape[0] > 0 and a["lanes"].shape[0] > 0 and a["tracks"].shape[0] > 0 and "input_sample" in a
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
