@@ -43,3 +43,16 @@ def lane_frames(n, h=320, w=1600, seed=2):
     # low-frequency structure so activations are not pure noise
     x = 0.5 * x + 0.5 * np.repeat(np.repeat(rng.uniform(0, 1, (n, 3, h // 16, w // 16)).astype(np.float32), 16, 2), 16, 3)
     return ((x - mean) / std).astype(np.float32)
+
+
+def assert_x3_convs(e, batch):
+    """Every conv layer of a split-precision engine runs on an x3 kernel or inside a fused launch (a conv that landed on a kernel of
+    another storage type would read the (hi, lo) pairs as something else)."""
+    labels = {}
+    for i in range(e.stats()["num_layers"]):
+        name, _, kind = e.layer_info(i)
+        if kind == M.OP_CONV:
+            labels[name] = e.layer_kernel(i, batch)
+    bad = {k: v for k, v in labels.items() if "x3" not in v and "fused" not in v}
+    assert labels and not bad, bad
+    return labels

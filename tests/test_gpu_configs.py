@@ -196,7 +196,8 @@ def test_ufld_small_16bit_modes(prec):
     le.close()
 
 
-def test_ufldv2_curvelanes_configuration_net_and_drop_in(tmp_path):
+@pytest.mark.parametrize("prec", ["fp32", None], ids=["fp32", "default"])
+def test_ufldv2_curvelanes_configuration_net_and_drop_in(tmp_path, prec):
     """The CurveLanes configuration (configs/curvelanes_res18.py: 10 lanes, 41 column anchors, LayerNorm; same parsingNet as CULane,
     convertPytorchToONNX.py:65-70) at a reduced input: network vs oracle in fp32, then frame -> lanes through the drop-in class with
     LaneModelType.UFLDV2_CURVELANES vs the oracle chain."""
@@ -206,14 +207,15 @@ def test_ufldv2_curvelanes_configuration_net_and_drop_in(tmp_path):
     path, W, g = netutil.model("ufldv2_curvelanes_res18", **kw)
     x = netutil.lane_frames(2, 256, 512, seed=4)
     want = nets.ufldv2_forward(x, W, "18", 200, 72, 100, 41, num_lanes=10)
-    e = CE.HipEngine(path, precision="fp32", max_batch=2)
+    e = CE.HipEngine(path, precision=prec, max_batch=2)
+    assert e.precision == (prec or "fp16x3")
     shapes, names = e.get_engine_output_shape()
     assert shapes == [[1, 200, 72, 10], [1, 100, 41, 10], [1, 2, 72, 10], [1, 2, 41, 10]]
     for o, w, nm in zip(e.engine_inference(x), want, names):
-        err, rel = report("ufldv2-curvelanes fp32 " + nm, o, w)
-        assert err <= 1e-3 * max(1.0, float(np.abs(w).max())), nm
+        err, rel = report("ufldv2-curvelanes %s %s" % (e.precision, nm), o, w)
+        assert err <= 1e-3 * max(1.0, float(np.abs(w).max())) and (prec == "fp32" or rel <= 1e-5), nm
     e.close()
-    det = D.UltrafastLaneDetectorV2(path, D.LaneModelType.UFLDV2_CURVELANES, precision="fp32")
+    det = D.UltrafastLaneDetectorV2(path, D.LaneModelType.UFLDV2_CURVELANES, precision=prec)
     assert det.cfg.crop_ratio == 0.8 and len(det.cfg.col_anchor) == 81
     rng = np.random.default_rng(5)
     frame = rng.integers(0, 255, (720, 1280, 3), dtype=np.uint8)

@@ -14,7 +14,7 @@ load_pkg()
 M = importlib.import_module("adas_amd.models")
 
 
-def run_case(CE, H, W, cin, cout, k, s, act, res_mode, prec, batch=2, seed=0, expect_kernel=None, info=None):
+def run_case(CE, H, W, cin, cout, k, s, act, res_mode, prec, batch=2, seed=0, expect_kernel=None, info=None, keep=None):
     ws = M.SynthWeights(seed, gain=1.0)
     g = M.Graph("unit", 3, H, W, ws)
     x, c3 = g.input()
@@ -37,6 +37,8 @@ def run_case(CE, H, W, cin, cout, k, s, act, res_mode, prec, batch=2, seed=0, ex
     kn = e.layer_kernel(e.layer_index("test"), batch)
     if info is not None:
         info["kernel"] = kn
+    if keep is not None:     # the fetched output itself (bit comparisons between runs)
+        keep["got"] = got
     if expect_kernel is not None:
         assert expect_kernel in kn, (kn, expect_kernel)
     e.close(); os.remove(path)

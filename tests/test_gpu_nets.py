@@ -79,17 +79,22 @@ def test_yolov8n_vs_oracle(CE, prec, tol_abs, tol_rel):
     e.close()
 
 
-def test_yolov5n_plumbing_config_c1(CE):
-    """BASELINE config 1 shape: YOLOv5n 640x640 single frame through the coreEngine surface."""
+@pytest.mark.parametrize("prec", [None, "fp32"], ids=["default", "fp32"])
+def test_yolov5n_plumbing_config_c1(CE, prec):
+    """BASELINE config 1 shape: YOLOv5n 640x640 single frame through the coreEngine surface, as its callers open it (no precision=:
+    the split precision) and in fp32, both at the fp32 mode's bounds."""
     path, W, g = netutil.model("yolov5n")
     x = netutil.coco_like_frames(1, seed=0)
     want = nets.yolov5_forward(x, W, "n")
-    e = CE.OnnxEngine(path, precision="fp32")
+    e = CE.OnnxEngine(path) if prec is None else CE.OnnxEngine(path, precision=prec)
+    assert e.precision == (prec or "fp16x3")
+    if prec is None:
+        netutil.assert_x3_convs(e, 1)
     got = e.engine_inference(x)[0]
     assert got.shape == want.shape == (1, 25200, 85)
     err = np.abs(got[..., 4:] - want[..., 4:]).max()
     berr = np.abs(got[..., :4] - want[..., :4]).max()
-    print("v5n fp32: score max|diff| %.3e, box max|diff| %.3e px" % (err, berr))
+    print("v5n %s: score max|diff| %.3e, box max|diff| %.3e px, rel %.3e" % (e.precision, err, berr, rel_l2(got, want)))
     # boxes are in input pixels (up to (2*sigmoid)^2 * 373 px): bound relative to their magnitude
     assert err <= 1e-3 and berr <= 1e-3 * max(1.0, float(np.abs(want[..., :4]).max()))
     e.close()
@@ -140,7 +145,7 @@ def test_hipengine_loads_a_real_onnx_file(CE, tmp_path):
     e1.close(); e2.close()
 
 
-@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16x3"])
 def test_ufldv2_tusimple_variant_vs_oracle(CE, prec):
     """Tusimple configuration (configs/tusimple_res18.py: 800x320, 100/100 cells, 56/41 anchors, fc_norm=False): the 1x1 `pool`
     conv output is re-viewed as the flat FC input through a buffer alias instead of going through LayerNorm."""
@@ -154,15 +159,18 @@ def test_ufldv2_tusimple_variant_vs_oracle(CE, prec):
     got = e.engine_inference(x)
     for o, w, nm in zip(got, want, names):
         print(prec, nm, "max|diff| %.3e rel %.3e" % (np.abs(o - w).max(), rel_l2(o, w)))
-        if prec == "fp32":
-            assert np.abs(o - w).max() <= 1e-3
+        if prec in ("fp32", "fp16x3"):
+            assert np.abs(o - w).max() <= 1e-3 and (prec == "fp32" or rel_l2(o, w) <= 1e-5)
         else:
             assert rel_l2(o, w) <= 6e-2
+    if prec == "fp16x3":
+        netutil.assert_x3_convs(e, 3)
     e.close()
 
 
 @pytest.mark.parametrize("name,prec,G,K", [("ufld_v1_res18", "fp32", 100, 56), ("ufld_v1_res18", "bf16", 100, 56),
-                                           ("ufld_v1_culane_res18", "fp32", 200, 18)])
+                                           ("ufld_v1_culane_res18", "fp32", 200, 18), ("ufld_v1_res18", "fp16x3", 100, 56),
+                                           ("ufld_v1_culane_res18", "fp16x3", 200, 18)])
 def test_ufld_v1_vs_oracle(CE, name, prec, G, K):
     """UFLD v1 network (800x288 -> one (1, G+1, K, 4) tensor, ultrafastLaneDetector.py:73-75,99) vs the torch fp32 restatement."""
     path, W, g = netutil.model(name)
@@ -174,8 +182,10 @@ def test_ufld_v1_vs_oracle(CE, name, prec, G, K):
     assert shapes == [[1, G + 1, K, 4]] and len(names) == 1
     got = e.engine_inference(x)[0]
     print(name, prec, "max|diff| %.3e rel %.3e" % (np.abs(got - want).max(), rel_l2(got, want)))
-    if prec == "fp32":
-        assert np.abs(got - want).max() <= 1e-3
+    if prec == "fp16x3":
+        netutil.assert_x3_convs(e, 2)
+    if prec in ("fp32", "fp16x3"):
+        assert np.abs(got - want).max() <= 1e-3 and (prec == "fp32" or rel_l2(got, want) <= 1e-5)
     else:
         assert rel_l2(got, want) <= 6e-2
     e.close()

@@ -105,18 +105,21 @@ def test_pipeline_step_from_camera_frames(tmp_path):
     pa.close(); pb.close(); dt.free(); lt.free()
 
 
-def test_pipeline_with_ufld_v1_lane_model():
-    """The fused step with a UFLD v1 lane model (one output tensor, v1 decoder): lane results equal the stand-alone path."""
+@pytest.mark.parametrize("prec", ["bf16", "fp16x3"])
+def test_pipeline_with_ufld_v1_lane_model(prec):
+    """The fused step with a UFLD v1 lane model (one output tensor, v1 decoder): lane results equal the stand-alone path, in a
+    throughput mode and in the split precision."""
     from oracle import ufld_decode as UD
     S = 2
     lane_path, _, _ = netutil.model("ufld_v1_res18")
     c = UD.ModelConfigV1("tusimple")
     cfg = dict(griding_num=c.griding_num, cls_num_per_lane=c.cls_num_per_lane, img_w=c.img_w, img_h=c.img_h, row_anchor=c.row_anchor)
-    pipe = PL.AdasPipeline(None, lane_path, n_streams=S, precision="bf16", src_hw=(720, 1280), use_graph=True, lane_cfg=cfg, track=False)
+    pipe = PL.AdasPipeline(None, lane_path, n_streams=S, precision=prec, src_hw=(720, 1280), use_graph=True, lane_cfg=cfg, track=False)
+    assert pipe.lane.precision == prec
     x = netutil.lane_frames(S, 288, 800, seed=5)
     dx = L.DeviceBuffer.from_array(x)
     pipe.step(None, dx.ptr); pipe.sync()
-    eng = CE.HipEngine(lane_path, "bf16", S)
+    eng = CE.HipEngine(lane_path, prec, S)
     dec = PP.Ufld1Decode(c.griding_num, c.cls_num_per_lane, c.img_w, c.img_h, 800, 288, 1280, 720, c.row_anchor, S)
     want = dec.run_host(eng.engine_inference(x)[0])
     for s in range(S):

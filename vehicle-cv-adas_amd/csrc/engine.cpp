@@ -611,8 +611,11 @@ int adas_engine_create(const char* model_path, int precision, int max_batch, ada
             }
             if (q2.out_buf == q1.in_buf[0] && q2.out_coff < q1.in_coff[0] + q1.in_c[0] && q1.in_coff[0] < q2.out_coff + q2.out_c) safe = false;
             if (!safe) continue;
-            const EngBuf& xb = e->bufs[q1.in_buf[0]];   // conv_c2f.hip addresses the input with 31-bit byte offsets: decided here, at max_batch
-            if ((double)max_batch * xb.h * xb.w * xb.c * 2.0 >= 2147483648.0) continue;
+            // conv_c2f.hip / conv_c2f_x3.hip address the input with 31-bit byte offsets (2 / 4 bytes per element): decided here, at
+            // max_batch, so the engine never records a fusion its launcher refuses at run time
+            const EngBuf& xb = e->bufs[q1.in_buf[0]];
+            const double elem = precision == PREC_X3 ? 4.0 : 2.0;
+            if ((double)max_batch * xb.h * xb.w * xb.c * elem >= 2147483648.0) continue;
         }
         {
             const TView vx = make_view(e, q1.in_buf[0], q1.in_coff[0], q1.in_c[0]), v01 = make_view(e, q1.out_buf, q1.out_coff, q1.out_c);
