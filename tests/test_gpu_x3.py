@@ -304,11 +304,13 @@ def test_c2f_block_in_one_launch_f32_class(case):
     assert rel < 3 * X3_REL, (case, rel)
 
 
-@pytest.mark.parametrize("case", [(640, 640, 3, 1, 2), (70, 90, 3, 1, 3), (96, 200, 6, 2, 40), (33, 47, 6, 2, 2)], ids=str)
+@pytest.mark.parametrize("case", [(640, 640, 3, 1, 2), (70, 90, 3, 1, 3), (96, 200, 6, 2, 40), (33, 47, 6, 2, 2),
+                                  (64, 96, 3, 0, 2), (62, 70, 6, 0, 3)], ids=str)
 def test_stem_with_its_second_conv_in_one_launch_f32_class(case):
     """conv_stem2_x3_kernel: the YOLO stem (3x3 / 6x6 s2, 3 -> 16, SiLU) and the 3x3 s2 conv behind it (16 -> 32, SiLU: model.1) as one
     launch in the split precision -- the stem tile lives in LDS as a hi and a lo plane, the 16-channel tensor never reaches HBM.  Full
-    and ragged extents (odd stem / conv2 sizes: tiles cut by both images' edges), more tiles than workgroups (96 x 200 at batch 40)."""
+    and ragged extents (odd stem / conv2 sizes: tiles cut by both images' edges), more tiles than workgroups (96 x 200 at batch 40), pad 0
+    for both stem sizes."""
     import os, tempfile
     import torch
     import torch.nn.functional as F
@@ -320,7 +322,7 @@ def test_stem_with_its_second_conv_in_one_launch_f32_class(case):
     t = g.conv(y, 32, 3, 2, "second", act=M.ACT_SILU)
     z = g.conv(t, 8, 1, 1, "tap", act=M.ACT_NONE, f32_out=True)
     g.output(z, 0, [1, z.h * z.w * 8], "o")
-    path = os.path.join(tempfile.gettempdir(), f"stem2unit_{H}_{W}_{k}.hipm")
+    path = os.path.join(tempfile.gettempdir(), f"stem2unit_{H}_{W}_{k}_{pad}.hipm")
     g.save(path)
     e = CE.HipEngine(path, "fp16x3", batch)
     xin = np.random.default_rng(4).uniform(0, 1, (batch, 3, H, W)).astype(np.float32)

@@ -1264,6 +1264,10 @@ hipError_t launch_detect_v6(const TView* ins, float* out, int n, int nc, int A, 
 }
 
 // ------------------------------------------------------------------------------------- LayerNorm
+// Two passes, both relative to a pivot: the row's first element p.  d = x - p is exact for x within a factor of two of p, and the mean
+// m and every deviation d - m are then resolved at the scale of the row's spread, not of its offset.  Relative to zero, an fp32 mean
+// of ~100 carries a rounding of up to 3.8e-6, and each x - mean inherits it: on a row at 100 with spread 1 that put 4e-6..1e-5 rel-L2
+// into the output; with the pivot it is 1e-7 at any offset (tests/test_gpu_x3_stems.py::test_layernorm_kernel).
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, T* __restrict__ out,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -1272,16 +1276,17 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const float* x = in + (size_t)blockIdx.x * len;
     T* y = out + (size_t)blockIdx.x * len;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float p = x[0];
     float s = 0.f;
-    for (int i = tid; i < len; i += 256) s += x[i];
+    for (int i = tid; i < len; i += 256) s += x[i] - p;
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if (lane == 0) red[wv] = s;
     __syncthreads();
-    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)len;
+    const float m = (red[0] + red[1] + red[2] + red[3]) / (float)len;   // mean - p
     __syncthreads();
     float v = 0.f;
     for (int i = tid; i < len; i += 256) {
-        float dlt = x[i] - mean;
+        float dlt = (x[i] - p) - m;
         v += dlt * dlt;
     }
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -1289,7 +1294,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     __syncthreads();
     const float var = (red[4] + red[5] + red[6] + red[7]) / (float)len;
     const float rstd = 1.0f / sqrtf(var + eps);
-    for (int i = tid; i < len; i += 256) st<T>(y + i, (x[i] - mean) * rstd * gamma[i] + beta[i]);
+    for (int i = tid; i < len; i += 256) st<T>(y + i, ((x[i] - p) - m) * rstd * gamma[i] + beta[i]);
 }
 hipError_t launch_layernorm(const float* in, void* out, const float* gamma, const float* beta, int n, int len, float eps,
                             int prec, hipStream_t st_) {
