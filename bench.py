@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end frames/s of the per-frame ADAS path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--streams S] [--det yolov8n] [--lane ufldv2_res18] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--streams S] [--det yolov8n] [--lane ufldv2_res18] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it builds and calibrates the models, draws the frames, warms up, times the K
+steps, checks that no timed frame overflowed the candidate arena, writes --dump-outputs and prints the line.  `--full` adds every
+other measurement after the timed steps, in this order: the repeats of the timed loop, the step latency distribution, the per-layer
+roofline pass (with its rocprofv3 child runs), the per-stage breakdown, the parity and end-to-end legs against the fp32 oracle, the
+post-processing HBM rates, the unfiltered / host-ingest / frame-at-a-time legs, the other precisions and the CPU baseline.  In a plain
+run those fields of the line are null; `value`, `ms_per_step` and the dumped arrays are the same in both.
 
 One "step" = one frame of each of S independent video streams through the whole hot path on one GPU:
 u8 camera frames (resident in HBM) -> letterbox / resize / normalise -> detector forward -> decode/letterbox/NMS -> ByteTrack
@@ -17,7 +24,7 @@ Precision: the EXACT mode by default (round 6): fp16x3 -- every value a (hi, lo)
 accumulate -- the mode whose every discrete decision (candidate sets, NMS survivors, track ids, lane cells) equals the fp32 oracle
 chain's on the timed frames; `value` / `dtype` are that mode's.  `--precision fp16|bf16` are the throughput modes (what the reference
 ships as *_fp16.trt, demo.py:18-29), `--precision fp32` the f32-MFMA mode.  The line carries `parity` (this run's own model outputs
-against the fp32 oracle), `modes` (frames/s of the other precisions on the same workload) and `config.fp16_value`.
+against the fp32 oracle), `modes` (frames/s of the other precisions on the same workload) and `config.fp16_value` (all three with --full).
 """
 import argparse
 import importlib
@@ -371,7 +378,7 @@ def measure_traffic_pmc(dom_label, args):
             d = tempfile.mkdtemp(prefix="adas_pmc_")
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
                    "--preset", args.preset, "--precision", args.precision, "--streams", str(args.streams), "--micro-batch", str(args.micro_batch),
-                   "--det", args.det, "--lane", args.lane, "--no-cpu-baseline", "--no-extras", "--no-overlap", "--steps", "3", "--warmup", "1",
+                   "--det", args.det, "--lane", args.lane, "--full", "--no-cpu-baseline", "--no-extras", "--no-overlap", "--steps", "3", "--warmup", "1",
                    "--repeats", "0", "--latency-steps", "8"]
             env = dict(os.environ, TMPDIR="/tmp", ADAS_BENCH_NO_PMC="1")
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=150, check=False)
@@ -394,7 +401,7 @@ def measure_traffic_pmc(dom_label, args):
         d = tempfile.mkdtemp(prefix="adas_kt_")
         cmd = [exe, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
                "--preset", args.preset, "--precision", args.precision, "--streams", str(args.streams), "--micro-batch", str(args.micro_batch),
-               "--det", args.det, "--lane", args.lane, "--no-cpu-baseline", "--no-extras", "--no-overlap", "--steps", "10", "--warmup", "3",
+               "--det", args.det, "--lane", args.lane, "--full", "--no-cpu-baseline", "--no-extras", "--no-overlap", "--steps", "10", "--warmup", "3",
                "--repeats", "0", "--latency-steps", "8"]
         env = dict(os.environ, TMPDIR="/tmp", ADAS_BENCH_NO_PMC="1")
         subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=150, check=False)
@@ -412,7 +419,7 @@ def measure_traffic_pmc(dom_label, args):
     return int(round(hbm)), {"collected": "in this run", "avg_launch_us_rocprof": (round(dur_us, 2) if dur_us else None), "rocprof_dispatches": dur_n, "fetch_kib_raw": round(tot["FETCH_SIZE"][0], 1), "write_kib_raw": round(tot["WRITE_SIZE"][0], 1),
                              "dispatches_sampled": [tot["FETCH_SIZE"][1], tot["WRITE_SIZE"][1]], "kernel_pattern": pat,
                              "seconds": round(time.perf_counter() - t0, 1),
-                             "method": "two child runs of bench.py (--no-overlap --steps 3 --no-extras) under rocprofv3 --pmc FETCH_SIZE / "
+                             "method": "two child runs of bench.py (--full --no-overlap --steps 3 --no-extras) under rocprofv3 --pmc FETCH_SIZE / "
                                        "--pmc WRITE_SIZE (+ --kernel-trace), per-dispatch average of the dominant kernel; "
                                        "FETCH_SIZE x2 (gfx950 16 B/lane correction), WRITE_SIZE as reported, KiB -> bytes"}
 
@@ -517,7 +524,7 @@ def idle_rank(SH, dist, args, stat_dev, pin):
             dist.barrier()
     barrier()                                    # the headline loop's barrier (timed_loop)
     SH.max_over_ranks(0.0, dist, stat_dev)       # ... its clock reduction
-    for _ in range(max(0, args.repeats)):        # ... one barrier per repeat of the loop
+    for _ in range(max(0, args.repeats) if args.full else 0):   # ... one barrier per repeat of the loop (--full only)
         barrier()
     SH.gather_stats({"frames": 0.0, "seconds": 0.0, "p50_ms": 0.0, "p99_ms": 0.0, "streams": 0.0, "numa_node": float(pin["numa_node"]),
                      "cpus": float(pin["cpus"]), "pinned": float(bool(pin["pinned"]))}, STAT_KEYS, dist, stat_dev)
@@ -587,6 +594,123 @@ def timed_loop(one_step, steps, warmup, sync, barrier):
     return time.perf_counter() - t0
 
 
+def measure_roofline(pipe, d_det, d_lane, S, args, rank, world, fps, flops_frame):
+    """--full: the per-layer hipEvent pass (events on the stream the kernels are launched on) over the timed batch, grouped by the kernel
+    instantiation each conv layer resolves to; the dominant kernel = most device time (its HBM bytes and rocprofv3 durations from
+    measure_traffic_pmc's child runs).  -> (the line's `roofline` block, {layer: (ms, kernel label)}, kernel launches per step)."""
+    conv_ms, conv_flops, all_ms = 0.0, 0.0, 0.0
+    by_kernel = {}
+    layer_ms = {}
+    n_launches = 0
+    for eng, dptr in ((pipe.det, d_det[0].ptr), (pipe.lane, d_lane[0].ptr)):
+        eng.profile(dptr, S, iters=3)            # the device idled while the stats were fetched: let the clocks come back first
+        stem_label = pair_label = c2f_label = ml_label = None
+        pending_shortcut = 0.0
+        for li, (name, fl, kind, ms) in enumerate(eng.profile(dptr, S, iters=10)):
+            all_ms += ms
+            raw_label = eng.layer_kernel(li, S)
+            layer_ms[name] = (ms, raw_label)
+            label = raw_label.replace("+shortcut", "")   # same kernel with the block's projection folded in
+            if not label.startswith("("):   # "(fused into ...)" / "(folded into ...)": no launch of its own
+                n_launches += 1
+            if kind == 1:   # OP_CONV
+                if label.startswith("(fused into the Detect"):
+                    continue            # runs inside the Detect launch (not a conv kernel): its FLOPs are left out of the conv totals
+                if label.startswith("(fused into the conv it is the shortcut of"):
+                    pending_shortcut += fl * S      # a 1x1 projection computed by the "+shortcut" launch behind it
+                    continue
+                launches = 1
+                if label.startswith("(fused into the stem") and stem_label:
+                    label, launches = stem_label, 0   # the stem launch does this layer's work: its FLOPs belong to that launch
+                elif label.startswith("(fused into the pair") and pair_label:
+                    label, launches = pair_label, 0   # second conv of a 3x3 -> 3x3 pair: computed by the first conv's launch
+                elif label.startswith("(fused into the C2f") and c2f_label:
+                    label, launches = c2f_label, 0    # Bottleneck pair / closing 1x1 of a C2f block computed by its cv1's launch
+                elif label.startswith(("(in the multi-layer", "(in the grouped launch")) and ml_label:
+                    label, launches = ml_label, 0     # a member of a multi-layer persistent launch (conv_ml.hip): its FLOPs belong to that launch
+                elif label.startswith("(fused into"):
+                    continue                          # fused into a neighbouring conv launch that reports the FLOPs itself
+                elif label.startswith("conv_stem"):
+                    stem_label = label
+                elif label.startswith("conv_pair_kernel"):
+                    pair_label = label
+                elif label.startswith("conv_c2f16"):
+                    c2f_label = label
+                elif label.startswith(("conv_ml_kernel", "conv_halo_group_kernel")):
+                    ml_label = label
+                extra = 0.0
+                if raw_label.endswith("+shortcut"):
+                    extra, pending_shortcut = pending_shortcut, 0.0
+                conv_ms += ms
+                conv_flops += fl * S + extra
+                k = by_kernel.setdefault(label, [0.0, 0.0, 0])
+                k[0] += ms; k[1] += fl * S + extra; k[2] += launches
+    achieved_all = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    dom_name, (dom_ms, dom_fl, dom_n) = max(by_kernel.items(), key=lambda kv: kv[1][0])
+    achieved = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+    top = sorted(by_kernel.items(), key=lambda kv: -kv[1][0])[:6]
+    traffic, traffic_src = None, None
+    if rank == 0 and world == 1 and not args.no_extras and os.environ.get("ADAS_BENCH_NO_PMC") != "1":
+        traffic, traffic_src = measure_traffic_pmc(dom_name, args)
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")       # fallback: the figure tools/gpu_round.sh collected at a stated commit
+    if traffic is None and os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("kernel") == dom_name and tj.get("streams") == S and tj.get("precision", "bf16") == args.precision:
+                traffic = tj.get("hbm_bytes_per_launch")
+                traffic_src = {"file": "profiles/traffic.json", "commit": tj.get("commit"), "collected": tj.get("collected"),
+                               "note": "PMC counters need rocprofv3 around the process: collected by tools/gpu_round.sh on this workload, "
+                                       "not in this run"}
+        except Exception:
+            traffic = None
+    rp_us = (traffic_src or {}).get("avg_launch_us_rocprof") if isinstance(traffic_src, dict) else None
+    dom_us_rp = rp_us if rp_us else dom_ms / dom_n * 1e3
+    achieved_rp = (dom_fl / dom_n) / (dom_us_rp * 1e-6) / 1e12 if dom_us_rp > 0 else 0.0
+    roof = {"bound": "mfma", "achieved": round(achieved_rp, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved_rp / PEAK_BF16_TFLOPS, 5), "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": dom_name, "launches_per_step": dom_n, "avg_launch_us": round(dom_us_rp, 2),
+            "avg_launch_us_rocprof": rp_us, "avg_launch_us_hipevent": round(dom_ms / dom_n * 1e3, 2),
+            "frac_hipevent": round(achieved / PEAK_BF16_TFLOPS, 5),
+            "duration_source": ("rocprofv3 --kernel-trace dispatch durations of this kernel, collected by a child run of this command (nets on one "
+                                "stream); the hipEvent figure is kept beside it" if rp_us else
+                                "hipEvents around the layers (no rocprofv3 figure in this run: --no-extras, N > 1, or rocprofv3 missing)"),
+            "gflop_per_launch": round(dom_fl / dom_n / 1e9, 3),
+            "peak_note": "dense 16-bit MFMA peak (bf16 and fp16 run at the same rate); fp32 mode uses the 1/16-rate f32 MFMA",
+            "method": "algorithmic conv FLOPs (2*MACs, SURVEY 8d) of the layers that launch this kernel / their summed "
+                      "launch durations (hipEvents around every layer on the launch stream, eager pass on the same "
+                      "batch after the timed region; nets NOT overlapped in this pass -- the matching rocprofv3 summary is "
+                      "profiles/rNN/bench_no_overlap_kernel_stats.csv, the default command's is bench_default_kernel_stats.csv)",
+            "all_conv_kernels_tflops": round(achieved_all, 2), "all_conv_frac": round(achieved_all / PEAK_BF16_TFLOPS, 5),
+            "conv_ms_per_step": round(conv_ms, 4), "all_layers_ms_per_step": round(all_ms, 4),
+            "end_to_end_tflops": round(flops_frame * fps / world / 1e12, 2),
+            "top_kernels": [{"kernel": k, "ms": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 else 0.0,
+                             "launches": v[2]} for k, v in top]}
+    if args.precision == "fp16x3":   # split precision: three f16 MFMAs per multiply-add of the algorithmic count
+        roof["mfma_products_per_mac"] = 3
+        roof["mfma_issue_frac"] = round(3.0 * achieved / PEAK_BF16_TFLOPS, 5)
+        roof["peak_note"] += "; fp16x3 issues 3 MFMAs per algorithmic multiply-add: `frac` counts algorithmic FLOPs, `mfma_issue_frac` the MFMA work"
+    return roof, layer_ms, n_launches
+
+
+def measure_stages(L, pipe, d_det, d_lane, NSTREAMS, B):
+    """--full: a second eager pass with section events for a per-stage breakdown (informational: an error is reported, not raised)."""
+    import ctypes as C
+    try:
+        d = L.PipelineDesc(pipe.det.handle, pipe.lane.handle, pipe.post.h, pipe.decode.h, pipe.tracker.h, NSTREAMS, 0, None, B if B > 1 else 0, 0)
+        h = C.c_void_p()
+        L.check(L.lib().adas_pipeline_create(C.byref(d), C.byref(h)))
+        for _ in range(2):
+            L.check(L.lib().adas_pipeline_step(h.value, d_det[0].ptr, d_lane[0].ptr))
+        ms = (C.c_float * 6)()
+        L.check(L.lib().adas_pipeline_timings(h.value, ms))
+        stage = dict(zip(("det_net_ms", "det_post_ms", "lane_net_ms", "lane_decode_ms", "tracker_ms", "step_ms"),
+                         [round(float(v), 4) for v in ms]))
+        L.lib().adas_pipeline_destroy(h.value)
+    except Exception as ex:  # breakdown is informational only
+        stage = {"error": str(ex)}
+    return stage
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -604,14 +728,17 @@ def main():
                     help="default: fp16x3, the exact mode (every decision of the fp32 oracle chain reproduced); fp16 / bf16 = throughput modes")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-overlap", action="store_true", help="keep detector and lane nets on one HIP stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity / other-precision / host-ingest legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, take every measurement besides the headline (repeats, "
+                    "step latency, roofline, stages, parity, other precisions, CPU baseline: see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the parity / other-precision / host-ingest legs (profiling runs)")
     ap.add_argument("--from-seam", action="store_true", help="start each step at the engine seam (pre-processed NCHW fp32 tensors resident "
                     "in HBM) instead of at the u8 camera frames")
     ap.add_argument("--candidates", type=float, default=100.0, help="anchors over box_score on the median generated frame (the detector's class "
                     "bias is calibrated to it); frames outside [8, 0.7 * capacity] are not used")
-    ap.add_argument("--repeats", type=int, default=5, help="repeats of the --steps loop after the headline one (min / median / max reported)")
-    ap.add_argument("--latency-steps", type=int, default=40, help="individually synchronised steps for the p50 / p99 step latency")
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: repeats of the --steps loop after the headline one (min / median / "
+                    "max reported)")
+    ap.add_argument("--latency-steps", type=int, default=40, help="with --full: individually synchronised steps for the p50 / p99 step latency")
     ap.add_argument("--pool", type=int, default=2, help="distinct frame sets cycled through")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
                     "(detections, candidates, tracks, lanes) as float64 .npy files to DIR (rank 0), e.g. bench_outputs/")
@@ -770,22 +897,23 @@ def main():
         last_set = ((args.steps - 1) // H) % P if args.steps > 0 else None
         last_cam = h_cam[last_set] if from_frames and last_set is not None else None
         dumped = dump_outputs(args.dump_outputs, pipe, L, PP, S, NSTREAMS, B, last_cam, t_cal, sd.sharpen)
-    # ---- after the headline: the same loop REPEATS more times (box-to-box and run-to-run spread of `value`), then the step latency
-    # distribution (every step synchronised: p50 / p99 of launch-to-completion, SURVEY 8e's per-rank statistics)
-    rep_fps = []
-    for _ in range(max(0, args.repeats)):
-        t_r = timed_loop(stepper(pipe), args.steps, 1, full_sync(pipe), barrier)
-        rep_fps.append(args.steps * S / t_r)
-    lat = []
-    sync_ = full_sync(pipe)
-    one_ = stepper(pipe)
-    for i in range(max(8, args.latency_steps)):
-        t0 = time.perf_counter()
-        one_(i)
-        sync_()
-        lat.append((time.perf_counter() - t0) * 1e3)
-    lat = np.sort(np.asarray(lat[2:]))
-    p50, p99 = float(np.percentile(lat, 50)), float(np.percentile(lat, 99))
+    # ---- --full, after the headline: the same loop REPEATS more times (box-to-box and run-to-run spread of `value`), then the step
+    # latency distribution (every step synchronised: p50 / p99 of launch-to-completion, SURVEY 8e's per-rank statistics)
+    rep_fps, lat, p50, p99 = [], None, 0.0, 0.0
+    if args.full:
+        for _ in range(max(0, args.repeats)):
+            t_r = timed_loop(stepper(pipe), args.steps, 1, full_sync(pipe), barrier)
+            rep_fps.append(args.steps * S / t_r)
+        lat = []
+        sync_ = full_sync(pipe)
+        one_ = stepper(pipe)
+        for i in range(max(8, args.latency_steps)):
+            t0 = time.perf_counter()
+            one_(i)
+            sync_()
+            lat.append((time.perf_counter() - t0) * 1e3)
+        lat = np.sort(np.asarray(lat[2:]))
+        p50, p99 = float(np.percentile(lat, 50)), float(np.percentile(lat, 99))
     per_rank = SH.gather_stats({"frames": float(args.steps * S), "seconds": local_elapsed, "p50_ms": p50, "p99_ms": p99, "streams": float(NSTREAMS),
                                 "numa_node": float(pin["numa_node"]), "cpus": float(pin["cpus"]), "pinned": float(bool(pin["pinned"]))},
                                STAT_KEYS, dist, stat_dev)
@@ -815,94 +943,16 @@ def main():
     hdrs = [pipe.tracker.fetch(s)[0] for s in range(min(NSTREAMS, 8))]
     n_trk = float(np.mean([h.n_tracked for h in hdrs]))
     n_lost = float(np.mean([h.n_lost for h in hdrs]))
+    frames = sum(r["frames"] for r in per_rank)      # = steps * S * world when every rank owns the same number of streams
+    fps = frames / elapsed
+    flops_frame = pipe.flops_per_frame()
 
-    # ---- roofline: per-layer hipEvent pass (events on the stream the kernels are launched on) over the same batch,
-    # grouped by the kernel instantiation each conv layer resolves to; the dominant kernel = most device time.
-    conv_ms, conv_flops, all_ms = 0.0, 0.0, 0.0
-    by_kernel = {}
-    layer_ms = {}
-    n_launches = 0
-    for eng, dptr in ((pipe.det, d_det[0].ptr), (pipe.lane, d_lane[0].ptr)):
-        eng.profile(dptr, S, iters=3)            # the device idled while the stats were fetched: let the clocks come back first
-        stem_label = pair_label = c2f_label = ml_label = None
-        pending_shortcut = 0.0
-        for li, (name, fl, kind, ms) in enumerate(eng.profile(dptr, S, iters=10)):
-            all_ms += ms
-            raw_label = eng.layer_kernel(li, S)
-            layer_ms[name] = (ms, raw_label)
-            label = raw_label.replace("+shortcut", "")   # same kernel with the block's projection folded in
-            if not label.startswith("("):   # "(fused into ...)" / "(folded into ...)": no launch of its own
-                n_launches += 1
-            if kind == 1:   # OP_CONV
-                if label.startswith("(fused into the Detect"):
-                    continue            # runs inside the Detect launch (not a conv kernel): its FLOPs are left out of the conv totals
-                if label.startswith("(fused into the conv it is the shortcut of"):
-                    pending_shortcut += fl * S      # a 1x1 projection computed by the "+shortcut" launch behind it
-                    continue
-                launches = 1
-                if label.startswith("(fused into the stem") and stem_label:
-                    label, launches = stem_label, 0   # the stem launch does this layer's work: its FLOPs belong to that launch
-                elif label.startswith("(fused into the pair") and pair_label:
-                    label, launches = pair_label, 0   # second conv of a 3x3 -> 3x3 pair: computed by the first conv's launch
-                elif label.startswith("(fused into the C2f") and c2f_label:
-                    label, launches = c2f_label, 0    # Bottleneck pair / closing 1x1 of a C2f block computed by its cv1's launch
-                elif label.startswith(("(in the multi-layer", "(in the grouped launch")) and ml_label:
-                    label, launches = ml_label, 0     # a member of a multi-layer persistent launch (conv_ml.hip): its FLOPs belong to that launch
-                elif label.startswith("(fused into"):
-                    continue                          # fused into a neighbouring conv launch that reports the FLOPs itself
-                elif label.startswith("conv_stem"):
-                    stem_label = label
-                elif label.startswith("conv_pair_kernel"):
-                    pair_label = label
-                elif label.startswith("conv_c2f16"):
-                    c2f_label = label
-                elif label.startswith(("conv_ml_kernel", "conv_halo_group_kernel")):
-                    ml_label = label
-                extra = 0.0
-                if raw_label.endswith("+shortcut"):
-                    extra, pending_shortcut = pending_shortcut, 0.0
-                conv_ms += ms
-                conv_flops += fl * S + extra
-                k = by_kernel.setdefault(label, [0.0, 0.0, 0])
-                k[0] += ms; k[1] += fl * S + extra; k[2] += launches
-    achieved_all = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    dom_name, (dom_ms, dom_fl, dom_n) = max(by_kernel.items(), key=lambda kv: kv[1][0])
-    achieved = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-    top = sorted(by_kernel.items(), key=lambda kv: -kv[1][0])[:6]
-    traffic, traffic_src = None, None
-    if rank == 0 and world == 1 and not args.no_extras and os.environ.get("ADAS_BENCH_NO_PMC") != "1":
-        traffic, traffic_src = measure_traffic_pmc(dom_name, args)
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")       # fallback: the figure tools/gpu_round.sh collected at a stated commit
-    if traffic is None and os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("kernel") == dom_name and tj.get("streams") == S and tj.get("precision", "bf16") == args.precision:
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_src = {"file": "profiles/traffic.json", "commit": tj.get("commit"), "collected": tj.get("collected"),
-                               "note": "PMC counters need rocprofv3 around the process: collected by tools/gpu_round.sh on this workload, "
-                                       "not in this run"}
-        except Exception:
-            traffic = None
-    rp_us = (traffic_src or {}).get("avg_launch_us_rocprof") if isinstance(traffic_src, dict) else None
-    dom_us_rp = rp_us if rp_us else dom_ms / dom_n * 1e3
-    achieved_rp = (dom_fl / dom_n) / (dom_us_rp * 1e-6) / 1e12 if dom_us_rp > 0 else 0.0
-    # second eager pass with section events for a per-stage breakdown
-    stage = None
-    try:
-        d = L.PipelineDesc(pipe.det.handle, pipe.lane.handle, pipe.post.h, pipe.decode.h, pipe.tracker.h, NSTREAMS, 0, None, B if B > 1 else 0, 0)
-        h = C.c_void_p()
-        L.check(L.lib().adas_pipeline_create(C.byref(d), C.byref(h)))
-        for _ in range(2):
-            L.check(L.lib().adas_pipeline_step(h.value, d_det[0].ptr, d_lane[0].ptr))
-        ms = (C.c_float * 6)()
-        L.check(L.lib().adas_pipeline_timings(h.value, ms))
-        stage = dict(zip(("det_net_ms", "det_post_ms", "lane_net_ms", "lane_decode_ms", "tracker_ms", "step_ms"),
-                         [round(float(v), 4) for v in ms]))
-        L.lib().adas_pipeline_destroy(h.value)
-    except Exception as ex:  # breakdown is informational only
-        stage = {"error": str(ex)}
+    roof = layer_ms = n_launches = stage = None
+    if args.full:
+        roof, layer_ms, n_launches = measure_roofline(pipe, d_det, d_lane, S, args, rank, world, fps, flops_frame)
+        stage = measure_stages(L, pipe, d_det, d_lane, NSTREAMS, B)
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     parity = None
     post_hbm = unfiltered = None
     if extras:
@@ -983,9 +1033,6 @@ def main():
         except Exception as ex:
             frame_at_a_time = {"error": repr(ex)}
 
-    frames = sum(r["frames"] for r in per_rank)      # = steps * S * world when every rank owns the same number of streams
-    fps = frames / elapsed
-    flops_frame = pipe.flops_per_frame()
     pipe.close()
 
     # ---- the other precisions on the same workload (same models, frames, steps): the line that meets 1e-3 absolutely (fp32)
@@ -1047,44 +1094,24 @@ def main():
                    "inputs": ("1280x720 BGR u8 camera frames resident in HBM; letterbox/resize/normalise for both nets run inside the step"
                               if from_frames else "engine-seam NCHW fp32 tensors resident in HBM (pre-processing outside the step)"),
                    "frame_selection": sel, "model_build_s": round(t_build, 1)},
-        "roofline": {"bound": "mfma", "achieved": round(achieved_rp, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved_rp / PEAK_BF16_TFLOPS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": dom_name, "launches_per_step": dom_n, "avg_launch_us": round(dom_us_rp, 2),
-                     "avg_launch_us_rocprof": rp_us, "avg_launch_us_hipevent": round(dom_ms / dom_n * 1e3, 2),
-                     "frac_hipevent": round(achieved / PEAK_BF16_TFLOPS, 5),
-                     "duration_source": ("rocprofv3 --kernel-trace dispatch durations of this kernel, collected by a child run of this command (nets on one "
-                                         "stream); the hipEvent figure is kept beside it" if rp_us else
-                                         "hipEvents around the layers (no rocprofv3 figure in this run: --no-extras, N > 1, or rocprofv3 missing)"),
-                     "gflop_per_launch": round(dom_fl / dom_n / 1e9, 3),
-                     "peak_note": "dense 16-bit MFMA peak (bf16 and fp16 run at the same rate); fp32 mode uses the 1/16-rate f32 MFMA",
-                     "method": "algorithmic conv FLOPs (2*MACs, SURVEY 8d) of the layers that launch this kernel / their summed "
-                               "launch durations (hipEvents around every layer on the launch stream, eager pass on the same "
-                               "batch after the timed region; nets NOT overlapped in this pass -- the matching rocprofv3 summary is "
-                               "profiles/rNN/bench_no_overlap_kernel_stats.csv, the default command's is bench_default_kernel_stats.csv)",
-                     "all_conv_kernels_tflops": round(achieved_all, 2), "all_conv_frac": round(achieved_all / PEAK_BF16_TFLOPS, 5),
-                     "conv_ms_per_step": round(conv_ms, 4), "all_layers_ms_per_step": round(all_ms, 4),
-                     "end_to_end_tflops": round(flops_frame * fps / world / 1e12, 2),
-                     "top_kernels": [{"kernel": k, "ms": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1) if v[0] > 0 else 0.0,
-                                      "launches": v[2]} for k, v in top]},
+        "roofline": roof,
         "host_ingest": host_ingest,
         "dumped_outputs": dumped,
         "repeats": ({"n": len(rep_fps), "fps_min": round(min(rep_fps), 1), "fps_median": round(float(np.median(rep_fps)), 1),
                      "fps_max": round(max(rep_fps), 1), "what": "the --steps loop again after the headline one, same process (rank 0)"}
                     if rep_fps else None),
-        "step_latency_ms": {"p50": round(p50, 4), "p99": round(p99, 4), "steps": int(len(lat)),
-                            "what": "one step launched and synchronised at a time (rank 0): graph launch + device time"},
+        "step_latency_ms": ({"p50": round(p50, 4), "p99": round(p99, 4), "steps": int(len(lat)),
+                             "what": "one step launched and synchronised at a time (rank 0): graph launch + device time"}
+                            if lat is not None else None),
         "post_hbm": post_hbm,
         "frame_at_a_time": frame_at_a_time,
         "unfiltered": unfiltered,
-        "per_rank": [{"frames": r["frames"], "seconds": round(r["seconds"], 5), "p50_ms": round(r["p50_ms"], 4), "p99_ms": round(r["p99_ms"], 4),
+        "per_rank": [{"frames": r["frames"], "seconds": round(r["seconds"], 5),
+                      "p50_ms": round(r["p50_ms"], 4) if args.full else None, "p99_ms": round(r["p99_ms"], 4) if args.full else None,
                       "streams": int(r["streams"]), "numa_node": int(r["numa_node"]), "cpus": int(r["cpus"]), "pinned": bool(r["pinned"])}
                      for r in per_rank],
     }
-    if args.precision == "fp16x3":   # split precision: three f16 MFMAs per multiply-add of the algorithmic count
-        result["roofline"]["mfma_products_per_mac"] = 3
-        result["roofline"]["mfma_issue_frac"] = round(3.0 * achieved / PEAK_BF16_TFLOPS, 5)
-        result["roofline"]["peak_note"] += "; fp16x3 issues 3 MFMAs per algorithmic multiply-add: `frac` counts algorithmic FLOPs, `mfma_issue_frac` the MFMA work"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import yolo_post
         lb = yolo_post.letterbox_params((720, 1280), (640, 640))
         result["cpu_baseline"] = cpu_baseline(args.det, args.lane, Wd, Wl, dpool[0], lpool[0], lb, cams=h_cam[0] if from_frames else None)

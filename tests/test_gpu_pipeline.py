@@ -137,13 +137,14 @@ def test_bench_gpus_n_relaunches_n_ranks(tmp_path, split, frames_per_step, strea
     """`python bench.py --gpus 2` with no torchrun environment must re-execute itself under torch.distributed.run and print ONE line
     with n_gpus = 2 and two per-rank records.  Rehearsed on this 1-GPU box with both ranks sharing the device and gloo carrying
     the statistics (ADAS_BENCH_SHARE_GPU / ADAS_BENCH_BACKEND exist for exactly this); the driver's 8-GPU run takes the same path
-    with RCCL.  `--total-streams N` runs the stream router's uneven splits (13-over-8 in tests/test_multigpu_gloo.py) for real."""
+    with RCCL.  `--total-streams N` runs the stream router's uneven splits (13-over-8 in tests/test_multigpu_gloo.py) for real.  `--full`:
+    the repeats and latency steps after the headline loop are collectives an idle rank has to follow as well."""
     import json, os, subprocess, sys
     from conftest import ROOT
     env = dict(os.environ, ADAS_BENCH_BACKEND="gloo", ADAS_BENCH_SHARE_GPU="1", ADAS_MODEL_DIR=str(tmp_path))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", *split,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", *split, "--full",
                           "--no-cpu-baseline", "--precision", "fp16", "--repeats", "1", "--latency-steps", "8"], env=env, capture_output=True,
                          text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -160,6 +161,30 @@ def test_bench_gpus_n_relaunches_n_ranks(tmp_path, split, frames_per_step, strea
     assert r["cpu_baseline"] is None and r["modes"] is None          # single-rank legs are skipped with world > 1
     # every rank reports where its launching thread was pinned (N > 1 only): a share of the CPUs, or its GPU's NUMA node
     assert all(q["cpus"] >= 1 and isinstance(q["pinned"], bool) for q in r["per_rank"])
+
+
+def test_bench_plain_run_times_the_headline_only(tmp_path):
+    """Without --full, bench.py sets up, times the steps and prints the line: the fields of every other measurement are null, while
+    `value`, `ms_per_step` and the workload description are there.  Two ranks share the GPU over gloo with a 1-stream job, so the
+    idle rank has to follow the plain run's collectives (no repeat barriers) as well."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    env = dict(os.environ, ADAS_BENCH_BACKEND="gloo", ADAS_BENCH_SHARE_GPU="1", ADAS_MODEL_DIR=str(tmp_path))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--total-streams", "1"],
+                         env=env, capture_output=True, text=True, timeout=400)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 2 and [q["streams"] for q in r["per_rank"]] == [1, 0] and r["steps"] == 3 and r["warmup"] == 1
+    assert r["value"] > 0 and r["ms_per_step"] > 0 and r["unit"] == "frames/s" and r["higher_is_better"] is True and r["dtype"] == "fp16x3"
+    assert r["config"]["frames_per_step"] == 1 and r["config"]["frames_at_candidate_capacity"] == 0
+    for key in ("roofline", "repeats", "step_latency_ms", "stages", "parity", "modes", "post_hbm", "host_ingest", "frame_at_a_time",
+                "unfiltered", "cpu_baseline"):
+        assert r[key] is None, key
+    assert r["config"]["kernel_launches_per_step_nets"] is None and all(q["p50_ms"] is None for q in r["per_rank"])
 
 
 def test_pipeline_step_frames_host_equals_device_frames(tmp_path):

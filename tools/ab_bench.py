@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Same-box A/B of engine switches: runs `bench.py --no-cpu-baseline --no-extras` once per variant (the switches are environment variables
+"""Same-box A/B of engine switches: runs `bench.py --full --no-cpu-baseline --no-extras` once per variant (the switches are environment variables
 read once per process, so every variant is its own process), interleaved over `--rounds` passes so that clock / thermal drift hits all
 variants alike, and prints frames/s (median of the repeats of every pass) and the per-net stage times.
 
@@ -25,7 +25,7 @@ for v in a.variant:
 res = {name: [] for name, _ in variants}
 for r in range(a.rounds):
     for name, env in variants:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--preset", a.preset, "--no-cpu-baseline", "--no-extras", "--steps", str(a.steps),
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--preset", a.preset, "--full", "--no-cpu-baseline", "--no-extras", "--steps", str(a.steps),
                "--repeats", str(a.repeats)] + a.extra.split()
         p = subprocess.run(cmd, env=dict(os.environ, ADAS_BENCH_NO_PMC="1", **env), capture_output=True, text=True, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -5,7 +5,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import load_pkg
 load_pkg()
 L = importlib.import_module("adas_amd._lib")
-sys.argv = ["bench.py", "--no-cpu-baseline", "--steps", "20"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--steps", "20"] + sys.argv[1:]
 import runpy
 try:
     runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")

@@ -6,7 +6,7 @@ for v in 0 1; do
   python tools/profile_layers.py yolov8n --batch 64 --precision fp16x3 --top 100 > gpurun_out/s2x/layers_y8n_x3_off$v.txt 2>&1
   echo "== ADAS_NO_HALO_S2P_X3=$v"; head -1 gpurun_out/s2x/layers_ufld_x3_off$v.txt; grep k3s2 gpurun_out/s2x/layers_ufld_x3_off$v.txt | cut -c1-150
   head -1 gpurun_out/s2x/layers_y8n_x3_off$v.txt; grep k3s2 gpurun_out/s2x/layers_y8n_x3_off$v.txt | cut -c1-150
-  ADAS_BENCH_NO_PMC=1 timeout 200 python bench.py --precision fp16x3 --no-extras --no-cpu-baseline --steps 20 --repeats 2 2>/dev/null | python -c "
+  ADAS_BENCH_NO_PMC=1 timeout 200 python bench.py --precision fp16x3 --full --no-extras --no-cpu-baseline --steps 20 --repeats 2 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
