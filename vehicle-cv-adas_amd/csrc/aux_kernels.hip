@@ -1263,6 +1263,91 @@ hipError_t launch_detect_v6(const TView* ins, float* out, int n, int nc, int A, 
     return hipGetLastError();
 }
 
+// The same head with DFL (YOLOv6 m / l: use_dfl = True, reg_max = 16): each side's distance is the expectation of a softmax over 17 bins,
+// sum_i softmax(z)_i * i (proj_conv's weights 0..16), the bins of side k at reg channels 17 k .. 17 k + 16.  Memory-bound: per row 68 fp32
+// reads, 5 + nc writes.  Workgroup = 32 consecutive rows of one frame: (1) the rows' 68 logits staged into LDS with 16-byte loads (rows
+// of one level are adjacent in NHWC, so a run of rows is one contiguous span per level), (2) 128 threads reduce one (row, side) each, the
+// softmax max-subtracted in fp32 with expf, (3) all 256 threads write the 32 rows as detect_v6_kernel does.
+constexpr int DFL_BINS = 17, DFL_CH = 4 * DFL_BINS;
+__global__ __launch_bounds__(256) void detect_v6_dfl_kernel(DetV6Dev d) {
+    __shared__ float lg[32 * DFL_CH];       // [row][side][bin]: thread (row, side) reads at 17 (4 row + side) + i, stride 17: no bank conflicts
+    __shared__ float dist[32 * 4];
+    const int no = d.nc + 5;
+    const int b = blockIdx.y, row0 = blockIdx.x * 32;
+    const int nrow = min(32, d.A - row0);
+    for (int e = threadIdx.x; e < nrow * (DFL_CH / 4); e += 256) {
+        const int r = e / (DFL_CH / 4), q = e - r * (DFL_CH / 4);
+        const int row = row0 + r;
+        const int l = (row >= d.row_off[2]) ? 2 : (row >= d.row_off[1] ? 1 : 0);
+        const int p = row - d.row_off[l];
+        const float* src = d.reg[l] + (size_t)b * d.hw[l] * d.reg_cs[l];       // frame base; in-frame offsets 32-bit
+        const float4 v = *reinterpret_cast<const float4*>(src + p * d.reg_cs[l] + 4 * q);
+        *reinterpret_cast<float4*>(lg + r * DFL_CH + 4 * q) = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const int r = threadIdx.x >> 2, k = threadIdx.x & 3;
+        if (r < nrow) {
+            const float* z = lg + r * DFL_CH + k * DFL_BINS;
+            float m = z[0];
+#pragma unroll
+            for (int i = 1; i < DFL_BINS; ++i) m = fmaxf(m, z[i]);
+            float ex[DFL_BINS], s = 0.f;
+#pragma unroll
+            for (int i = 0; i < DFL_BINS; ++i) {
+                ex[i] = expf(z[i] - m);
+                s += ex[i];
+            }
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < DFL_BINS; ++i) acc += (ex[i] / s) * (float)i;
+            dist[r * 4 + k] = acc;
+        }
+    }
+    __syncthreads();
+    float* out = d.out + ((size_t)b * d.A + row0) * no;
+    const int nel = nrow * no;
+    for (int e = threadIdx.x; e < nel; e += 256) {
+        const int r = e / no, c = e - r * no;               // 32-bit, e < 32 * no
+        const int row = row0 + r;
+        const int l = (row >= d.row_off[2]) ? 2 : (row >= d.row_off[1] ? 1 : 0);
+        const int p = row - d.row_off[l];
+        float o;
+        if (c < 4) {
+            const float* rg = dist + r * 4;
+            const float ax = (float)(p % d.nx[l]) + 0.5f, ay = (float)(p / d.nx[l]) + 0.5f;
+            const float x1 = ax - rg[0], y1 = ay - rg[1], x2 = ax + rg[2], y2 = ay + rg[3];
+            const float s = (float)d.stride[l];
+            o = (c == 0 ? (x1 + x2) / 2 : c == 1 ? (y1 + y2) / 2 : c == 2 ? x2 - x1 : y2 - y1) * s;
+        } else if (c == 4) {
+            o = 1.0f;
+        } else {
+            const float* cls = d.cls[l] + (size_t)b * d.hw[l] * d.cls_cs[l];
+            o = 1.0f / (1.0f + expf(-cls[p * d.cls_cs[l] + (c - 5)]));
+        }
+        out[e] = o;
+    }
+}
+// ins[2l] = reg_preds.l (4 x 17 fp32 channels), ins[2l + 1] = cls_preds.l (nc fp32 channels)
+hipError_t launch_detect_v6_dfl(const TView* ins, float* out, int n, int nc, int A, const int strides[3], hipStream_t st_) {
+    DetV6Dev d;
+    int off = 0;
+    for (int l = 0; l < 3; ++l) {
+        const TView& r = ins[2 * l];
+        const TView& c = ins[2 * l + 1];
+        if (!r.f32 || !c.f32 || r.c != DFL_CH || c.c != nc || r.coff || c.coff || r.h != c.h || r.w != c.w) return hipErrorInvalidValue;
+        if ((r.cs & 3) || r.cs < DFL_CH || c.cs < nc) return hipErrorInvalidValue;                 // 16-byte row starts for the staged loads
+        if ((long long)r.h * r.w * r.cs >= (1LL << 31) || (long long)c.h * c.w * c.cs >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit in-frame offsets
+        d.reg[l] = (const float*)r.p; d.cls[l] = (const float*)c.p; d.reg_cs[l] = r.cs; d.cls_cs[l] = c.cs;
+        d.hw[l] = r.h * r.w; d.nx[l] = r.w; d.stride[l] = strides[l]; d.row_off[l] = off;
+        off += d.hw[l];
+    }
+    if (off != A) return hipErrorInvalidValue;
+    d.out = out; d.nc = nc; d.A = A; d.n = n;
+    hipLaunchKernelGGL(detect_v6_dfl_kernel, dim3((A + 31) / 32, n), dim3(256), 0, st_, d);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------- LayerNorm
 // Two passes, both relative to a pivot: the row's first element p.  d = x - p is exact for x within a factor of two of p, and the mean
 // m and every deviation d - m are then resolved at the scale of the row's spread, not of its offset.  Relative to zero, an fp32 mean

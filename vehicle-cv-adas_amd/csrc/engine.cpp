@@ -289,6 +289,22 @@ int adas_engine_create(const char* model_path, int precision, int max_batch, ada
             for (uint32_t k = 0; k < o.n_in && k < 3; ++k) ins[k] = view(o.in_buf[k], o.in_coff[k], o.in_c[k]);
             ok = o.n_in <= 3 && wsum_supported((int)o.n_in, ins, view(o.out_buf, o.out_coff, o.out_c)) && o.act <= ACT_RELU6;
         }
+        if (o.type == OP_DETECT_V6 && o.n_in == 6) {   // params[5] = reg_max: 0 = 4 distances (containers before DFL carry 0), 16 = DFL bins
+            const float rm = o.params[5];
+            char why[160] = "";
+            if (rm != 0.0f && rm != 16.0f)
+                snprintf(why, sizeof(why), "reg_max %g is not supported (0: 4 distance channels; 16: 4 x 17 DFL bins)", (double)rm);
+            for (int l = 0; l < 3 && !why[0]; ++l)
+                if (o.in_c[2 * l] != 4 * ((int)rm + 1))
+                    snprintf(why, sizeof(why), "level %d regression input has %d channels, reg_max %d needs 4 x (reg_max + 1) = %d", l, o.in_c[2 * l],
+                             (int)rm, 4 * ((int)rm + 1));
+            if (why[0]) {
+                fclose(f);
+                free_engine(e);
+                set_error("[%s]: layer %s: YOLOv6 Detect: %s", model_path, std::string(o.name, strnlen(o.name, sizeof(o.name))).c_str(), why);
+                return ADAS_ERR_FORMAT;
+            }
+        }
         if ((o.type == OP_CONV || o.type == OP_DWCONV) && o.act > ACT_LEAKY) {   // hard-swish / hard-sigmoid: element-wise layers only (kernels.h)
             fclose(f);
             free_engine(e);
@@ -973,6 +989,8 @@ int adas_engine_layer_kernel(const adas_engine* e, int layer, int batch, char* n
         snprintf(name, cap, e->prec == PREC_X3 ? "detect_v8_fused_x3_kernel" : "detect_v8_fused_kernel");
     } else if (o.type == OP_DETECT_V5 && op.det_src[0] >= 0) {
         snprintf(name, cap, "detect_v5_fused_kernel");
+    } else if (o.type == OP_DETECT_V6 && o.params[5] != 0.0f) {
+        snprintf(name, cap, "detect_v6_dfl_kernel");
     } else {
         snprintf(name, cap, "%s", o.type < 16 ? kOther[o.type] : "?");
     }
@@ -1104,7 +1122,8 @@ int engine_run_op(adas_engine* e, int i, const float* d_in, int batch, hipStream
             TView ins[6];
             for (int k = 0; k < 6; ++k) ins[k] = make_view(e, o.in_buf[k], o.in_coff[k], o.in_c[k]);
             int strides[3] = {(int)o.params[2], (int)o.params[3], (int)o.params[4]};
-            err = launch_detect_v6(ins, (float*)e->bufs[o.out_buf].d, batch, (int)o.params[0], (int)o.params[1], strides, st);
+            err = (o.params[5] != 0.0f ? launch_detect_v6_dfl : launch_detect_v6)(ins, (float*)e->bufs[o.out_buf].d, batch, (int)o.params[0],
+                                                                                  (int)o.params[1], strides, st);
             break;
         }
         case OP_UPSAMPLE2:

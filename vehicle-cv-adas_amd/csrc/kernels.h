@@ -140,6 +140,8 @@ hipError_t launch_upsample2(TView in, TView out, int n, int prec, hipStream_t st
 bool depth2space_supported(const TView& in, const TView& out);
 hipError_t launch_depth2space(TView in, TView out, int n, int prec, hipStream_t st);   // block 2: ConvTranspose2d(k 2, s 2) behind a 1x1 conv (YOLOv6)
 hipError_t launch_detect_v6(const TView* ins, float* out, int n, int nc, int A, const int strides[3], hipStream_t st);
+// the DFL form (YOLOv6 m / l): reg views of 4 x 17 bin logits per anchor; softmax expectation per side, then the same decode
+hipError_t launch_detect_v6_dfl(const TView* ins, float* out, int n, int nc, int A, const int strides[3], hipStream_t st);
 // three chained 5x5 s1 p2 max-pools (SPPF) in one launch: out[0] = pool(in), out[1] = pool(out[0]), out[2] = pool(out[1])
 bool sppf_pool3_applicable(int prec, const TView& in, const TView out[3]);
 hipError_t launch_sppf_pool3(const TView& in, const TView out[3], int n, int prec, hipStream_t st);

@@ -57,6 +57,8 @@ V5_SILU_GAIN = 1.15             # YOLOv5 (C3 blocks; kept at the round-1 value: 
                                 # and no better at 1.0)
 RELU_RES_GAIN = 0.8             # ResNet lane nets: ReLU + residual adds double the variance; flat drift at 0.8 (9e-4 rel-L2 fp16)
 SYNTH_GAINS = {"yolov6n": 0.95, "yolov6s": 0.95,                      # plain ReLU 3x3 stacks (no residuals): He gain 1 holds the variance; 0.95 decays gently
+               "yolov6m": 0.92,                                       # ReLU + BottleRep shortcuts: neck rms ~1 at 0.92, ~3 at 0.95, 0.15 at 0.85
+               "yolov6l": 1.07,                                       # SiLU BottleReps: activations run away between 1.08 and 1.10, bias-level at 1.0
                "yolov9c": 1.06,
                "yolov9s": 1.06,                                       # 1.12 (yolov9t's) has a runaway mode on small inputs (96x128: rms 1e5 at P5)
                "yolov7-tiny": 1.0,                                    # LeakyReLU: piecewise linear, no chaos (fp16 rel-L2 1.3e-3 at any gain); 1.0 keeps rms ~0.4
@@ -89,7 +91,7 @@ class View:
 
 
 class SynthWeights:
-    """Seeded synthetic parameters.  kind: 'conv' (OIHW), 'bias', 'linear' (out,in), 'ln_w', 'ln_b'."""
+    """Seeded synthetic parameters.  kind: 'conv' (OIHW), 'bias', 'linear' (out,in), 'ln_w', 'ln_b', 'alpha'."""
 
     def __init__(self, seed=0, gain=1.0):
         self.rng = np.random.default_rng(seed)
@@ -110,6 +112,8 @@ class SynthWeights:
             a = (1.0 + 0.05 * self.rng.standard_normal(shape)).astype(np.float32)
         elif kind == "ln_b":
             a = (0.05 * self.rng.standard_normal(shape)).astype(np.float32)
+        elif kind == "alpha":      # a learned scalar shortcut (YOLOv6 BottleRep): drawn away from 1, so a dropped alpha shows
+            a = self.rng.uniform(0.6, 0.9, shape).astype(np.float32)
         else:
             raise ValueError(kind)
         self.store[name] = a
@@ -858,6 +862,113 @@ def yolov6(scale="n", nc=80, imgsz=640, wsrc=None, seed=0):
 
 
 # =====================================================================================
+# YOLOv6 v3.0 m / l (meituan/YOLOv6 configs/yolov6m.py, yolov6l.py; models/efficientrep.py CSPBepBackbone, models/reppan.py
+# CSPRepBiFPANNeck, models/effidehead.py Detect with use_dfl=True, reg_max=16; layers/common.py BepC3, RepBlock, BottleRep, SimSPPF, SPPF,
+# BiFusion).  Deploy form.  The basic block is the config's training_mode block: m RepVGGBlock (one 3x3 + ReLU), l ConvBNSiLU (3x3 + SiLU);
+# BepC3's cv1 / cv2 / cv3 follow it (ConvBNReLU | ConvBNSiLU), and so does the P5 merge (SimSPPF | SPPF).  The neck's reduce layers, BiFusion
+# and down-sampling convs are ConvBNReLU in both.  BepC3 = cv3(cat(m(cv1 x), cv2 x)), m = RepBlock of max(1, n // 2) BottleReps
+# (conv2(conv1 x) + alpha x, alpha a learned scalar: a weighted-sum layer behind the plain conv2).  The head is n / s's with 4 x 17 DFL bins
+# per level: OP_DETECT_V6 with params[5] = reg_max = 16 runs the softmax, the expectation against proj_conv's 0..16 and dist2bbox.
+# Sizes: m 34.86 M parameters / 85.1 GFLOPs, l 59.61 M / 149.5 G (upstream tables: 34.9 M / 85.8 G, 59.6 M / 150.7 G).
+# =====================================================================================
+V6_CSP_SCALES = {"m": (0.60, 0.75, 2.0 / 3, False), "l": (1.0, 1.0, 1.0 / 2, True)}    # depth, width, csp_e, ConvBNSiLU blocks
+V6_REG_MAX = 16
+
+
+def yolov6_csp(scale="m", nc=80, imgsz=640, wsrc=None, seed=0):
+    depth, width, csp_e, silu = V6_CSP_SCALES[scale]
+    name = "yolov6" + scale
+    wsrc = wsrc or SynthWeights(seed, gain=synth_gain(name))
+    H, W = _hw(imgsz)
+    g = Graph(name, 3, H, W, wsrc)
+    x, cin = g.input()
+    rep_n = lambda n: max(round(n * depth), 1) if n > 1 else n
+    ch = [int(math.ceil(c * width / 8) * 8) for c in (64, 128, 256, 512, 1024, 256, 128, 128, 256, 256, 512)]   # make_divisible(c * w, 8)
+    nb = [rep_n(n) for n in (1, 6, 12, 18, 6)]
+    nn_ = rep_n(12)
+    bact, bsuf = (ACT_SILU, ".block.conv") if silu else (ACT_RELU, ".rbr_reparam")
+
+    def blk(src, c, s, nm, out=None, true_cin=None):         # the basic block: RepVGGBlock (deploy) | ConvBNSiLU, 3x3
+        return g.conv(src, c, 3, s, nm + bsuf, act=bact, out=out, true_cin=true_cin)
+
+    def cba(src, c, k, s, nm, act, out=None):                # ConvBNReLU | ConvBNSiLU
+        return g.conv(src, c, k, s, nm + ".block.conv", act=act, out=out)
+
+    def bottlerep(src, nm, out=None):                        # BottleRep(weight=True): conv2(conv1(x)) + alpha * x
+        y = blk(blk(src, src.c, 1, nm + ".conv1"), src.c, 1, nm + ".conv2")
+        alpha = g.w(nm + ".alpha", (1,), "alpha")
+        g.n_params += alpha.size
+        return g.wsum([y, src], [1.0, float(alpha[0])], nm + ".shortcut", act=ACT_NONE, out=out)
+
+    def bepc3(src, c2, n, nm, out=None):                     # parameters requested in forward order: cv1, the BottleReps, cv2, cv3
+        c_ = int(c2 * csp_e)
+        cat = g.buf(src.h, src.w, 2 * c_)                    # cat(m(cv1 x), cv2 x)
+        y = cba(src, c_, 1, 1, nm + ".cv1", bact)
+        nr = max(1, n // 2)
+        for i in range(nr):
+            y = bottlerep(y, nm + (".m.conv1" if i == 0 else f".m.block.{i - 1}"), out=cat.slice(0, c_) if i == nr - 1 else None)
+        cba(src, c_, 1, 1, nm + ".cv2", bact, out=cat.slice(c_, c_))
+        return cba(cat, c2, 1, 1, nm + ".cv3", bact, out=out)
+
+    # ---- CSPBepBackbone (fuse_P2)
+    x = blk(x, ch[0], 2, "backbone.stem", true_cin=cin)
+    feats = []
+    for i in range(1, 5):
+        x = blk(x, ch[i], 2, f"backbone.ERBlock_{i + 1}.0")
+        x = bepc3(x, ch[i], nb[i], f"backbone.ERBlock_{i + 1}.1")
+        feats.append(x)
+    x3, x2, x1, x = feats                                     # P2 (stride 4), P3, P4, P5 before the channel merge
+    c_ = ch[4] // 2                                           # SimSPPF | SPPF (c5, c5, 5): cv2(cat(x, m(x), m(m(x)), m(m(m(x))))), x = cv1(.)
+    sp = "backbone.ERBlock_5.2"
+    cat4 = g.buf(x.h, x.w, 4 * c_)
+    cba(x, c_, 1, 1, sp + ".cv1", bact, out=cat4.slice(0, c_))
+    for i in range(3):
+        g.maxpool(cat4.slice(i * c_, c_), 5, 1, 2, out=cat4.slice((i + 1) * c_, c_), name=f"{sp}.m{i}")
+    x0 = cba(cat4, ch[4], 1, 1, sp + ".cv2", bact)
+
+    # ---- CSPRepBiFPANNeck
+    def bifusion(deep, same, shallow, c, nm):
+        cat = g.buf(same.h, same.w, 3 * c)
+        g.deconv2x2(deep, c, nm + ".upsample.upsample_transpose", out=cat.slice(0, c))
+        cba(same, c, 1, 1, nm + ".cv1", ACT_RELU, out=cat.slice(c, c))
+        t_ = cba(shallow, c, 1, 1, nm + ".cv2", ACT_RELU)
+        cba(t_, c, 3, 2, nm + ".downsample", ACT_RELU, out=cat.slice(2 * c, c))
+        return cba(cat, c, 1, 1, nm + ".cv3", ACT_RELU)
+
+    catn3 = g.buf(H // 16, W // 16, ch[7] + ch[6])            # cat(downsample2(pan_out2), fpn_out1)
+    catn4 = g.buf(H // 32, W // 32, ch[9] + ch[5])            # cat(downsample1(pan_out1), fpn_out0)
+    fpn0 = cba(x0, ch[5], 1, 1, "neck.reduce_layer0", ACT_RELU, out=catn4.slice(ch[9], ch[5]))
+    f0 = bepc3(bifusion(fpn0, x1, x2, ch[5], "neck.Bifusion0"), ch[5], nn_, "neck.Rep_p4")
+    fpn1 = cba(f0, ch[6], 1, 1, "neck.reduce_layer1", ACT_RELU, out=catn3.slice(ch[7], ch[6]))
+    pan2 = bepc3(bifusion(fpn1, x2, x3, ch[6], "neck.Bifusion1"), ch[6], nn_, "neck.Rep_p3")
+    cba(pan2, ch[7], 3, 2, "neck.downsample2", ACT_RELU, out=catn3.slice(0, ch[7]))
+    pan1 = bepc3(catn3, ch[8], nn_, "neck.Rep_n3")
+    cba(pan1, ch[9], 3, 2, "neck.downsample1", ACT_RELU, out=catn4.slice(0, ch[9]))
+    pan0 = bepc3(catn4, ch[10], nn_, "neck.Rep_n4")
+
+    # ---- EffiDeHead (inference, use_dfl = True): layer names as n / s; reg_preds.i has 4 x (reg_max + 1) channels, bins of a side adjacent
+    ins, strides = [], []
+    levels = [pan2, pan1, pan0]
+    nreg = 4 * (V6_REG_MAX + 1)
+    for i, f in enumerate(levels):
+        s_ = H // f.h
+        strides.append(s_)
+        st = g.conv(f, f.c, 1, 1, f"detect.stems.{i}.conv")
+        cf = g.conv(st, f.c, 3, 1, f"detect.cls_convs.{i}.conv")
+        cl = g.conv(cf, nc, 1, 1, f"detect.cls_preds.{i}", act=ACT_NONE, f32_out=True, bias_fill=-math.log((1 - 0.01) / 0.01))
+        rf = g.conv(st, f.c, 3, 1, f"detect.reg_convs.{i}.conv")
+        rg = g.conv(rf, nreg, 1, 1, f"detect.reg_preds.{i}", act=ACT_NONE, f32_out=True, bias_fill=1.0)
+        ins += [rg, cl]
+    A = sum(f.h * f.w for f in levels)
+    no = nc + 5
+    head = g.buf(1, 1, A * no, f32=True)
+    g._op(OP_DETECT_V6, ins, head, params=[nc, A] + strides + [V6_REG_MAX], name="detect.decode")
+    g.output(head, 0, [1, A, no], "outputs")
+    g.meta = dict(kind="yolov6", nc=nc, anchors=A, strides=strides)
+    return g
+
+
+# =====================================================================================
 # YOLOv7-tiny (WongKinYiu/yolov7 cfg/deploy/yolov7-tiny.yaml; README.md:55 lists YOLOv7; yoloDetector.py:110-124 decodes its head as the
 # v5 layout (1, A, 5+nc)).  78 rows, every Conv with LeakyReLU(0.1): ELAN-tiny blocks (two 1x1 branches, two chained 3x3, concat of the
 # four, 1x1), MP = 2x2 stride-2 max-pool, an SPPCSPC-tiny (5 / 9 / 13 max-pools), PAN neck, IDetect (its ImplicitA / ImplicitM fold
@@ -1262,6 +1373,8 @@ BUILDERS = {
     "yolov7-tiny": lambda **k: yolov7_tiny(**k),
     "yolov6n": lambda **k: yolov6("n", **k),
     "yolov6s": lambda **k: yolov6("s", **k),
+    "yolov6m": lambda **k: yolov6_csp("m", **k),
+    "yolov6l": lambda **k: yolov6_csp("l", **k),
     "yolov5n": lambda **k: yolov5("n", **k), "yolov5s": lambda **k: yolov5("s", **k),
     "yolov5m": lambda **k: yolov5("m", **k), "yolov5l": lambda **k: yolov5("l", **k), "yolov5x": lambda **k: yolov5("x", **k),
     "ufldv2_res18": lambda **k: ufldv2("18", **k), "ufldv2_res34": lambda **k: ufldv2("34", **k),

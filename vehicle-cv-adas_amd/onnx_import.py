@@ -8,7 +8,7 @@ architectures `models.py` builds (hand-written HIP kernels per layer type).  Wha
   * a dependency-free reader of the ONNX protobuf wire format (the `onnx` package is not required): initializers
     (float / float16 / double, raw_data or typed fields), Conv / BatchNormalization / Gemm / MatMul nodes in graph order,
     graph input and output shapes;
-  * architecture detection (YOLOv8 n/s/m/l/x, YOLOv5 n/s/m/l, UFLDv2 CULane ResNet-18/34) from output shapes, the first
+  * architecture detection (YOLOv8 n/s/m/l/x, YOLOv5 n/s/m/l, YOLOv6 n/s/m/l, UFLDv2 CULane ResNet-18/34) from output shapes, the first
     convolution and initializer names;
   * a weight source for `models.build`: parameters are taken BY NAME when the exporter kept PyTorch names (ultralytics
     exports after Conv+BN fusion keep `model.N.conv.weight`), with BatchNorm folded when BN tensors are present, and BY
@@ -282,6 +282,14 @@ def fold_bn(w, b, gamma, beta, mean, var, eps):
     return w2, ((b0 - mean) * s + beta).astype(np.float32)
 
 
+V6_CSP_CONVS = {"m": 108, "l": 150}     # Conv + ConvTranspose nodes of a v3.0 yolov6m / yolov6l deploy export (models.yolov6_csp n_convs)
+
+
+def _is_v6_proj(w, b):
+    """EffiDeHead's proj_conv: the bias-free 1x1 conv from the 17 DFL bins of one side to its distance."""
+    return b is None and w.shape == (1, M.V6_REG_MAX + 1, 1, 1)
+
+
 def detect_arch(m):
     """-> (builder name, kwargs).  Raises ValueError with what was found when nothing matches."""
     outs = [s for _, s in m.outputs]
@@ -338,12 +346,23 @@ def detect_arch(m):
             return "yolov8" + scale, dict(nc=o[1] - 4, imgsz=(H, W))
         if c0[2] == 3 and o[1] > o[2] and any(nd["op"] == "ConvTranspose" for nd in m.nodes):
             # (1, A, 5+nc) with A = one row per cell, transposed-conv up-sampling in the neck: YOLOv6 v3.0 (RepBiFPANNeck); deploy export
-            # (RepVGG blocks fused).  Told apart by width: 16-channel stem = n, 32 = s; the conv count pins the depth (0.33).
+            # (RepVGG blocks fused).  Told apart by width: 16-channel stem = n, 32 = s; the conv count pins the depth (0.33).  A Softmax
+            # (the DFL tail of EffiDeHead, use_dfl=True) marks the CSP scales: 48-channel stem = m, 64 = l, each pinned by its conv count
+            # (proj_convs not counted).
             if H % 32 or W % 32:
                 raise ValueError("YOLO input size must be multiples of 32: " + found)
+            built = ("YOLOv6 variant not built (v3.0 deploy exports of yolov6n / yolov6s, 69 Conv + 2 ConvTranspose nodes, and of yolov6m / "
+                     "yolov6l with the DFL head, %d / %d Conv + ConvTranspose nodes besides the 3 proj_convs, are): " % (V6_CSP_CONVS["m"], V6_CSP_CONVS["l"]))
+            A = (H // 8) * (W // 8) + (H // 16) * (W // 16) + (H // 32) * (W // 32)
+            if any(nd["op"] == "Softmax" for nd in m.nodes):
+                scale = {48: "m", 64: "l"}.get(c0[0])
+                n_proj = sum(1 for w_, b_ in convs if _is_v6_proj(w_, b_))
+                if scale is None or len(convs) - n_proj != V6_CSP_CONVS[scale] or n_proj != 3 or o[1] != A:
+                    raise ValueError(built + found)
+                return "yolov6" + scale, dict(nc=o[2] - 5, imgsz=(H, W))
             scale = {16: "n", 32: "s"}.get(c0[0])
-            if scale is None or len(convs) != 71 or o[1] != (H // 8) * (W // 8) + (H // 16) * (W // 16) + (H // 32) * (W // 32):
-                raise ValueError("YOLOv6 variant not built (v3.0 yolov6n / yolov6s deploy exports, 69 Conv + 2 ConvTranspose nodes, are): " + found)
+            if scale is None or len(convs) != 71 or o[1] != A:
+                raise ValueError(built + found)
             return "yolov6" + scale, dict(nc=o[2] - 5, imgsz=(H, W))
         if c0[2] == 3 and o[1] > o[2]:                      # (1, A, 5+nc) behind a 3x3 stem: YOLOv7 (v5-layout head, yoloDetector.py:110-124)
             if H % 32 or W % 32:
@@ -371,6 +390,17 @@ class OnnxWeights:
         self.arch = arch
         self.init = m.initializers
         self.convs = _convs_in_order(m)
+        if arch in ("yolov6m", "yolov6l"):
+            # the DFL proj_convs are the Detect op's own arithmetic (sum_i softmax_i * i): checked and left out of the positional map
+            proj = np.arange(M.V6_REG_MAX + 1, dtype=np.float32).reshape(1, -1, 1, 1)
+            for w, b in self.convs:
+                if _is_v6_proj(w, b) and not np.array_equal(w, proj):
+                    raise ValueError("YOLOv6 DFL proj_conv weights are %s, not 0, 1, ..., %d: the Detect op decodes with those fixed bins"
+                                     % (np.array2string(w.ravel(), precision=3), M.V6_REG_MAX))
+            self.convs = [(w, b) for w, b in self.convs if not _is_v6_proj(w, b)]
+            # BottleRep alphas: the one-element constant operand of each `Mul`, in execution order
+            self._alphas = [np.asarray(self.init[i], np.float32).reshape(1) for nd in m.nodes if nd["op"] == "Mul"
+                            for i in nd["inputs"] if i in self.init and np.asarray(self.init[i]).size == 1]
         self.store = {}
         self.by_name = any(k.endswith(".conv.weight") or k.endswith("conv1.weight") or k.startswith("model.") and k.endswith(".weight")
                            for k in self.init)
@@ -470,11 +500,26 @@ class OnnxWeights:
             raise ValueError("YOLOv6 export: tensor %r (%d values) does not sit at its layer's position in the graph (%d values there)" % (name, np.asarray(named).size, pos.size))
         return None     # the named path below takes it
 
+    def _v6_alpha(self, name):
+        """YOLOv6 m / l: the k-th BottleRep alpha the builder asks for is the k-th Mul by a one-element constant; cross-checked against the
+        named tensor when the export kept upstream's parameter names."""
+        k = getattr(self, "_alpha_idx", 0)
+        self._alpha_idx = k + 1
+        if k >= len(self._alphas):
+            raise ValueError("YOLOv6 export: BottleRep alpha %r is shortcut #%d, the graph has %d Mul nodes by a scalar constant" % (name, k + 1, len(self._alphas)))
+        pos = self._alphas[k]
+        named = self.init.get(name)
+        if named is not None and not np.array_equal(np.asarray(named, np.float32).reshape(1), pos):
+            raise ValueError("YOLOv6 export: alpha %r (%s) does not sit at its shortcut's position in the graph (%s there)" % (name, named, pos))
+        return pos
+
     def __call__(self, name, shape, kind, fill=None):
         if name in self.store:
             return self.store[name]
         arr = None
-        if self.arch.startswith("yolov6"):
+        if kind == "alpha" and self.arch in ("yolov6m", "yolov6l"):
+            arr = self._v6_alpha(name)
+        elif self.arch.startswith("yolov6"):
             arr = self._v6_lookup(name, shape)
         if arr is None and kind in ("conv", "bias") and (name.endswith(".weight") or name.endswith(".bias")):
             base = name.rsplit(".", 1)[0]
