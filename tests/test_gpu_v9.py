@@ -1,7 +1,7 @@
 """GPU: YOLOv9t (GELAN-t; README.md:57 lists YOLOv9, yoloDetector.py:114,121 decodes its head like v8's): the average-pool kernel,
 network vs the torch oracle (fp32 <= 1e-3 on tapped activations and the head; fp16 / bf16 bounds on a calibrated head), the drop-in
 YoloDetector(model_type=YOLOV9) and the fused pipeline step against the oracle chain."""
-import importlib, os, tempfile
+import importlib
 
 import numpy as np
 import pytest
@@ -31,7 +31,7 @@ def rel_l2(a, b):
 
 @pytest.mark.parametrize("k,s,p,c,hw", [(2, 1, 0, 32, (160, 160)), (2, 1, 0, 96, (23, 37)), (3, 2, 1, 64, (40, 56)), (2, 2, 0, 16, (20, 20))], ids=str)
 @pytest.mark.parametrize("prec,tol", [("fp32", 1e-6), ("fp16", 1e-3), ("bf16", 8e-3), ("fp16x3", 3e-6)])
-def test_average_pool_kernel(k, s, p, c, hw, prec, tol):
+def test_average_pool_kernel(tmp_path, k, s, p, c, hw, prec, tol):
     H, W = hw
     batch = 2
     ws = M.SynthWeights(5, gain=1.0)
@@ -41,7 +41,7 @@ def test_average_pool_kernel(k, s, p, c, hw, prec, tol):
     y = g.avgpool(a, k, s, p, name="test")
     z = g.conv(y, 8, 1, 1, "tap", act=M.ACT_NONE, f32_out=True)
     g.output(z, 0, [1, z.h * z.w * 8], "o")
-    path = os.path.join(tempfile.gettempdir(), f"apunit_{k}_{s}_{p}_{c}_{H}.hipm")
+    path = str(tmp_path / "apunit.hipm")
     g.save(path)
     e = CE.HipEngine(path, prec, batch)
     xin = np.random.default_rng(0).uniform(0, 1, (batch, 3, H, W)).astype(np.float32)
@@ -49,7 +49,7 @@ def test_average_pool_kernel(k, s, p, c, hw, prec, tol):
     got = e.fetch_activation("test", batch)
     a_dev = e.fetch_activation("expand", batch)
     label = e.layer_kernel(e.layer_index("test"), batch)
-    e.close(); os.remove(path)
+    e.close()
     want = F.avg_pool2d(torch.from_numpy(a_dev).double(), k, s, p, False, True).numpy()
     assert label == "avgpool_kernel", label
     assert got.shape == want.shape and rel_l2(got, want) <= tol, rel_l2(got, want)
