@@ -271,8 +271,9 @@ class HipEngine(EngineBase):
 class EfficientdetEngine(EngineBase):
     """The exported EfficientDet-D0 graph the reference hands OnnxEngine (efficientdetDetector.py:38): network + in-graph anchor decode and
     NMS, three outputs -- boxes (n, 4) xyxy float32 in input pixels, class ids (n), confidences (n), by descending confidence
-    (:68-70).  Here: the "efficientdet-d0" engine graph (models.efficientdet: ten raw head tensors, device-resident) followed by the
-    device tail (postproc.EffdetTail).  engine_inference takes the reference's (1, 3, H, W) tensor; a batch returns per-frame lists."""
+    (:68-70).  Here: an "efficientdet-d0" .. "efficientdet-d3" engine graph (models.efficientdet under compound scaling: ten raw head
+    tensors, device-resident; the input size -- 512, 640, 768, 896 -- comes from the container) followed by the device tail
+    (postproc.EffdetTail).  engine_inference takes the reference's (1, 3, H, W) tensor; a batch returns per-frame lists."""
 
     OUTPUT_NAMES = ["boxes", "class_ids", "scores"]
 
@@ -287,7 +288,8 @@ class EfficientdetEngine(EngineBase):
         want = [("regression.l%d" % (i // 2)) if i % 2 == 0 else ("classification.l%d" % (i // 2)) for i in range(10)]
         if names != want:
             self.net.close()
-            raise Exception("%s is not an EfficientDet head graph (outputs %s)" % (model_path, names))
+            raise Exception("%s is not an EfficientDet head graph (efficientdet-d0 .. efficientdet-d3: outputs regression.l<i> / classification.l<i>, "
+                            "i = 0 .. 4); its outputs are %s" % (model_path, names))
         self.num_classes = int(shapes[1][2])
         shp = self.net.get_engine_input_shape()
         self.tail = EffdetTail(shp[2:], self.num_classes, score_thr, iou_thr, max_det, max_candidates, max_batch)

@@ -968,46 +968,9 @@ ADAS_DEV void effdet_anchor(const EffdetTailCfg& cfg, int a, int& level, int& ro
     const double cy = (double)stride / 2.0 + (double)y * (double)stride, cx = (double)stride / 2.0 + (double)x * (double)stride;
     out[0] = (float)(cy - ay2); out[1] = (float)(cx - ax2); out[2] = (float)(cy + ay2); out[3] = (float)(cx + ax2);
 }
-ADAS_DEV void effdet_tail_frame(const Ctx& c, const EffdetTailCfg& cfg, const EffdetTailFrame& f, void* lds) {
-    EffdetTailLds L = effdet_tail_carve(lds, cfg.cap);
-    int total = 0;
-    for (int l = 0; l < 5; ++l) total += (cfg.in_h >> (3 + l)) * (cfg.in_w >> (3 + l)) * 9;
-    // ---- candidates in anchor order: chunks of nthr anchors, block-wide exclusive scan of the keep flags
-    int n_cand = 0;
-    for (int a0 = 0; a0 < total; a0 += c.nthr) {
-        const int a = a0 + c.tid;
-        int keep = 0, best_c = 0;
-        float sc = 0.f;
-        if (a < total) {
-            int base = 0, level = 0;
-            for (int l = 0; l < 5; ++l) {
-                const int n = (cfg.in_h >> (3 + l)) * (cfg.in_w >> (3 + l)) * 9;
-                if (a < base + n || l == 4) { level = l; break; }
-                base += n;
-            }
-            const float* p = f.cls[level] + (size_t)(a - base) * cfg.nc;
-            float best = p[0];
-            for (int k = 1; k < cfg.nc; ++k) {
-                const float v = p[k];
-                if (v > best) { best = v; best_c = k; }
-            }
-            sc = (float)(1.0 / (1.0 + exp(-(double)best)));
-            keep = ((double)sc > cfg.score_thr) ? 1 : 0;
-        }
-        L.scan[c.tid + 1] = keep;
-        c.sync();
-        if (c.tid == 0) {
-            L.scan[0] = 0;
-            for (int i = 0; i < c.nthr; ++i) L.scan[i + 1] += L.scan[i];
-        }
-        c.sync();
-        const int pos = n_cand + L.scan[c.tid];
-        if (keep && pos < cfg.cap) {
-            L.score[pos] = sc; L.anchor[pos] = a; L.cid[pos] = best_c;
-        }
-        n_cand += L.scan[c.nthr];
-        c.sync();
-    }
+// Second phase of the tail: n_cand candidates lie in L.score / L.anchor / L.cid in anchor order (entries past cfg.cap were dropped).
+// Overflow report, rank, decode + clip, per-class NMS.  Shared by the single-workgroup tail and by the finish pass of the two-pass one.
+ADAS_DEV void effdet_tail_rank_nms(const Ctx& c, const EffdetTailCfg& cfg, const EffdetTailFrame& f, const EffdetTailLds& L, int n_cand) {
     if (c.tid == 0) f.count[1] = n_cand;
     if (n_cand > cfg.cap) {   // overflow: the caller reports ADAS_ERR_CAPACITY
         if (c.tid == 0) f.count[0] = 0;
@@ -1069,6 +1032,270 @@ ADAS_DEV void effdet_tail_frame(const Ctx& c, const EffdetTailCfg& cfg, const Ef
         c.sync();
     }
     if (c.tid == 0) f.count[0] = kept;
+}
+ADAS_DEV void effdet_tail_frame(const Ctx& c, const EffdetTailCfg& cfg, const EffdetTailFrame& f, void* lds) {
+    EffdetTailLds L = effdet_tail_carve(lds, cfg.cap);
+    int total = 0;
+    for (int l = 0; l < 5; ++l) total += (cfg.in_h >> (3 + l)) * (cfg.in_w >> (3 + l)) * 9;
+    // ---- candidates in anchor order: chunks of nthr anchors, block-wide exclusive scan of the keep flags
+    int n_cand = 0;
+    for (int a0 = 0; a0 < total; a0 += c.nthr) {
+        const int a = a0 + c.tid;
+        int keep = 0, best_c = 0;
+        float sc = 0.f;
+        if (a < total) {
+            int base = 0, level = 0;
+            for (int l = 0; l < 5; ++l) {
+                const int n = (cfg.in_h >> (3 + l)) * (cfg.in_w >> (3 + l)) * 9;
+                if (a < base + n || l == 4) { level = l; break; }
+                base += n;
+            }
+            const float* p = f.cls[level] + (size_t)(a - base) * cfg.nc;
+            float best = p[0];
+            for (int k = 1; k < cfg.nc; ++k) {
+                const float v = p[k];
+                if (v > best) { best = v; best_c = k; }
+            }
+            sc = (float)(1.0 / (1.0 + exp(-(double)best)));
+            keep = ((double)sc > cfg.score_thr) ? 1 : 0;
+        }
+        L.scan[c.tid + 1] = keep;
+        c.sync();
+        if (c.tid == 0) {
+            L.scan[0] = 0;
+            for (int i = 0; i < c.nthr; ++i) L.scan[i + 1] += L.scan[i];
+        }
+        c.sync();
+        const int pos = n_cand + L.scan[c.tid];
+        if (keep && pos < cfg.cap) {
+            L.score[pos] = sc; L.anchor[pos] = a; L.cid[pos] = best_c;
+        }
+        n_cand += L.scan[c.nthr];
+        c.sync();
+    }
+    effdet_tail_rank_nms(c, cfg, f, L, n_cand);
+}
+
+// ===========================================================================
+// EfficientDet tail in two passes.  The candidate phase above has one workgroup walk every class logit of its frame (each lane its own
+// nc-float row) and thread 0 add up nthr flags after every nthr anchors.  Here that phase is a pass of its own over
+// (anchor chunks x frames) workgroups:
+//   class-max pass   a chunk is `chunk` consecutive anchors of ONE pyramid level (the last chunk of a level is short), i.e. one contiguous
+//                    run of n * nc floats of that level's [rows][nc] tensor.  The run is staged through LDS `tile` anchors at a time,
+//                    consecutive lanes reading consecutive floats; `parts` threads share a row (contiguous class segments, joined in class
+//                    order so that the first maximum wins, as the sequential v > best loop has it); best logit, class, score and keep
+//                    decision are the expressions of effdet_tail_frame.  The chunk's kept anchors go out in anchor order as (score,
+//                    anchor, class) into the frame's lists at [first anchor of the chunk ...) and their number into count[chunk].
+//   finish pass      one workgroup per frame: prefix over the chunk counts (wave prefix, then one short scan over the wave totals), the
+//                    lists copied behind one another into the LDS candidate arrays -- anchor order by construction --, then
+//                    effdet_tail_rank_nms as before.
+// No workgroup waits on another and nothing is accumulated across workgroups: every output word has exactly one writer.
+// ===========================================================================
+struct EffdetScanCfg {
+    int chunk;   // anchors per chunk (>= 1)
+    int tile;    // anchors staged per trip (>= 1)
+    int parts;   // threads per anchor row (>= 1)
+};
+struct EffdetScanLists {   // one frame's candidate lists
+    float* score;          // [total anchors]; chunk k's list starts at the index of its first anchor
+    int* anchor;           // [total anchors]
+    int* cid;              // [total anchors]
+    int* count;            // [chunks]
+};
+ADAS_HD int effdet_level_rows(const EffdetTailCfg& cfg, int l) { return (cfg.in_h >> (3 + l)) * (cfg.in_w >> (3 + l)) * 9; }
+ADAS_HD int effdet_total_rows(const EffdetTailCfg& cfg) {
+    int t = 0;
+    for (int l = 0; l < 5; ++l) t += effdet_level_rows(cfg, l);
+    return t;
+}
+ADAS_HD int effdet_scan_chunks(const EffdetTailCfg& cfg, const EffdetScanCfg& sc) {
+    int t = 0;
+    for (int l = 0; l < 5; ++l) t += (effdet_level_rows(cfg, l) + sc.chunk - 1) / sc.chunk;
+    return t;
+}
+// chunk k -> level, first row inside the level, rows in the chunk, global index of its first anchor
+ADAS_HD void effdet_scan_chunk_span(const EffdetTailCfg& cfg, const EffdetScanCfg& sc, int k, int& level, int& row0, int& n, int& a0) {
+    int base = 0;
+    level = 4;
+    for (int l = 0; l < 5; ++l) {
+        const int rows = effdet_level_rows(cfg, l), nch = (rows + sc.chunk - 1) / sc.chunk;
+        if (k < nch || l == 4) { level = l; break; }
+        k -= nch;
+        base += rows;
+    }
+    const int rows = effdet_level_rows(cfg, level);
+    row0 = k * sc.chunk;
+    n = rows - row0 < sc.chunk ? rows - row0 : sc.chunk;
+    a0 = base + row0;
+}
+// LDS of the class-max pass: staged logits (+ 3 floats: the staging keeps global 16-byte alignment), partial maxima, the chunk's results,
+// wave totals
+ADAS_HD size_t effdet_scan_lds_bytes(const EffdetScanCfg& sc, int nc, int nthr) {
+    return ((size_t)sc.tile * nc + 4) * 4 + (size_t)sc.tile * sc.parts * 8 + (size_t)sc.chunk * 8 + ((size_t)(nthr + 63) / 64 + 1) * 4;
+}
+
+// block-wide exclusive prefix of one keep flag / one count per thread; `total` = the block's sum; ws: LDS, one int per wave.
+// Two barriers; ws may be reused after the call returns.
+ADAS_DEV int block_prefix_flag(const Ctx& c, bool fl, int* ws, int& total) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int lane = c.tid & 63, wv = c.tid >> 6, nw = (c.nthr + 63) >> 6;
+    const unsigned long long m = __ballot(fl);
+    if (lane == 0) ws[wv] = __popcll(m);
+    c.sync();
+    int mine = __popcll(m & ((1ull << lane) - 1ull)), tot = 0;
+    for (int w = 0; w < nw; ++w) {
+        const int cw = ws[w];
+        if (w < wv) mine += cw;
+        tot += cw;
+    }
+    c.sync();
+    total = tot;
+    return mine;
+#else
+    (void)c; (void)ws;
+    total = fl ? 1 : 0;   // nthr == 1
+    return 0;
+#endif
+}
+ADAS_DEV int block_prefix_count(const Ctx& c, int v, int* ws, int& total) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int lane = c.tid & 63, wv = c.tid >> 6, nw = (c.nthr + 63) >> 6;
+    int inc = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    if (lane == 63) ws[wv] = inc;
+    c.sync();
+    int mine = inc - v, tot = 0;
+    for (int w = 0; w < nw; ++w) {
+        const int cw = ws[w];
+        if (w < wv) mine += cw;
+        tot += cw;
+    }
+    c.sync();
+    total = tot;
+    return mine;
+#else
+    (void)c; (void)ws;
+    total = v;   // nthr == 1
+    return 0;
+#endif
+}
+
+// ---- class-max pass: chunk k of one frame.  cls[l]: this frame's class logits of level l.
+ADAS_DEV void effdet_scan_chunk(const Ctx& c, const EffdetTailCfg& cfg, const EffdetScanCfg& sc, const float* const cls[5], int k,
+                                const EffdetScanLists& out, void* lds) {
+    int level, row0, n, a0;
+    effdet_scan_chunk_span(cfg, sc, k, level, row0, n, a0);
+    const int nc = cfg.nc, P = sc.parts, seg = (nc + P - 1) / P;
+    float* stage = (float*)lds;
+    float* pv = stage + (size_t)sc.tile * nc + 4;   // [tile][parts] partial maxima
+    int* pi = (int*)(pv + (size_t)sc.tile * P);     // [tile][parts] their classes
+    float* rs = (float*)(pi + (size_t)sc.tile * P); // [chunk] score
+    int* rc = (int*)(rs + sc.chunk);                // [chunk] class, -1: not kept
+    int* ws = rc + sc.chunk;
+    for (int t0 = 0; t0 < n; t0 += sc.tile) {
+        const int nt = n - t0 < sc.tile ? n - t0 : sc.tile, nfl = nt * nc;
+        const float* src = cls[level] + (size_t)(row0 + t0) * nc;
+        // stage[pad + i] = src[i]: lane i reads float i; the body moves 16 bytes per lane from 16-byte aligned global and LDS addresses
+        int head = (int)((0 - (((uintptr_t)src) >> 2)) & 3);
+        if (head > nfl) head = nfl;
+        const int pad = (4 - head) & 3, nv = (nfl - head) >> 2;
+        ADAS_PAR_FOR(c, i, 0, head) stage[pad + i] = src[i];
+#if defined(__HIP_DEVICE_COMPILE__)
+        ADAS_PAR_FOR(c, v, 0, nv) *(float4*)(stage + pad + head + 4 * v) = *(const float4*)(src + head + 4 * v);
+#else
+        ADAS_PAR_FOR(c, i, head, head + 4 * nv) stage[pad + i] = src[i];
+#endif
+        ADAS_PAR_FOR(c, i, head + 4 * nv, nfl) stage[pad + i] = src[i];
+        c.sync();
+        // `parts` threads per row: thread (a, q) takes classes [q * seg, (q + 1) * seg)
+        ADAS_PAR_FOR(c, w, 0, nt * P) {
+            const int a = w / P, q = w - a * P;
+            const int lo = q * seg, hi = lo + seg < nc ? lo + seg : nc;
+            const float* p = stage + pad + (size_t)a * nc;
+            float best = 0.f;
+            int bi = -1;   // an empty segment (parts * seg > nc + seg - 1) takes no part
+            if (lo < hi) {
+                best = p[lo];
+                bi = lo;
+                for (int j = lo + 1; j < hi; ++j) {
+                    const float v = p[j];
+                    if (v > best) { best = v; bi = j; }
+                }
+            }
+            pv[w] = best;
+            pi[w] = bi;
+        }
+        c.sync();
+        ADAS_PAR_FOR(c, a, 0, nt) {
+            float best = pv[a * P];
+            int bi = pi[a * P];
+            for (int q = 1; q < P; ++q) {   // class order: a later segment wins only when strictly larger
+                const float v = pv[a * P + q];
+                if (pi[a * P + q] >= 0 && v > best) { best = v; bi = pi[a * P + q]; }
+            }
+            const float s = (float)(1.0 / (1.0 + exp(-(double)best)));
+            rs[t0 + a] = s;
+            rc[t0 + a] = ((double)s > cfg.score_thr) ? bi : -1;
+        }
+        c.sync();
+    }
+    // ---- the chunk's kept anchors, in anchor order
+    int base = 0;
+    for (int j0 = 0; j0 < n; j0 += c.nthr) {
+        const int j = j0 + c.tid;
+        const bool fl = j < n && rc[j] >= 0;
+        int tot;
+        const int pos = base + block_prefix_flag(c, fl, ws, tot);
+        if (fl) {
+            out.score[a0 + pos] = rs[j]; out.anchor[a0 + pos] = a0 + j; out.cid[a0 + pos] = rc[j];
+        }
+        base += tot;
+    }
+    if (c.tid == 0) out.count[k] = base;
+}
+
+// ---- finish pass of one frame.  LDS: effdet_finish_lds_bytes(cap, nthr): the arrays of the single-workgroup tail, then per thread the
+// chunk's list offset and first anchor, then the wave totals.
+ADAS_HD size_t effdet_finish_lds_bytes(int cap, int nthr) { return effdet_tail_lds_bytes(cap, nthr) + ((size_t)2 * nthr + (size_t)(nthr + 63) / 64 + 2) * 4; }
+ADAS_DEV void effdet_tail_finish(const Ctx& c, const EffdetTailCfg& cfg, const EffdetScanCfg& sc, const EffdetTailFrame& f,
+                                 const EffdetScanLists& in, void* lds) {
+    EffdetTailLds L = effdet_tail_carve(lds, cfg.cap);
+    int* off = L.scan + c.nthr + 2;   // [nthr + 1] exclusive prefix of this trip's counts
+    int* first = off + c.nthr + 1;    // [nthr] first anchor of each chunk of this trip
+    int* ws = first + c.nthr;
+    const int n_chunks = effdet_scan_chunks(cfg, sc);
+    int n_cand = 0;
+    for (int k0 = 0; k0 < n_chunks; k0 += c.nthr) {
+        const int k = k0 + c.tid;
+        int cnt = 0, a0 = 0;
+        if (k < n_chunks) {
+            int level, row0, n;
+            effdet_scan_chunk_span(cfg, sc, k, level, row0, n, a0);
+            cnt = in.count[k];
+        }
+        int tot;
+        off[c.tid] = block_prefix_count(c, cnt, ws, tot);
+        first[c.tid] = a0;
+        if (c.tid == 0) off[c.nthr] = tot;
+        c.sync();
+        ADAS_PAR_FOR(c, j, 0, tot) {
+            const int pos = n_cand + j;
+            if (pos >= cfg.cap) continue;
+            int lo = 0, hi = c.nthr;   // the last t with off[t] <= j: its list holds entry j (off[t + 1] > j)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (off[mid] <= j) lo = mid; else hi = mid;
+            }
+            const int src = first[lo] + (j - off[lo]);
+            L.score[pos] = in.score[src]; L.anchor[pos] = in.anchor[src]; L.cid[pos] = in.cid[src];
+        }
+        n_cand += tot;
+        c.sync();
+    }
+    effdet_tail_rank_nms(c, cfg, f, L, n_cand);
 }
 
 }  // namespace adas

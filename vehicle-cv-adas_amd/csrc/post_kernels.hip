@@ -416,6 +416,13 @@ struct EffdetTailDev {
     float* boxes;          // [B][max_det][4]
     int* ids;              // [B][max_det]
     float* confs;          // [B][max_det]
+    // two-pass tail (post_core.h: effdet_scan_chunk / effdet_tail_finish)
+    EffdetScanCfg sc;
+    int total, n_chunks;   // anchors / chunks per frame
+    float* l_score;        // [B][total] candidate lists, chunk by chunk
+    int* l_anchor;         // [B][total]
+    int* l_cid;            // [B][total]
+    int* l_count;          // [B][n_chunks]
 };
 __global__ __launch_bounds__(1024) void effdet_tail_kernel(EffdetTailDev d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -429,9 +436,34 @@ __global__ __launch_bounds__(1024) void effdet_tail_kernel(EffdetTailDev d) {
     Ctx c{(int)threadIdx.x, (int)blockDim.x};
     effdet_tail_frame(c, d.cfg, f, smem);
 }
+// class-max pass: grid (chunks, frames), every class logit read once, consecutive lanes on consecutive floats
+__global__ __launch_bounds__(256) void effdet_scan_kernel(EffdetTailDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t b = blockIdx.y;
+    const float* cls[5];
+    for (int l = 0; l < 5; ++l) cls[l] = d.cls[l] + b * d.rows[l] * d.cfg.nc;
+    EffdetScanLists o{d.l_score + b * d.total, d.l_anchor + b * d.total, d.l_cid + b * d.total, d.l_count + b * d.n_chunks};
+    Ctx c{(int)threadIdx.x, (int)blockDim.x};
+    effdet_scan_chunk(c, d.cfg, d.sc, cls, (int)blockIdx.x, o, smem);
+}
+// finish pass: one workgroup per frame gathers the chunk lists in anchor order, then rank / decode / NMS
+__global__ __launch_bounds__(1024) void effdet_finish_kernel(EffdetTailDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t b = blockIdx.x, md = d.cfg.max_det;
+    EffdetTailFrame f;
+    for (int l = 0; l < 5; ++l) {
+        f.reg[l] = d.reg[l] + b * d.rows[l] * 4;
+        f.cls[l] = d.cls[l] + b * d.rows[l] * d.cfg.nc;
+    }
+    f.count = d.count + b * 2; f.boxes = d.boxes + b * md * 4; f.ids = d.ids + b * md; f.confs = d.confs + b * md;
+    EffdetScanLists in{d.l_score + b * d.total, d.l_anchor + b * d.total, d.l_cid + b * d.total, d.l_count + b * d.n_chunks};
+    Ctx c{(int)threadIdx.x, (int)blockDim.x};
+    effdet_tail_finish(c, d.cfg, d.sc, f, in, smem);
+}
 struct adas_effdet_tail {
     adas_effdet_tail_params p;
     int max_batch;
+    int one_wg;            // ADAS_EFFDET_TAIL_ONE_WG=1 at create time: the single-workgroup tail (effdet_tail_kernel), for comparisons
     EffdetTailDev dev;
     void* arena;
     hipStream_t last;
@@ -837,25 +869,43 @@ int adas_effdet_tail_create(const adas_effdet_tail_params* p, int max_batch, ada
     h->p = *p;
     h->max_batch = max_batch;
     h->last = 0;
+    {
+        const char* e = getenv("ADAS_EFFDET_TAIL_ONE_WG");
+        h->one_wg = (e && e[0] == '1') ? 1 : 0;
+    }
+    EffdetTailDev& d = h->dev;
+    d.cfg = EffdetTailCfg{p->in_h, p->in_w, p->num_classes, p->max_candidates, p->max_det, p->score_thr, p->iou_thr, p->anchor_scale};
+    // 256 anchors per chunk; 64 rows staged per trip, four threads to a row (fewer rows when nc is large: 48 KiB of logits at most)
+    d.sc.chunk = 256;
+    d.sc.parts = 4;
+    d.sc.tile = 12288 / p->num_classes < 64 ? (12288 / p->num_classes < 1 ? 1 : 12288 / p->num_classes) : 64;
+    d.total = effdet_total_rows(d.cfg);
+    d.n_chunks = effdet_scan_chunks(d.cfg, d.sc);
     const size_t B = max_batch, md = p->max_det;
-    const size_t bytes = B * (md * (16 + 4 + 4) + 8) + 8 * 256;
+    const size_t lists = h->one_wg ? 0 : B * ((size_t)d.total * 12 + (size_t)d.n_chunks * 4);
+    const size_t bytes = B * (md * (16 + 4 + 4) + 8) + lists + 12 * 256;
     if (hipMalloc(&h->arena, bytes) != hipSuccess) {
         delete h;
         return hip_fail(hipGetLastError(), "hipMalloc(effdet tail arena)", __FILE__, __LINE__);
     }
     hipMemset(h->arena, 0, bytes);
     unsigned char* q = (unsigned char*)h->arena;
-    EffdetTailDev& d = h->dev;
-    d.cfg = EffdetTailCfg{p->in_h, p->in_w, p->num_classes, p->max_candidates, p->max_det, p->score_thr, p->iou_thr, p->anchor_scale};
     for (int l = 0; l < 5; ++l) d.rows[l] = (size_t)(p->in_h >> (3 + l)) * (size_t)(p->in_w >> (3 + l)) * 9;
     d.count = carve<int>(q, B * 2);
     d.boxes = carve<float>(q, B * md * 4);
     d.ids = carve<int>(q, B * md);
     d.confs = carve<float>(q, B * md);
-    if (hipFuncSetAttribute((const void*)effdet_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+    if (!h->one_wg) {
+        d.l_score = carve<float>(q, B * d.total);
+        d.l_anchor = carve<int>(q, B * d.total);
+        d.l_cid = carve<int>(q, B * d.total);
+        d.l_count = carve<int>(q, B * d.n_chunks);
+    }
+    if (hipFuncSetAttribute((const void*)effdet_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)effdet_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
         (void)hipFree(h->arena);
         delete h;
-        return hip_fail(hipGetLastError(), "hipFuncSetAttribute(effdet_tail_kernel)", __FILE__, __LINE__);   // fails here, not at the first launch
+        return hip_fail(hipGetLastError(), "hipFuncSetAttribute(effdet tail kernels)", __FILE__, __LINE__);   // fails here, not at the first launch
     }
     *out = h;
     return ADAS_OK;
@@ -875,8 +925,14 @@ int adas_effdet_tail_run(adas_effdet_tail* h, const float* const* d_reg, const f
     }
     hipStream_t st = (hipStream_t)stream;
     h->last = st;
-    const size_t lds = effdet_tail_lds_bytes(h->p.max_candidates, 1024);
-    hipLaunchKernelGGL(effdet_tail_kernel, dim3(batch), dim3(1024), lds, st, d);
+    if (h->one_wg) {
+        const size_t lds = effdet_tail_lds_bytes(h->p.max_candidates, 1024);
+        hipLaunchKernelGGL(effdet_tail_kernel, dim3(batch), dim3(1024), lds, st, d);
+    } else {
+        hipLaunchKernelGGL(effdet_scan_kernel, dim3(d.n_chunks, batch), dim3(256), effdet_scan_lds_bytes(d.sc, d.cfg.nc, 256), st, d);
+        ADAS_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(effdet_finish_kernel, dim3(batch), dim3(1024), effdet_finish_lds_bytes(h->p.max_candidates, 1024), st, d);
+    }
     ADAS_HIP_TRY(hipGetLastError());
     return ADAS_OK;
 }

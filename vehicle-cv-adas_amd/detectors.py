@@ -284,9 +284,10 @@ class YoloDetector(_Defaults):
 class EfficientdetDetector(_Defaults):
     """efficientdetDetector.py:18-111.  The exported EfficientDet graph carries its own decode + NMS; around it the reference does
     letterbox + BGR mean/std normalisation (:57-65) and inverse letterbox + score filter + label lookup (:67-85).  Both run on the
-    device here (adas_preprocess_effdet, adas_effdet_post_*).  The graph itself is coreEngine.EfficientdetEngine: the EfficientDet-D0
-    network (models.efficientdet: EfficientNet-B0 MBConv + squeeze-and-excitation, BiFPN, separable-conv heads) and the in-graph tail
-    (anchor decode + per-class NMS, adas_effdet_tail_*) on the device -- `model_path` is an "efficientdet-d0" .hipm container; or pass
+    device here (adas_preprocess_effdet, adas_effdet_post_*).  The graph itself is coreEngine.EfficientdetEngine: an EfficientDet-D0 .. D3
+    network (models.efficientdet: EfficientNet-B0 .. B3 MBConv + squeeze-and-excitation, BiFPN, separable-conv heads -- the reference's
+    "efficientDet b0/b1/b2/b3") and the in-graph tail (anchor decode + per-class NMS, adas_effdet_tail_*) on the device -- `model_path` is
+    an "efficientdet-d0" .. "efficientdet-d3" .hipm container, whose input size (512 / 640 / 768 / 896) the detector takes over; or pass
     `engine=`, any object with the EngineBase surface (get_engine_input_shape / get_engine_output_shape / engine_inference /
     engine_dtype).  An EfficientDet .onnx with its NMS baked in is not importable (onnx_import fails loudly), which is why the default
     `model_path` names a .hipm container and not the reference's './models/efficientdet-d0-coco_fp32.onnx' (efficientdetDetector.py:22).

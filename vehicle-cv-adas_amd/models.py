@@ -66,6 +66,7 @@ SYNTH_GAINS = {"yolov6n": 0.95, "yolov6s": 0.95,                      # plain Re
                "yolov10s": 1.0,
                "yolov10n": 1.05,                                      # critical ~1.09 (1.08 already drifts: fp16 rel-L2 1.9e-3 at P5, boxes 0.3 px)
                "efficientdet-d0": 1.0,                                # = EFFDET_GAIN
+               "efficientdet-d1": 1.02, "efficientdet-d2": 1.01, "efficientdet-d3": 0.965,   # just below each scale's critical gain: EFFDET_SCALES
                "yolov8m": 0.99, "yolov8l": 0.96, "yolov8x": 0.98}     # deeper Bottleneck chains: critical gain ~1.03 (m), ~0.97 (l), ~1.0 (x)
 
 
@@ -1297,21 +1298,65 @@ def _sepconv(g, x, cout, name, act=ACT_NONE, f32_out=False, dw_name=None, bias_f
     return g.conv(t, cout, 1, 1, name + ".pw", act=act, f32_out=f32_out, bias_fill=bias_fill)
 
 
-def efficientdet(nc=90, imgsz=512, wsrc=None, seed=0, fpn_c=64, fpn_cells=3, head_layers=3, num_anchors=9, cls_bias=-5.0):
-    """EfficientDet-D0 up to its two raw head tensors per pyramid level: box regression (dy, dx, dh, dw) x 9 anchors and class logits
+def round_filters(c, width):
+    """EfficientNet's channel scaling: multiply, round to the nearest 8 (at least 8), add 8 when that lost more than 10 %."""
+    v = c * width
+    r = max(8, int(v + 4) // 8 * 8)
+    return r + 8 if r < 0.9 * v else r
+
+
+def effnet_stages(width, depth):
+    """EFFNET_B0 under compound scaling (arXiv:1905.11946 section 3.3): channels through round_filters, repeats ceil(depth * n)."""
+    return [(e, k, s, round_filters(c, width), int(math.ceil(depth * n))) for e, k, s, c, n in EFFNET_B0]
+
+
+# EfficientDet compound scaling (arXiv:1911.09070 table 1): backbone (width, depth) coefficients, input size, BiFPN width / cells, head
+# layers.  gain (SYNTH_GAINS) / cls_bias: the seeded synthetic weights' operating point, found on the CPU with the torch oracle
+# (tests/effdet_oracle.py) at the native size on eight camera-like frames (bench.cam_frames(3, 77), (2, 78), (3, 5)).  The deeper BiFPNs
+# turn critical earlier and more sharply than D0's: below the critical gain the best class logit sits in a narrow band above the header
+# bias and hardly follows the input, above it single frames run away.  d = best logit - cls_bias:
+#   D1  gain 1.00: d median 0.31, 99.98 % 0.63 .. 1.2, |reg| < 1.2;  1.02: d 99.8 % 0.66 .. 3.1, max 6.2, |reg| < 4.6;  1.03: |reg| 3.2 on four
+#       frames already; 1.04: 23,000+ candidates, |reg| 64.  At 1.02 / cls_bias -4.2: candidates over 0.05 per frame 0, 0, 19, 4, 1043, 37, 0, 91
+#       (-4.0: up to 1444; -3.8: 2224, over max_candidates).
+#   D2  gain 1.00: d max 0.99;  1.01: d 99.8 % 0.48 .. 1.44, max 3.1, |reg| < 1.8;  1.02: one frame runs away (d 76, |reg| 54);  1.04: |reg| 281.
+#       At 1.01 / cls_bias -4.0: 0, 0, 0, 0, 776, 0, 0, 0 candidates (-3.8: 1588; -3.7: 2389).
+#   D3  gain 0.93 / 0.95: d the same on every frame to three digits (the input signal has died: max 0.35 / 0.40);  0.965: d 99.98 % 0.44 .. 0.53,
+#       max 0.63, |reg| < 0.58;  0.97: two frames leave the band (d max 2.4);  0.975: d 13.6, 3,000 candidates at -5;  1.0: |reg| 123.
+#       At 0.965 / cls_bias -3.42: 0, 0, 0, 0, 0, 165, 0, 2 candidates (-3.40: up to 336; -3.38 at gain 0.97: 2,000 - 20,000).
+# Box regressions are finite at all of these settings.  D0's numbers are at EFFDET_GAIN.  A trained checkpoint needs none of this.
+EFFDET_SCALES = {
+    0: dict(width=1.0, depth=1.0, imgsz=512, fpn_c=64, fpn_cells=3, head_layers=3, gain=EFFDET_GAIN, cls_bias=-5.0),
+    1: dict(width=1.0, depth=1.1, imgsz=640, fpn_c=88, fpn_cells=4, head_layers=3, gain=SYNTH_GAINS["efficientdet-d1"], cls_bias=-4.2),
+    2: dict(width=1.1, depth=1.2, imgsz=768, fpn_c=112, fpn_cells=5, head_layers=3, gain=SYNTH_GAINS["efficientdet-d2"], cls_bias=-4.0),
+    3: dict(width=1.2, depth=1.4, imgsz=896, fpn_c=160, fpn_cells=6, head_layers=4, gain=SYNTH_GAINS["efficientdet-d3"], cls_bias=-3.42),
+}
+
+
+def efficientdet_scaled(scale, **k):
+    """EfficientDet-D<scale> (1..3): models.efficientdet at the compound-scaling row of EFFDET_SCALES; keyword arguments override it."""
+    cfg = EFFDET_SCALES[scale]
+    k.setdefault("imgsz", cfg["imgsz"])
+    k.setdefault("cls_bias", cfg["cls_bias"])
+    return efficientdet(fpn_c=cfg["fpn_c"], fpn_cells=cfg["fpn_cells"], head_layers=cfg["head_layers"], scale=scale, **k)
+
+
+def efficientdet(nc=90, imgsz=512, wsrc=None, seed=0, fpn_c=64, fpn_cells=3, head_layers=3, num_anchors=9, cls_bias=-5.0, scale=0):
+    """EfficientDet-D<scale> (D0 by default; D1..D3 through efficientdet_scaled) up to its two raw head tensors per pyramid level: box regression (dy, dx, dh, dw) x 9 anchors and class logits
     nc x 9 anchors, rows ordered (y, x, anchor) -- what the exported graph feeds its in-graph anchor decode + NMS
     (postproc.EffdetTail).  Symmetric k // 2 padding (the PyTorch-native variant of the architecture): weights of the public
     TF-'same'-padded checkpoints (stride 2 pads right / bottom only) are NOT valid for this graph -- see detectors.EfficientdetDetector.
     cls_bias: the classifier
-    header's bias (trained nets start it at -log(99) = -4.6; -5 leaves ~1 % of the seeded net's anchors over a 0.05 score threshold)."""
+    header's bias (trained nets start it at -log(99) = -4.6; -5 leaves ~1 % of the seeded D0's anchors over a 0.05 score threshold; the
+    other scales' values are in EFFDET_SCALES).  scale: the row of EFFDET_SCALES that sets the backbone's width / depth and the graph's name."""
     H, W = _hw(imgsz)
     assert H % 128 == 0 and W % 128 == 0, "EfficientDet needs inputs divisible by 128 (five pyramid levels, 2x resampling)"
-    ws = wsrc or SynthWeights(seed, gain=EFFDET_GAIN)
-    g = Graph("efficientdet-d0", 3, H, W, ws)
+    cfg = EFFDET_SCALES[scale]
+    ws = wsrc or SynthWeights(seed, gain=cfg["gain"])
+    g = Graph("efficientdet-d%d" % scale, 3, H, W, ws)
     x, c3 = g.input()
-    t = g.conv(x, 32, 3, 2, "stem", true_cin=c3)
+    t = g.conv(x, round_filters(32, cfg["width"]), 3, 2, "stem", true_cin=c3)
     feats, bi = [], 0
-    for si, (e, k, s, c, n) in enumerate(EFFNET_B0):
+    for si, (e, k, s, c, n) in enumerate(effnet_stages(cfg["width"], cfg["depth"])):
         for r in range(n):
             t = _mbconv(g, t, f"blocks.{bi}", e, k, s if r == 0 else 1, c)
             bi += 1
@@ -1362,6 +1407,8 @@ def efficientdet(nc=90, imgsz=512, wsrc=None, seed=0, fpn_c=64, fpn_cells=3, hea
 
 BUILDERS = {
     "efficientdet-d0": lambda **k: efficientdet(**k),
+    "efficientdet-d1": lambda **k: efficientdet_scaled(1, **k), "efficientdet-d2": lambda **k: efficientdet_scaled(2, **k),
+    "efficientdet-d3": lambda **k: efficientdet_scaled(3, **k),
     "yolov8n": lambda **k: yolov8("n", **k), "yolov8s": lambda **k: yolov8("s", **k),
     "yolov8m": lambda **k: yolov8("m", **k), "yolov8l": lambda **k: yolov8("l", **k),
     "yolov8x": lambda **k: yolov8("x", **k),

@@ -97,9 +97,11 @@ class YoloPost:
 
 
 class EffdetTail:
-    """The in-graph tail of the exported EfficientDet-D0 (adas_effdet_tail_*): anchor decode + score threshold + per-class NMS over the ten
-    raw head tensors of the "efficientdet-d0" engine graph -> (boxes xyxy float32, class ids, confidences) per frame, the three arrays
-    EfficientdetDetector.__process_output reads (efficientdetDetector.py:68-70)."""
+    """The in-graph tail of an exported EfficientDet (adas_effdet_tail_*): anchor decode + score threshold + per-class NMS over the ten
+    raw head tensors of an "efficientdet-d0" .. "efficientdet-d3" engine graph -> (boxes xyxy float32, class ids, confidences) per frame,
+    the three arrays EfficientdetDetector.__process_output reads (efficientdetDetector.py:68-70).  Two launches per run: a class-max pass
+    over (anchor chunks x frames) workgroups, then one workgroup per frame for rank, decode and NMS; ADAS_EFFDET_TAIL_ONE_WG=1 in the
+    environment when the object is created selects the older single-workgroup launch (same results, for comparisons)."""
 
     def __init__(self, in_hw, num_classes=90, score_thr=0.05, iou_thr=0.5, max_det=100, max_candidates=2048, max_batch=1, anchor_scale=4.0):
         p = L.EffdetTailParams(int(in_hw[0]), int(in_hw[1]), int(num_classes), int(max_candidates), int(max_det), 0, float(score_thr), float(iou_thr),
