@@ -387,6 +387,34 @@ int adas_lane_geometry_run(adas_lane_geometry* h, const adas_ufld_decode* decode
 int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometry_result* res, int32_t* area_points,
                              int32_t* bird_points);
 
+/* -----------------------------------------------------------------------------------
+ * Bird-view image: replaces the cv2.warpPerspective calls of PerspectiveTransformation.transformToBirdView /
+ * .transformToFrontalView (perspectiveTransformation.py:89-117) for 8-bit BGR frames, INTER_LINEAR, BORDER_CONSTANT 0, on frames
+ * that already sit in HBM.  The arithmetic restates OpenCV 4.5's reference path (csrc/warp_core.h); parity with a real cv2
+ * build is UNPINNED.  One matrix per frame of a batch; matrices may change between runs.
+ * ----------------------------------------------------------------------------------- */
+typedef struct adas_warp adas_warp;
+typedef struct {
+    int32_t src_h, src_w; /* source frames: [batch][src_h][src_w][3] u8 */
+    int32_t dst_h, dst_w; /* warped frames: [batch][dst_h][dst_w][3] u8; all four: 1..4320 rows, 1..16384 columns */
+} adas_warp_params;
+/* Host state only (every matrix starts as the identity); device memory is allocated by the first run / device_view. */
+int adas_warp_create(const adas_warp_params* p, int max_batch, adas_warp** out);
+int adas_warp_destroy(adas_warp* h);
+/* M9: row-major 3x3.  inverse_map = 0: M maps source to destination (the cv2 default) and is inverted here, a singular
+ * matrix is ADAS_ERR_INVALID; inverse_map != 0: M maps destination to source (cv2.WARP_INVERSE_MAP).  frame = -1 sets the
+ * matrix of every frame.  Takes effect with the next run. */
+int adas_warp_set_matrix(adas_warp* h, int frame, const double* M9, int inverse_map);
+/* Warps frames [0, batch) of d_src_bgr, frame f with matrix f.  Asynchronous on `stream`; matrices changed since the last run
+ * are copied to the device on that stream ahead of the kernel, from pageable host memory: such a run may block the host until the
+ * copy is staged, and is not capturable into a graph (a run with no matrix changed since the last one is a plain launch).
+ * d_dst_bgr may be NULL: the handle's own [max_batch][dst_h][dst_w][3] buffer is written. */
+int adas_warp_run(adas_warp* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, int batch, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_dst_bgr [dst_h][dst_w][3], after the last run's stream has drained.  A frame that no
+ * run has written (frame >= the largest batch run with d_dst_bgr = NULL) is ADAS_ERR_INVALID. */
+int adas_warp_fetch(adas_warp* h, int frame, uint8_t* h_dst_bgr);
+int adas_warp_device_view(adas_warp* h, const uint8_t** d_dst_bgr);
+
 /* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Headless counterpart of the reference's demo.py main loop (demo.py:230-296) on the drop-in classes: per frame
-detector -> tracker, lane detector (+ device geometry), distance / collision point, FCWS / LDWS / LKAS state machine.
+detector -> tracker, lane detector (+ device geometry), distance / collision point, bird-view image (device warp of the frame the
+detector staged), FCWS / LDWS / LKAS state machine.
 No window, no video codec: frames come from a seeded synthetic 1280x720 clip (moving rectangles on noise) or from a
 .npy file of uint8 BGR frames (N, H, W, 3); one summary line per frame.
 
@@ -87,7 +88,14 @@ def main():
         vehicle_distance = distanceDetector.calcCollisionPoint(laneDetector.lane_info.area_points)
         if analyzeMsg.CheckStatus() and laneDetector.lane_info.area_status:
             transformView.updateTransformParams(*laneDetector.lane_info.lanes_points[1:3], analyzeMsg.transform_status)
-        (vehicle_direction, vehicle_curvature), vehicle_offset = laneDetector.curve_and_offset
+        birdview_show = transformView.transformToBirdView(objectDetector.staged_frame)    # demo.py:289, from the frame already in HBM
+        bird = laneDetector.birdview_lanes_points                                         # demo.py:291, left by the device geometry
+        # demo.py:292 calls calcCurveAndOffset on the warped image, so this loop does too; laneDetector.curve_and_offset holds the same
+        # three values from the device geometry (the two agree to 1e-7 relative, test_lane_detector_device_geometry: the same points, an fp64 fit on either side)
+        if min(len(bird[1]), len(bird[2])) >= 3:                                          # a parabola needs three points per ego lane
+            (vehicle_direction, vehicle_curvature), vehicle_offset = transformView.calcCurveAndOffset(birdview_show, *bird[1:3])
+        else:
+            (vehicle_direction, vehicle_curvature), vehicle_offset = (None, None), None
         analyzeMsg.UpdateCollisionStatus(vehicle_distance, laneDetector.lane_info.area_status)
         analyzeMsg.UpdateOffsetStatus(vehicle_offset)
         analyzeMsg.UpdateRouteStatus(vehicle_direction, vehicle_curvature)
@@ -100,7 +108,7 @@ def main():
         n += 1
     dt = time.perf_counter() - t0
     print("%d frames in %.2f s (%.1f frames/s, single stream, host frames: upload + 2 nets + post-processing + fetch per frame)" % (n, dt, n / dt))
-    objectDetector.close(); laneDetector.close(); objectTracker.close()
+    transformView.close(); objectDetector.close(); laneDetector.close(); objectTracker.close()
     return n
 
 

@@ -66,6 +66,10 @@ class LaneGeometryResult(C.Structure):
                 ("bird_counts", C.c_int32 * 4), ("curvature", C.c_double), ("offset", C.c_double)]
 
 
+class WarpParams(C.Structure):
+    _fields_ = [("src_h", C.c_int32), ("src_w", C.c_int32), ("dst_h", C.c_int32), ("dst_w", C.c_int32)]
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -187,6 +191,12 @@ _SIGS = {
     "adas_lane_geometry_set_matrix": (C.c_int, [_P, _P]),
     "adas_lane_geometry_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "adas_lane_geometry_fetch": (C.c_int, [_P, C.c_int, C.POINTER(LaneGeometryResult), _P, _P]),
+    "adas_warp_create": (C.c_int, [C.POINTER(WarpParams), C.c_int, C.POINTER(_P)]),
+    "adas_warp_destroy": (C.c_int, [_P]),
+    "adas_warp_set_matrix": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "adas_warp_run": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "adas_warp_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_warp_device_view": (C.c_int, [_P, C.POINTER(_P)]),
     "adas_bytetrack_create": (C.c_int, [C.POINTER(BytetrackParams), C.c_int, C.POINTER(_P)]),
     "adas_bytetrack_destroy": (C.c_int, [_P]),
     "adas_bytetrack_reset": (C.c_int, [_P, C.c_int]),

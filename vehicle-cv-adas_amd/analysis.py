@@ -1,18 +1,22 @@
 """The consumers of the hot path's outputs (SURVEY.md 8f rows f2 + f3), Linux-runnable and without cv2:
 
     SingleCamDistanceMeasure   <- ObjectDetector/distanceMeasure.py:7-93   (distance from box height, nearest object inside the ego lane)
-    PerspectiveTransformation  <- ufldDetector/perspectiveTransformation.py:10-214 (homography of lane POINTS, curvature radius, lateral offset)
+    PerspectiveTransformation  <- ufldDetector/perspectiveTransformation.py:10-214 (homography of lane POINTS, curvature radius, lateral offset;
+                                  the bird-view / frontal-view IMAGE through the device warp, postproc.PerspectiveWarp)
     TaskConditions             <- taskConditions.py:88-312 (median-window FCWS / LDWS / LKAS state machine; the reference file imports
                                   ctypes.windll at module scope and runs on Windows only)
 
 They take what `detectors.py` produces (RectInfo list, LaneInfo) -- a few hundred bytes per frame -- and, like the reference,
 run on the host: after GPU-resident decode/NMS/tracking this is per-frame scalar bookkeeping (<0.2 ms), not a kernel.
-Same public names and call shapes as the reference so demo.py:284-296 reads unchanged; image warping and every Draw*
-method are out of scope (cv2).
+The one per-pixel step, transformToBirdView / transformToFrontalView (cv2.warpPerspective of the whole frame, :89-117), runs on
+the device (csrc/warp_kernels.hip); the library is imported when one of the two is first called, so this module and everything
+else in it work without it.  Same public names and call shapes as the reference so demo.py:284-296 reads unchanged; every
+Draw* method is out of scope (cv2).
 
 Third-party arithmetic restated here (parity UNPINNED against real OpenCV, cv2 is absent): `perspective_matrix`
 (cv2.getPerspectiveTransform: the 8x8 linear system of the four point pairs, solved in float64) and `point_in_polygon`
-(cv2.pointPolygonTest(measureDist=False): +1 inside, 0 on an edge/vertex, -1 outside).  Everything else is pinned by
+(cv2.pointPolygonTest(measureDist=False): +1 inside, 0 on an edge/vertex, -1 outside); cv2.warpPerspective's 8-bit INTER_LINEAR
+arithmetic is restated in csrc/warp_core.h, equally unpinned.  Everything else is pinned by
 tests/golden/analysis.json.gz, produced by the reference's own classes under stubs (tests/golden/make_golden_analysis.py).
 """
 from enum import Enum
@@ -122,10 +126,16 @@ def perspective_matrix(src, dst) -> np.ndarray:
     return np.append(h, 1.0).reshape(3, 3)
 
 
+INTER_LINEAR = 1                  # cv2.INTER_LINEAR: the only interpolation the device warp implements
+
+
 class PerspectiveTransformation:
     def __init__(self, img_size=(1280, 720), logger=None):
         self.img_size = img_size
         self.logger = logger
+        self._warp = None           # postproc.PerspectiveWarp, created by the first transformToBirdView / transformToFrontalView
+        self._warp_key = None
+        self._warp_src = None
         w, h = img_size
         self.src = np.float32([(w * 0.3, h * 0.7), (w * 0.2, h), (w * 0.95, h), (w * 0.8, h * 0.7)])      # :24-27 tl, bl, br, tr
         ox = w / 4
@@ -154,6 +164,56 @@ class PerspectiveTransformation:
             bl, br = (L[:, 0].min() - 5, bl[1]), (R[:, 0].max() + 5, br[1])
         self.src = np.float32([tl, bl, br, tr])
         self._refresh()
+
+    def _warp_image(self, img, M, flags):
+        """cv2.warpPerspective(img, M, self.img_size, flags=flags) on the device.  img: HxWx3 uint8 ndarray, or a detectors.StagedFrame
+        (the frame a detector already uploaded: no second copy)."""
+        if flags != INTER_LINEAR:
+            raise NotImplementedError("warpPerspective flags=%r: only INTER_LINEAR (%d) is implemented on the device" % (flags, INTER_LINEAR))
+        from . import postproc, _lib           # lazy: the rest of this module needs no library
+        staged = hasattr(img, "ptr") and not isinstance(img, np.ndarray)
+        if staged:
+            src_hw = (img.height, img.width)
+        else:
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise Exception("frame must be an HxWx3 uint8 BGR image, got %s" % (img.shape,))
+            src_hw = img.shape[:2]
+        w, h = (int(v) for v in self.img_size)
+        key = (tuple(int(v) for v in src_hw), (h, w))
+        if self._warp_key != key:
+            if self._warp is not None:
+                self._warp.close()
+            self._warp = postproc.PerspectiveWarp(key[0], key[1], 1)
+            self._warp_key = key
+        self._warp.set_matrix(M)             # self.M / self.M_inv as they are now (updateTransformParams replaces them)
+        if staged:
+            self._warp.run(img.ptr, 1)
+        else:
+            if self._warp_src is None or self._warp_src.nbytes < img.nbytes:
+                if self._warp_src is not None:
+                    self._warp_src.free()
+                self._warp_src = _lib.DeviceBuffer(img.nbytes)
+            self._warp_src.upload(img)
+            self._warp.run(self._warp_src.ptr, 1)
+        return self._warp.fetch(0)
+
+    def transformToBirdView(self, img, flags=INTER_LINEAR):
+        """Frontal-view image -> bird-view image of img_size (:89-103)."""
+        return self._warp_image(img, self.M, flags)
+
+    def transformToFrontalView(self, img, flags=INTER_LINEAR):
+        """Bird-view image -> frontal-view image of img_size (:106-117)."""
+        return self._warp_image(img, self.M_inv, flags)
+
+    def close(self):
+        """Releases the device warp handle and the frame buffer the two image methods created (they are created again on the next call).
+        A no-op when neither method has been called."""
+        if self._warp is not None:
+            self._warp.close()
+        if self._warp_src is not None:
+            self._warp_src.free()
+        self._warp = self._warp_key = self._warp_src = None
 
     def transformToBirdViewPoints(self, points):
         """Homogeneous transform of (x, y) points, integer-truncated (:120-142)."""

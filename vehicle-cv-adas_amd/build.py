@@ -21,6 +21,7 @@ UNITS = [
     ("api_common.cpp", []),
     ("post_kernels.hip", ["-ffp-contract=off"]),
     ("pre_kernels.hip", ["-ffp-contract=off"]),
+    ("warp_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

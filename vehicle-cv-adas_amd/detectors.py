@@ -331,6 +331,11 @@ class EfficientdetDetector(_Defaults):
     def object_info(self):
         return self._object_info
 
+    @property
+    def staged_frame(self):
+        """The last frame's device copy (StagedFrame), to hand to the other task classes of the same loop iteration."""
+        return self._stage.staged
+
     def DetectFrame(self, srcimg) -> None:
         fptr, h, w = self._stage.upload(srcimg)
         t = self._stage.tensor_for(self.input_shapes)

@@ -4,6 +4,8 @@ YoloPost      <- YoloDetector.__process_output + Scaler.convert_boxes_coordinate
                  (ObjectDetector/yoloDetector.py:104-157, utils.py:70-87,105-256)
 UfldDecode    <- UltrafastLaneDetectorV2.__process_output (ultrafastLaneDetectorV2.py:114-181)
 DeviceTracker <- BYTETracker.update/reset (ObjectTracker/byteTrack/byteTracker.py:62-200)
+PerspectiveWarp <- cv2.warpPerspective in PerspectiveTransformation.transformToBirdView / transformToFrontalView
+                 (ufldDetector/perspectiveTransformation.py:89-117)
 """
 import ctypes as C
 
@@ -298,6 +300,46 @@ class LaneGeometry:
     def close(self):
         if getattr(self, "h", None):
             L.lib().adas_lane_geometry_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class PerspectiveWarp:
+    """cv2.warpPerspective(frame, M, dsize, INTER_LINEAR, BORDER_CONSTANT 0) of BGR u8 frames resident in HBM, one matrix per frame of a
+    batch (perspectiveTransformation.py:89-117).  OpenCV's reference arithmetic restated (csrc/warp_core.h), parity with a real cv2
+    build unpinned."""
+
+    def __init__(self, src_hw, dst_hw, max_batch=1):
+        p = L.WarpParams(int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]))
+        self.src_hw, self.dst_hw, self.max_batch = (p.src_h, p.src_w), (p.dst_h, p.dst_w), int(max_batch)
+        h = C.c_void_p()
+        L.check(L.lib().adas_warp_create(C.byref(p), self.max_batch, C.byref(h)))
+        self.h = h.value
+
+    def set_matrix(self, M, frame=-1, inverse=False):
+        """M maps source to destination (cv2's default); inverse=True: destination to source (cv2.WARP_INVERSE_MAP).
+        frame=-1: every frame of the batch."""
+        m = np.ascontiguousarray(M, np.float64).reshape(9)
+        L.check(L.lib().adas_warp_set_matrix(self.h, int(frame), L.ptr(m), 1 if inverse else 0))
+
+    def run(self, src_ptr, batch=1, dst_ptr=None, stream=None):
+        """src_ptr: device pointer of [batch][src_h][src_w][3] u8.  dst_ptr=None writes the handle's own buffer (fetch / device_view)."""
+        L.check(L.lib().adas_warp_run(self.h, src_ptr, dst_ptr, int(batch), stream))
+
+    def fetch(self, frame=0):
+        out = np.empty((self.dst_hw[0], self.dst_hw[1], 3), np.uint8)
+        L.check(L.lib().adas_warp_fetch(self.h, int(frame), L.ptr(out)))
+        return out
+
+    def device_view(self):
+        p = C.c_void_p()
+        L.check(L.lib().adas_warp_device_view(self.h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_warp_destroy(self.h)
             self.h = None
 
     __del__ = close
