@@ -146,6 +146,10 @@ typedef struct adas_ml_layer_desc {
 } adas_ml_layer_desc;
 int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch, int precision, int32_t* deps, int32_t* targets,
                        uint64_t* items, int items_cap, int32_t summary[4]);
+/* Which conv kernel one such layer launches on at `batch` frames in `precision` (ADAS_PREC_*), on the description alone: the label
+ * adas_engine_layer_kernel gives the layer in an engine whose max_batch is `batch` (no device: tests/test_conv_route_cpu.py).  `kernel`
+ * only tells 1x1 (4) from 3x3 (any other value); the kernel class comes from the plan. */
+int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precision, char* name, int name_cap);
 /* Debug/parity tap: copy an intermediate activation (by layer index) to the host as NCHW fp32. */
 int adas_engine_fetch_activation(adas_engine* e, int layer, int batch, float* h_out_nchw, int64_t dims[4]);
 

@@ -542,9 +542,11 @@ static int h8_blocks_per_unit(long tiles8, int ncb) {
     return 0;
 }
 
-bool halo8_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& res, int res_mode) {
+bool halo8_applicable(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out, &res = a.res;
+    const int n = a.n, res_mode = a.res_mode;
     if (!h8_mode()) return false;
-    if (kh != 3 || kw != 3 || stride != 1 || pad != 1) return false;
+    if (a.kh != 3 || a.kw != 3 || a.stride != 1 || a.pad != 1) return false;
     if (in.f32 || out.f32 || out.h != in.h || out.w != in.w) return false;
     if ((out.c & 127) || (in.c & 31) || in.c < 64) return false;
     if ((in.cs & 7) || (in.coff & 7) || (out.cs & 7) || (out.coff & 7)) return false;
@@ -568,11 +570,13 @@ static bool h8_ds_enabled() {
     return v == 1;
 }
 
-bool halo8_ds_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& x) {
+bool halo8_ds_applicable(const ConvArgs& a, const TView& x) {
     if (!h8_ds_enabled()) return false;
-    TView none = out;
-    none.p = nullptr;
-    if (!halo8_applicable(kh, kw, stride, pad, n, in, out, none, RES_NONE)) return false;
+    const TView &out = a.out;
+    const int n = a.n;
+    ConvArgs plain = a;   // the shortcut arrives through the MFMAs: the launch reads no residual
+    plain.res_mode = RES_NONE;
+    if (!halo8_applicable(plain)) return false;
     if (x.f32 || (x.c & 31) || x.c < 32 || x.c > 512 || ((x.cs | x.coff) & 7)) return false;
     if ((x.h + 1) / 2 != out.h || (x.w + 1) / 2 != out.w) return false;   // 1x1, stride 2, pad 0
     return (double)n * x.h * x.w * x.cs * 2.0 < (double)H8_OOB;
@@ -622,13 +626,14 @@ static hipError_t h8_launch(const H8Dev& d, int act, dim3 grid, hipStream_t st) 
 
 hipError_t launch_conv_halo8(const ConvArgs& a, hipStream_t st) {
     HaloPlan pl;
-    if (!halo8_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode) || !plan_halo(a.out.h, a.out.w, 1, &pl, H8_MAXPIX, 0, h8_policy()))
-        return hipErrorNotSupported;
+    if (!halo8_applicable(a) || !plan_halo(a.out.h, a.out.w, 1, &pl, H8_MAXPIX, 0, h8_policy())) return hipErrorInvalidValue;
     {   // ADAS_H8_SW=<strip width>: narrower strips = squarer tiles = less halo per window (and more padded pixels): an experiment knob
         static int sw = -1;
         if (sw < 0) { const char* e = getenv("ADAS_H8_SW"); sw = e ? atoi(e) : 0; }
         HaloPlan alt;
-        if (sw > 0 && plan_halo_sw(a.out.h, a.out.w, 1, sw, H8_MAXPIX, &alt) && alt.eff >= 0.6) pl = alt;
+        if (sw > 0 && plan_halo_sw(a.out.h, a.out.w, 1, sw, H8_MAXPIX, &alt) && alt.eff >= 0.6 &&
+            h8_blocks_per_unit(((long)a.n * alt.NS * alt.TPS + 7) / 8, a.out.c / 128) > 0)   // (re-checked against the fill rule, as conv_halo8_x3 does)
+            pl = alt;
     }
     H8Dev d;
     d.in = (const uint16_t*)a.in.p; d.wgt = (const uint16_t*)a.wgt; d.bias = a.bias; d.out = (uint16_t*)a.out.p;
@@ -657,7 +662,7 @@ hipError_t launch_conv_halo8(const ConvArgs& a, hipStream_t st) {
         d.res_mode = RES_NONE;   // the shortcut arrives through the MFMAs
     }
     d.cpw = h8_blocks_per_unit(d.tiles8, d.ncb);
-    if (d.cpw <= 0) return hipErrorNotSupported;
+    if (d.cpw <= 0) return hipErrorInvalidValue;
     const int upt = d.ncb / d.cpw;
     d.mg_upt = (uint32_t)(((1ull << 32) + (uint64_t)upt - 1) / (uint64_t)upt);
     const int units8 = d.tiles8 * upt;

@@ -662,8 +662,10 @@ bool halo8_x3_shape_ok(int kh, int kw, int stride, int pad, const TView& in, con
 }
 size_t halo8_x3_weight_bytes(int cout, int cin) { return (size_t)(x8_cout_pad(cout) / 32) * (size_t)(2 * (x8_cin_pad(cin) / 32)) * X8_SLAB; }
 
-bool halo8_x3_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& res, int res_mode) {
-    if (!halo8_x3_shape_ok(kh, kw, stride, pad, in, out)) return false;
+bool halo8_x3_applicable(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out, &res = a.res;
+    const int n = a.n, res_mode = a.res_mode;
+    if (!halo8_x3_shape_ok(a.kh, a.kw, a.stride, a.pad, in, out)) return false;
     if (res_mode != RES_NONE && ((res.cs & 7) || (res.coff & 7) || res.f32)) return false;
     if ((double)n * in.h * in.w * in.cs * 4.0 >= (double)X8_OOB || (double)n * out.h * out.w * out.cs * 4.0 >= (double)X8_OOB) return false;
     if (res_mode != RES_NONE && (double)n * out.h * out.w * res.cs * 4.0 >= (double)X8_OOB) return false;
@@ -758,8 +760,7 @@ static hipError_t x8_launch(const H8XDev& d, int act, dim3 grid, hipStream_t st)
 
 hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st) {
     HaloPlan pl;
-    if (!a.wgt_h8x3 || !halo8_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode) || !x8_plan(a.out.h, a.out.w, &pl))
-        return hipErrorNotSupported;
+    if (!a.wgt_h8x3 || !halo8_x3_applicable(a) || !x8_plan(a.out.h, a.out.w, &pl)) return hipErrorInvalidValue;
     {   // ADAS_H8X_SW=<strip width>: narrower strips = squarer tiles = smaller windows (less halo re-read) at more padded pixels; the
         // tile grid is then re-checked against the item-count rule below (an experiment knob, like conv_halo8's ADAS_H8_SW)
         static int sw = -1;
@@ -788,7 +789,7 @@ hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st) {
     d.tiles8 = (d.ntiles + 7) / 8;
     d.ncb = x8_cout_pad(a.out.c) / 64;
     d.cpw = x8_blocks_per_unit(d.tiles8, d.ncb);
-    if (d.cpw <= 0) return hipErrorNotSupported;
+    if (d.cpw <= 0) return hipErrorInvalidValue;
     const int upt = d.ncb / d.cpw;
     d.mg_upt = (uint32_t)(((1ull << 32) + (uint64_t)upt - 1) / (uint64_t)upt);
     const int units8 = d.tiles8 * upt;

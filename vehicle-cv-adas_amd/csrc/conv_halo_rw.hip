@@ -353,10 +353,12 @@ static bool rw_enabled() {
     return v == 1;
 }
 
-// Launch-time choice on static shapes (same weight packing as conv_halo).  n = frames in this launch.
-bool halo_rw_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out) {
+// Launch-time choice on static shapes (same weight packing as conv_halo).
+bool halo_rw_applicable(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out;
     if (!rw_enabled()) return false;
-    if (stride != 1 || kh != 3 || kw != 3 || pad != 1) return false;
+    if (a.stride != 1 || a.kh != 3 || a.kw != 3 || a.pad != 1) return false;
+    if (a.res_mode != RES_NONE && (((a.res.cs | a.res.coff) & 7) != 0)) return false;   // the residual is read 16 bytes at a time
     if (in.f32 || out.f32 || out.h != in.h || out.w != in.w) return false;
     if ((in.c & 7) || (in.cs & 7) || (in.coff & 7) || (out.c & 3) || (out.cs & 3) || (out.coff & 3)) return false;
     if (in.c < 16 || in.c > 64 || out.c <= 16 || halo_bn(out.c) == 48) return false;  // BN = 16 / 48 packings stay on conv_halo
@@ -366,7 +368,7 @@ bool halo_rw_applicable(int kh, int kw, int stride, int pad, int n, const TView&
     const int bn = out.c <= 32 ? 32 : RW_BN;
     if (!plan_rw(in.h, in.w, nch, bn, &pl, nullptr) || pl.eff < 0.6) return false;
     // persistence pays only when every workgroup sees several tiles
-    const long tiles = (long)n * pl.NS * pl.TPS * ((out.c + bn - 1) / bn);
+    const long tiles = (long)a.n * pl.NS * pl.TPS * ((out.c + bn - 1) / bn);
     return tiles >= 4 * 256;
 }
 
@@ -391,9 +393,7 @@ hipError_t launch_conv_halo_rw(const ConvArgs& a, hipStream_t st) {
     RwPlan pl;
     const int nch = (a.in.c + 31) / 32;
     int per_cu = 1;
-    if (!halo_rw_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out) ||
-        !plan_rw(a.in.h, a.in.w, nch, a.out.c <= 32 ? 32 : RW_BN, &pl, &per_cu))
-        return hipErrorNotSupported;
+    if (!halo_rw_applicable(a) || !plan_rw(a.in.h, a.in.w, nch, a.out.c <= 32 ? 32 : RW_BN, &pl, &per_cu)) return hipErrorInvalidValue;
     RwDev d;
     d.in = (const uint16_t*)a.in.p; d.wgt = (const uint16_t*)a.wgt; d.bias = a.bias; d.out = (uint16_t*)a.out.p;
     d.res = (const uint16_t*)a.res.p;
@@ -409,7 +409,6 @@ hipError_t launch_conv_halo_rw(const ConvArgs& a, hipStream_t st) {
     int grid = 8 * persist_slots(1) * per_cu / d.NT * d.NT;  // one (or two, see plan_rw) workgroups per CU, a multiple of the channel tiles
     const size_t lds = ((size_t)nch * 9 * bn * 32 + (size_t)2 * nch * pl.maxpix * 32) * 2;
     const bool res = a.res_mode != RES_NONE;
-    if (res && (((a.res.cs | a.res.coff) & 7) != 0)) return hipErrorNotSupported;  // halo_rw_applicable() keeps such layers on conv_halo
     ADAS_DISPATCH_E16(a.prec == PREC_FP16, E, {
         if (bn == 32) {
             if (nch == 1) return res ? rw_launch<E, 1, true, 32>(d, a.act, grid, lds, st) : rw_launch<E, 1, false, 32>(d, a.act, grid, lds, st);

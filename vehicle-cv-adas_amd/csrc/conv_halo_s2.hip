@@ -276,8 +276,9 @@ static bool s2p_enabled() {
 }
 
 // Launch-time choice on static shapes (conv_halo's weight packing): stride 2, 3x3, pad 1, Cout a multiple of 128, no residual.
-bool halo_s2p_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out) {
-    if (!s2p_enabled() || stride != 2 || kh != 3 || kw != 3 || pad != 1 || res_mode != RES_NONE) return false;
+bool halo_s2p_applicable(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out;
+    if (!s2p_enabled() || a.stride != 2 || a.kh != 3 || a.kw != 3 || a.pad != 1 || a.res_mode != RES_NONE) return false;
     if (in.f32 || out.f32 || out.h != (in.h + 2 - 3) / 2 + 1 || out.w != (in.w + 2 - 3) / 2 + 1) return false;
     if ((in.c & 7) || (in.cs & 7) || (in.coff & 7) || (out.c & 127) || (out.cs & 3) || (out.coff & 3)) return false;
     if (in.c < 16 || (long)in.h * in.w * in.cs >= (1L << 30)) return false;
@@ -287,12 +288,12 @@ bool halo_s2p_applicable(int kh, int kw, int stride, int pad, int res_mode, int 
     if (in.c < 128) return false;
     S2Plan pl;
     if (!plan_s2(out.h, out.w, &pl) || pl.eff < 0.45) return false;
-    return (long)n * pl.NS * pl.TPS * (out.c / 128) >= 512;
+    return (long)a.n * pl.NS * pl.TPS * (out.c / 128) >= 512;
 }
 
 hipError_t launch_conv_halo_s2p(const ConvArgs& a, hipStream_t st) {
     S2Plan pl;
-    if (!halo_s2p_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out) || !plan_s2(a.out.h, a.out.w, &pl)) return hipErrorNotSupported;
+    if (!halo_s2p_applicable(a) || !plan_s2(a.out.h, a.out.w, &pl)) return hipErrorInvalidValue;
     S2Dev d;
     d.in = (const uint16_t*)a.in.p; d.wgt = (const uint16_t*)a.wgt; d.bias = a.bias; d.out = (uint16_t*)a.out.p;
     d.in_cs = a.in.cs; d.in_coff = a.in.coff; d.cin = a.in.c; d.H = a.in.h; d.W = a.in.w;
@@ -948,19 +949,21 @@ bool halo_s2p_x3_shape_ok(int kh, int kw, int stride, int pad, int res_mode, con
     return plan_s2(out.h, out.w, &pl) && pl.eff >= 0.45;
 }
 
-bool halo_s2p_x3_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out) {
-    if (!halo_s2p_x3_shape_ok(kh, kw, stride, pad, res_mode, in, out)) return false;
+bool halo_s2p_x3_applicable(const ConvArgs& a) {
+    if (!halo_s2p_x3_shape_ok(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.in, a.out)) return false;
     S2Plan pl;
-    if (!plan_s2(out.h, out.w, &pl)) return false;
+    if (!plan_s2(a.out.h, a.out.w, &pl)) return false;
     // one 8-wave workgroup per CU: the launch has to fill a good part of the chip (ADAS_S2X_MIN_ITEMS, default 96; 256 until the end of
     // round 6: YOLOv8l's 40x40 -> 20x20 layers at 8 frames are 128 items and ran on the generic kernel at 134 TFLOP/s)
     static long min_items = -1;
     if (min_items < 0) { const char* e = getenv("ADAS_S2X_MIN_ITEMS"); min_items = e ? atol(e) : 96; if (min_items < 1) min_items = 96; }
-    return (long)n * pl.NS * pl.TPS * ((out.c + 63) / 64) >= min_items;
+    return (long)a.n * pl.NS * pl.TPS * ((a.out.c + 63) / 64) >= min_items;
 }
 
-// the LDS-DMA form (conv_s2d_x3_kernel); hipErrorNotSupported where it does not apply (ADAS_NO_S2D_X3=1, tensors past the 32-bit offsets)
-static bool s2d_x3_fits(int n, const TView& in, const TView& out) {
+// the LDS-DMA form (conv_s2d_x3_kernel) takes the layer unless ADAS_NO_S2D_X3=1 or a tensor passes the 32-bit offsets: then conv_s2p_x3 runs it
+bool s2d_x3_fits(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out;
+    const int n = a.n;
     static int on = -1;
     if (on < 0) { const char* e = getenv("ADAS_NO_S2D_X3"); on = (e && e[0] == '1') ? 0 : 1; }
     const size_t in_bytes = (size_t)n * in.h * in.w * in.cs * 4, out_bytes = (size_t)n * out.h * out.w * out.cs * 4;
@@ -968,12 +971,9 @@ static bool s2d_x3_fits(int n, const TView& in, const TView& out) {
     const size_t wgt_bytes = (size_t)2 * ncb * nck * S2D_SLAB;
     return on && ncb <= 32 && in_bytes < 0x70000000ull && out_bytes < 0x70000000ull && wgt_bytes < 0x70000000ull;
 }
-// which of the two stride-2 kernels of the split precision a layer runs on (adas_engine_layer_kernel's label)
-bool halo_s2d_x3_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out) {
-    return halo_s2p_x3_applicable(kh, kw, stride, pad, res_mode, n, in, out) && s2d_x3_fits(n, in, out);
-}
-static hipError_t launch_conv_s2d_x3(const ConvArgs& a, const S2Plan& pl, hipStream_t st) {
-    if (!s2d_x3_fits(a.n, a.in, a.out)) return hipErrorNotSupported;
+hipError_t launch_conv_s2d_x3(const ConvArgs& a, hipStream_t st) {
+    S2Plan pl;
+    if (!a.wgt_h8x3 || !halo_s2p_x3_applicable(a) || !s2d_x3_fits(a) || !plan_s2(a.out.h, a.out.w, &pl)) return hipErrorInvalidValue;
     const size_t in_bytes = (size_t)a.n * a.in.h * a.in.w * a.in.cs * 4, out_bytes = (size_t)a.n * a.out.h * a.out.w * a.out.cs * 4;
     const int ncb = (a.out.c + 63) / 64, nck = 2 * (a.in.c / 32);
     const size_t wgt_bytes = (size_t)2 * ncb * nck * S2D_SLAB;
@@ -992,7 +992,7 @@ static hipError_t launch_conv_s2d_x3(const ConvArgs& a, const S2Plan& pl, hipStr
     d.ncb = ncb;
     { static int xm = -1; if (xm < 0) { const char* e = getenv("ADAS_HALO_XMAP"); xm = e ? atoi(e) : 1; } d.xmap = xm; }
     const size_t lds = (size_t)4 * d.plane16 * 64 + 9 * S2D_TAP;
-    if (lds > 160 * 1024) return hipErrorNotSupported;   // (plan_s2 keeps 4 planes <= S2_MAXPIX pixels: plane16 <= 352; its mg_pw covers plane + 8 >= plane16 pixels)
+    if (lds > 160 * 1024) return hipErrorInvalidValue;   // (plan_s2 keeps 4 planes <= S2_MAXPIX pixels: plane16 <= 352; its mg_pw covers plane + 8 >= plane16 pixels)
     const int nvb = 8 * d.tiles8 * d.ncb;
     // workgroups per CU over the launch (ADAS_S2D_ROUNDS, default 16: up to 4,096 workgroups, the later ones dealt as CUs fall free).  One
     // persistent workgroup per CU (= 1) is the faster launch on its own (profiles/r06/s2d_x3_phases.txt) but in the step, where the other
@@ -1023,12 +1023,7 @@ static hipError_t launch_conv_s2d_x3(const ConvArgs& a, const S2Plan& pl, hipStr
 
 hipError_t launch_conv_s2p_x3(const ConvArgs& a, hipStream_t st) {
     S2Plan pl;
-    if (!a.wgt_h8x3 || !halo_s2p_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out) || !plan_s2(a.out.h, a.out.w, &pl))
-        return hipErrorNotSupported;
-    {
-        const hipError_t e = launch_conv_s2d_x3(a, pl, st);
-        if (e != hipErrorNotSupported) return e;
-    }
+    if (!a.wgt_h8x3 || !halo_s2p_x3_applicable(a) || !plan_s2(a.out.h, a.out.w, &pl)) return hipErrorInvalidValue;
     S2XDev d;
     d.in = (const unsigned char*)a.in.p; d.wgt = (const uint16_t*)a.wgt_h8x3; d.bias = a.bias; d.out = (x3s*)a.out.p;
     d.in_cs = a.in.cs; d.in_coff = a.in.coff; d.cin = a.in.c; d.H = a.in.h; d.W = a.in.w;

@@ -317,62 +317,43 @@ static Tile pick_tile(const ConvArgs& a, int prec) {
     return Tile{bm, bn};
 }
 
-const char* conv_tile_name(const ConvArgs& a, int prec) {
-    Tile t = pick_tile(a, prec);
-    static thread_local char buf[32];
-    snprintf(buf, sizeof(buf), "%dx%d", t.bm, t.bn);
-    return buf;
-}
+static const char* act_tag(int act) { return act == ACT_SILU ? "SILU" : (act == ACT_RELU ? "RELU" : (act == ACT_LEAKY ? "LEAKY" : "NONE")); }
 
 // Name of the kernel instantiation a conv launch resolves to (as rocprofv3 --kernel-trace prints it, minus namespaces).
-const char* conv_kernel_name(const ConvArgs& a, int prec, int kernel) {
+const char* conv_kernel_name(const ConvArgs& a, bool stem) {
     static thread_local char buf[96];
-    if (prec == PREC_X3 && kernel == CONV_STEM) {
-        snprintf(buf, sizeof(buf), "conv_stem_x3_kernel<%d,%d,%s>", a.kh, (a.out.c + 15) / 16, a.act == ACT_SILU ? "SILU" : (a.act == ACT_RELU ? "RELU" : "LEAKY"));
+    const char* actn = act_tag(a.act);
+    if (stem) {   // (the split precision's stem is instantiated for SiLU, ReLU and leaky ReLU only: stem_x3_applicable)
+        snprintf(buf, sizeof(buf), a.prec == PREC_X3 ? "conv_stem_x3_kernel<%d,%d,%s>" : "conv_stem_kernel<%d,%d,%s>", a.kh, (a.out.c + 15) / 16, actn);
         return buf;
     }
-    if (prec == PREC_X3 && kernel == CONV_FC) return "fc_x3_kernel";
-    if (prec == PREC_X3 && kernel == CONV_PW) {
-        snprintf(buf, sizeof(buf), "conv_pwx3_kernel<%d>", (a.in.c + 31) / 32);
-        return buf;
-    }
-    if (prec == PREC_X3) {
-        if (a.wgt_h8x3 && halo8_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) {
-            snprintf(buf, sizeof(buf), "conv_h8x3_kernel<%s>", a.act == ACT_SILU ? "SILU" : (a.act == ACT_RELU ? "RELU" : (a.act == ACT_LEAKY ? "LEAKY" : "NONE")));
-            return buf;
+    switch (conv_route(a)) {
+        case ConvRoute::X3_FC: return "fc_x3_kernel";
+        case ConvRoute::X3_PW: snprintf(buf, sizeof(buf), "conv_pwx3_kernel<%d>", (a.in.c + 31) / 32); break;
+        case ConvRoute::H8X3: snprintf(buf, sizeof(buf), "conv_h8x3_kernel<%s>", actn); break;
+        case ConvRoute::S2D_X3: snprintf(buf, sizeof(buf), "conv_s2d_x3_kernel<%s>", actn); break;
+        case ConvRoute::S2P_X3: snprintf(buf, sizeof(buf), "conv_s2p_x3_kernel<%s>", actn); break;
+        case ConvRoute::X3: return conv_x3_kernel_name(a);
+        case ConvRoute::HALO:
+            snprintf(buf, sizeof(buf), a.stride == 1 && halo_tile_pixels(a) == 128 ? "conv_halo_kernel<%d,%s,s%d,bm128>" : "conv_halo_kernel<%d,%s,s%d>",
+                     a.halo_bn > 0 ? a.halo_bn : halo_bn(a.out.c), actn, a.stride);
+            break;
+        case ConvRoute::HALO_RW:
+            snprintf(buf, sizeof(buf), a.out.c <= 32 ? "conv_halo_rw_kernel<%d,%s,bn32>" : "conv_halo_rw_kernel<%d,%s>", (a.in.c + 31) / 32, actn);
+            break;
+        case ConvRoute::S2P: snprintf(buf, sizeof(buf), "conv_s2p_kernel<%s>", actn); break;
+        case ConvRoute::H8: snprintf(buf, sizeof(buf), "conv_h8_kernel<%s>", actn); break;
+        case ConvRoute::FC: return "fc_kernel";
+        case ConvRoute::PW: snprintf(buf, sizeof(buf), "conv_pw_kernel<%d>", (a.in.c + 31) / 32); break;
+        case ConvRoute::PWG: return pwg_kernel_name(a.m, a.out.c);
+        case ConvRoute::IGEMM: {
+            Tile t = pick_tile(a, a.prec);
+            const bool of32 = a.out.f32 || a.prec == PREC_FP32;
+            const char* en = a.prec == PREC_FP32 ? "f32" : (a.prec == PREC_FP16 ? "f16" : "bf16");
+            snprintf(buf, sizeof(buf), "conv_igemm_kernel<%s,%s,%d,%d>", en, of32 ? "f32" : en, t.bm, t.bn);
+            break;
         }
-        if (a.wgt_h8x3 && halo_s2p_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) {
-            snprintf(buf, sizeof(buf), "%s<%s>", halo_s2d_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out) ? "conv_s2d_x3_kernel" : "conv_s2p_x3_kernel",
-                     a.act == ACT_SILU ? "SILU" : (a.act == ACT_RELU ? "RELU" : (a.act == ACT_LEAKY ? "LEAKY" : "NONE")));
-            return buf;
-        }
-        return conv_x3_kernel_name(a);
-    }
-    const char* actn = a.act == ACT_SILU ? "SILU" : (a.act == ACT_RELU ? "RELU" : (a.act == ACT_LEAKY ? "LEAKY" : "NONE"));
-    if (kernel == CONV_HALO && a.halo_bn > 0 && a.halo_bn != halo_bn(a.out.c)) {
-        snprintf(buf, sizeof(buf), a.stride == 1 && halo_tile_pixels(a) == 128 ? "conv_halo_kernel<%d,%s,s%d,bm128>" : "conv_halo_kernel<%d,%s,s%d>", a.halo_bn, actn, a.stride);
-    } else if (kernel == CONV_HALO && halo_rw_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out)) {
-        snprintf(buf, sizeof(buf), a.out.c <= 32 ? "conv_halo_rw_kernel<%d,%s,bn32>" : "conv_halo_rw_kernel<%d,%s>", (a.in.c + 31) / 32, actn);
-    } else if (kernel == CONV_HALO && halo_s2p_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) {
-        snprintf(buf, sizeof(buf), "conv_s2p_kernel<%s>", actn);
-    } else if (kernel == CONV_HALO && halo8_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) {
-        snprintf(buf, sizeof(buf), "conv_h8_kernel<%s>", actn);
-    } else if (kernel == CONV_HALO) {
-        snprintf(buf, sizeof(buf), a.stride == 1 && halo_tile_pixels(a) == 128 ? "conv_halo_kernel<%d,%s,s%d,bm128>" : "conv_halo_kernel<%d,%s,s%d>",
-                 halo_bn(a.out.c), actn, a.stride);
-    } else if (kernel == CONV_FC) {
-        snprintf(buf, sizeof(buf), "fc_kernel");
-    } else if (kernel == CONV_PW) {
-        snprintf(buf, sizeof(buf), "conv_pw_kernel<%d>", (a.in.c + 31) / 32);
-    } else if (kernel == CONV_STEM) {
-        snprintf(buf, sizeof(buf), "conv_stem_kernel<%d,%d,%s>", a.kh, (a.out.c + 15) / 16, actn);
-    } else if (kernel == CONV_GATHER && pwg_applicable(prec, a.kh, a.kw, a.stride, a.pad, a.in, a.out, a.res, a.res_mode)) {
-        snprintf(buf, sizeof(buf), "%s", pwg_kernel_name(a.m, a.out.c));
-    } else {
-        Tile t = pick_tile(a, prec);
-        const bool of32 = a.out.f32 || prec == PREC_FP32;
-        const char* en = prec == PREC_FP32 ? "f32" : (prec == PREC_FP16 ? "f16" : "bf16");
-        snprintf(buf, sizeof(buf), "conv_igemm_kernel<%s,%s,%d,%d>", en, of32 ? "f32" : en, t.bm, t.bn);
+        case ConvRoute::INVALID: return "(no kernel takes this launch)";
     }
     return buf;
 }
@@ -456,50 +437,52 @@ ConvPlan plan_conv(int prec, int kh, int kw, int stride, int pad, int max_n, int
     return p;
 }
 
-hipError_t launch_conv(const ConvArgs& a, int prec, hipStream_t st) {
-    ConvPlan pl = plan_conv(prec, a.kh, a.kw, a.stride, a.pad, a.max_n, a.res_mode, a.in, a.out);
-    if (pl.kpad != a.kpad) return hipErrorInvalidValue;  // weights were packed for a different plan
-    if (prec == PREC_X3) {
-        if ((a.up_c > 0 && pl.kernel != CONV_PW) || a.ds_w) return hipErrorInvalidValue;
-        if (pl.kernel == CONV_FC) return launch_fc_x3(a, st);
-        if (pl.kernel == CONV_PW) return launch_conv_pw_x3(a, st);
-        if (a.wgt_h8x3 && halo8_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) {
-            hipError_t e = launch_conv_halo8_x3(a, st);
-            if (e != hipErrorNotSupported) return e;
-        }
-        if (a.wgt_h8x3 && halo_s2p_x3_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) {
-            hipError_t e = launch_conv_s2p_x3(a, st);
-            if (e != hipErrorNotSupported) return e;
-        }
-        return launch_conv_x3(a, st);
+ConvRoute conv_route(const ConvArgs& a) {
+    const ConvPlan pl = plan_conv(a.prec, a.kh, a.kw, a.stride, a.pad, a.max_n, a.res_mode, a.in, a.out);
+    if (pl.kpad != a.kpad) return ConvRoute::INVALID;                     // weights were packed for a different plan
+    if (a.up_c > 0 && pl.kernel != CONV_PW) return ConvRoute::INVALID;    // only conv_pw / conv_pw_x3 fetch the folded upsample's channels
+    if (a.prec == PREC_X3) {
+        if (a.ds_w) return ConvRoute::INVALID;
+        if (pl.kernel == CONV_FC) return ConvRoute::X3_FC;
+        if (pl.kernel == CONV_PW) return ConvRoute::X3_PW;
+        // the two half-chunk kernels read the second weight packing (the engine gave it to the layer if its shape can take either)
+        if (a.wgt_h8x3 && halo8_x3_applicable(a)) return ConvRoute::H8X3;
+        if (a.wgt_h8x3 && halo_s2p_x3_applicable(a)) return s2d_x3_fits(a) ? ConvRoute::S2D_X3 : ConvRoute::S2P_X3;
+        return ConvRoute::X3;
     }
-    if (a.up_c > 0 && pl.kernel != CONV_PW) return hipErrorInvalidValue;   // only conv_pw fetches the folded upsample's channels
-    if (a.ds_w) {   // the engine dropped the projection's launch: only conv_halo8 computes it inside this conv
-        if (pl.kernel != CONV_HALO) return hipErrorInvalidValue;
-        hipError_t e = launch_conv_halo8(a, st);
-        return e == hipErrorNotSupported ? hipErrorInvalidValue : e;
-    }
-    if (pl.kernel == CONV_HALO && a.halo_bn > 0 && a.halo_bn != halo_bn(a.out.c)) return launch_conv_halo(a, st);   // packed for narrower blocks
     if (pl.kernel == CONV_HALO) {
-        if (halo_rw_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out)) {
-            hipError_t e = launch_conv_halo_rw(a, st);
-            if (e != hipErrorNotSupported) return e;  // e.g. a residual view that is not 16-byte aligned: same packing, other kernel
-        }
-        if (halo_s2p_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) {
-            hipError_t e = launch_conv_halo_s2p(a, st);
-            if (e != hipErrorNotSupported) return e;
-        }
-        if (halo8_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) {
-            hipError_t e = launch_conv_halo8(a, st);
-            if (e != hipErrorNotSupported) return e;
-        }
-        return launch_conv_halo(a, st);
+        const ConvRoute r = (a.halo_bn > 0 && a.halo_bn != halo_bn(a.out.c)) ? ConvRoute::HALO   // packed for narrower blocks: conv_halo only
+                            : halo_rw_applicable(a)                          ? ConvRoute::HALO_RW
+                            : halo_s2p_applicable(a)                         ? ConvRoute::S2P
+                            : halo8_applicable(a)                            ? ConvRoute::H8
+                                                                             : ConvRoute::HALO;
+        // ds_w: the engine dropped the projection's launch, and only conv_h8 computes it inside this conv
+        return a.ds_w && r != ConvRoute::H8 ? ConvRoute::INVALID : r;
     }
-    if (pl.kernel == CONV_PW) return launch_conv_pw(a, st);
-    if (pl.kernel == CONV_FC) return a.res_mode == RES_NONE ? launch_fc(a, st) : hipErrorInvalidValue;
-    if (pwg_applicable(prec, a.kh, a.kw, a.stride, a.pad, a.in, a.out, a.res, a.res_mode)) {   // wide 1x1: same packing, K-looped GEMM kernel
-        hipError_t e = launch_conv_pwg(a, st);
-        if (e != hipErrorNotSupported) return e;
+    if (a.ds_w) return ConvRoute::INVALID;
+    if (pl.kernel == CONV_PW) return ConvRoute::PW;
+    if (pl.kernel == CONV_FC) return a.res_mode == RES_NONE ? ConvRoute::FC : ConvRoute::INVALID;
+    return pwg_applicable(a) ? ConvRoute::PWG : ConvRoute::IGEMM;   // wide 1x1: same packing, K-looped GEMM kernel
+}
+
+hipError_t launch_conv(const ConvArgs& a, hipStream_t st) {
+    const int prec = a.prec;
+    switch (conv_route(a)) {
+        case ConvRoute::INVALID: return hipErrorInvalidValue;
+        case ConvRoute::X3_FC: return launch_fc_x3(a, st);
+        case ConvRoute::X3_PW: return launch_conv_pw_x3(a, st);
+        case ConvRoute::H8X3: return launch_conv_halo8_x3(a, st);
+        case ConvRoute::S2D_X3: return launch_conv_s2d_x3(a, st);
+        case ConvRoute::S2P_X3: return launch_conv_s2p_x3(a, st);
+        case ConvRoute::X3: return launch_conv_x3(a, st);
+        case ConvRoute::HALO: return launch_conv_halo(a, st);
+        case ConvRoute::HALO_RW: return launch_conv_halo_rw(a, st);
+        case ConvRoute::S2P: return launch_conv_halo_s2p(a, st);
+        case ConvRoute::H8: return launch_conv_halo8(a, st);
+        case ConvRoute::PW: return launch_conv_pw(a, st);
+        case ConvRoute::FC: return launch_fc(a, st);
+        case ConvRoute::PWG: return launch_conv_pwg(a, st);
+        case ConvRoute::IGEMM: break;
     }
     ConvDev d;
     d.in = a.in.p; d.wgt = a.wgt; d.bias = a.bias; d.out = a.out.p; d.res = a.res.p;

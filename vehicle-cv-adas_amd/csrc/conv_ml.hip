@@ -429,12 +429,7 @@ bool ml_layer_supported(const ConvArgs& a, int kernel) {
     if (a.res_mode != RES_NONE && (!a.res.p || a.res.f32 || !bytes_fit_31(a.res, a.n))) return false;
     if (kernel == CONV_HALO) {
         if (a.up_c > 0) return false;
-        // launch_conv's order of choice: the persistent / stride-2 / LDS-DMA kernels come first and have no tile body here
-        if (!(a.halo_bn > 0 && a.halo_bn != halo_bn(a.out.c))) {
-            if (halo_rw_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out)) return false;
-            if (halo_s2p_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) return false;
-            if (halo8_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) return false;
-        }
+        if (conv_route(a) != ConvRoute::HALO) return false;   // the persistent / stride-2 / LDS-DMA kernels have no tile body here
         HaloDev d;
         int bn, bm;
         size_t lds;
@@ -749,11 +744,7 @@ int ml_plan_status(const MlPlan* p, unsigned* error_word, unsigned* head16) {
 bool group_layer_supported(const ConvArgs& a, int kernel) {
     if (kernel != CONV_HALO || !prec_is16(a.prec) || a.in.f32 || a.out.f32 || a.ds_w || a.up_c > 0) return false;
     if (a.act != ACT_NONE && a.act != ACT_SILU && a.act != ACT_RELU && a.act != ACT_LEAKY) return false;
-    if (!(a.halo_bn > 0 && a.halo_bn != halo_bn(a.out.c))) {   // launch_conv's order of choice
-        if (halo_rw_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out)) return false;
-        if (halo_s2p_applicable(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.n, a.in, a.out)) return false;
-        if (halo8_applicable(a.kh, a.kw, a.stride, a.pad, a.n, a.in, a.out, a.res, a.res_mode)) return false;
-    }
+    if (conv_route(a) != ConvRoute::HALO) return false;
     HaloDev d;
     int bn, bm;
     size_t lds;

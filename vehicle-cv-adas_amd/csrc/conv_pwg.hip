@@ -176,13 +176,13 @@ static bool pwg_enabled() {
     return v == 1;
 }
 
-bool pwg_applicable(int prec, int kh, int kw, int stride, int pad, const TView& in, const TView& out, const TView& res, int res_mode) {
-    if (!pwg_enabled() || !prec_is16(prec) || in.f32 || out.f32) return false;
-    if (kh != 1 || kw != 1 || stride != 1 || pad != 0) return false;
+bool pwg_applicable(const ConvArgs& a) {
+    const TView &in = a.in, &out = a.out, &res = a.res;
+    if (!pwg_enabled() || !prec_is16(a.prec) || in.f32 || out.f32) return false;
+    if (a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.kpad < in.c) return false;
     if (in.h == 1 && in.w == 1) return false;   // Linear layers: conv_fc.hip
     if ((in.c & 7) || in.c < 2 * PWG_KS || (in.cs & 7) || (in.coff & 7) || (out.c & 3) || (out.cs & 3) || (out.coff & 3)) return false;
-    if (res_mode != RES_NONE && (res.f32 || (res.cs & 3) || (res.coff & 3))) return false;
-    return true;
+    return a.res_mode == RES_NONE || !(res.f32 || (res.cs & 3) || (res.coff & 3));
 }
 
 // BM: 128-pixel tiles unless they would leave the chip with fewer than two workgroups per CU
@@ -193,7 +193,7 @@ static int pwg_bm(int m, int cout) {
 const char* pwg_kernel_name(int m, int cout) { return pwg_bm(m, cout) == 128 ? "conv_pwg_kernel<128>" : "conv_pwg_kernel<64>"; }
 
 hipError_t launch_conv_pwg(const ConvArgs& a, hipStream_t st) {
-    if (!pwg_applicable(a.prec, a.kh, a.kw, a.stride, a.pad, a.in, a.out, a.res, a.res_mode) || a.kpad < a.in.c) return hipErrorNotSupported;
+    if (!pwg_applicable(a)) return hipErrorInvalidValue;
     PwgDev d;
     d.in = (const uint16_t*)a.in.p; d.wgt = (const uint16_t*)a.wgt; d.bias = a.bias; d.out = (uint16_t*)a.out.p; d.res = (const uint16_t*)a.res.p;
     d.in_cs = a.in.cs; d.in_coff = a.in.coff; d.K = a.in.c; d.KP = a.kpad;

@@ -28,21 +28,6 @@ static TView make_view(const adas_engine* e, int buf, int coff, int c) {
     return v;
 }
 
-// does conv `ci` (with a projection shortcut link) take its shortcut into its own launch at this batch?
-static bool ds_folded(const adas_engine* e, int ci, int batch) {
-    const EngOp& c = e->ops[ci];
-    if (c.ds_src < 0 || c.kernel != CONV_HALO || c.halo_bn > 0) return false;   // (a narrow-block packing runs on conv_halo only)
-    const FileOp& o = c.f;
-    const FileOp& d = e->ops[c.ds_src].f;
-    // exactly launch_conv's order of choice: halo_rw and the stride-2 kernel come before conv_halo8 and know nothing of ds_w, and
-    // conv_halo8 is asked with the conv's real residual view (the projection's output buffer)
-    const TView in = make_view(e, o.in_buf[0], o.in_coff[0], o.in_c[0]), out = make_view(e, o.out_buf, o.out_coff, o.out_c);
-    if (halo_rw_applicable(o.kh, o.kw, o.stride, o.pad, batch, in, out)) return false;
-    if (halo_s2p_applicable(o.kh, o.kw, o.stride, o.pad, o.res_mode, batch, in, out)) return false;
-    if (!halo8_applicable(o.kh, o.kw, o.stride, o.pad, batch, in, out, make_view(e, o.res_buf, o.res_coff, o.out_c), o.res_mode)) return false;
-    return halo8_ds_applicable(o.kh, o.kw, o.stride, o.pad, batch, in, out, make_view(e, d.in_buf[0], d.in_coff[0], d.in_c[0]));
-}
-
 // is op `i` one of the three convs a fused C2f launch computes besides its cv1?
 static bool in_c2f(const adas_engine* e, int i) {
     for (auto& q : e->ops)
@@ -56,7 +41,7 @@ static bool is_c2f_tail(const adas_engine* e, int i) {   // the block's cv2: its
     return false;
 }
 
-// The ConvArgs engine_run_op launches op `i` (a plain OP_CONV: not a stem / pair / C2f launch) with at this batch.
+// The ConvArgs of op `i` (a plain OP_CONV: not a stem / pair / C2f launch) at this batch, without a folded projection shortcut (fold_ds).
 static ConvArgs conv_args_of(const adas_engine* e, int i, int batch) {
     const EngOp& op = e->ops[i];
     const FileOp& o = op.f;
@@ -72,18 +57,34 @@ static ConvArgs conv_args_of(const adas_engine* e, int i, int batch) {
     a.k = op.k; a.kpad = op.kpad; a.m = batch * a.out.h * a.out.w; a.max_n = e->max_batch; a.prec = e->prec;
     if (op.has_x3h8) a.wgt_h8x3 = wb + op.x3h8_w_off;
     a.halo_bn = op.halo_bn;
-    if (op.ds_src >= 0 && ds_folded(e, i, batch)) {
-        const EngOp& dsop = e->ops[op.ds_src];
-        a.ds_in = make_view(e, dsop.f.in_buf[0], dsop.f.in_coff[0], dsop.f.in_c[0]);
-        a.ds_w = wb + dsop.ds_w_off;
-        a.ds_bias = (const float*)(wb + dsop.b_off);
-    }
     if (op.up_src >= 0) {
         const FileOp& u = e->ops[op.up_src].f;
         a.up = make_view(e, u.in_buf[0], u.in_coff[0], u.in_c[0]);
         a.up_c = (int)u.out_c;
     }
     return a;
+}
+
+// `a` = conv_args_of(e, i, batch): does the launch take the conv's projection shortcut (if it has a link to one) into itself?  Only conv_h8
+// computes it, so: where the conv runs on conv_h8 as it is (asked with its real residual view, the projection's output buffer) and conv_h8
+// can carry this projection.  Then the projection's arguments are added to `a`.
+static bool fold_ds(const adas_engine* e, int i, ConvArgs* a) {
+    if (e->ops[i].ds_src < 0 || e->ops[i].kernel != CONV_HALO) return false;
+    const EngOp& dsop = e->ops[e->ops[i].ds_src];
+    const TView x = make_view(e, dsop.f.in_buf[0], dsop.f.in_coff[0], dsop.f.in_c[0]);
+    if (conv_route(*a) != ConvRoute::H8 || !halo8_ds_applicable(*a, x)) return false;
+    unsigned char* wb = (unsigned char*)e->d_weights;
+    a->ds_in = x;
+    a->ds_w = wb + dsop.ds_w_off;
+    a->ds_bias = (const float*)(wb + dsop.b_off);
+    return true;
+}
+
+// does conv `ci` (with a projection shortcut link) take its shortcut into its own launch at this batch?
+static bool ds_folded(const adas_engine* e, int ci, int batch) {
+    if (e->ops[ci].ds_src < 0) return false;
+    ConvArgs a = conv_args_of(e, ci, batch);
+    return fold_ds(e, ci, &a);
 }
 
 // ---- multi-layer launches (conv_ml.hip): opt-in, ADAS_ML=1 when the engine is created.
@@ -974,17 +975,9 @@ int adas_engine_layer_kernel(const adas_engine* e, int layer, int batch, char* n
     } else if (o.type == OP_CONV && op.kernel == CONV_STEM && op.fuse_conv2 >= 0) {
         snprintf(name, cap, e->prec == PREC_X3 ? "conv_stem2_x3_kernel<%d>+conv3x3s2" : "conv_stem_kernel<%d,1,SILU>+conv3x3s2", (int)o.kh);
     } else if (o.type == OP_CONV) {
-        ConvArgs a;
-        a.in = make_view(e, o.in_buf[0], o.in_coff[0], o.in_c[0]);
-        a.out = make_view(e, o.out_buf, o.out_coff, o.out_c);
-        a.n = batch; a.kh = o.kh; a.kw = o.kw; a.stride = o.stride; a.pad = o.pad; a.act = o.act; a.res_mode = o.res_mode;
-        if (o.res_mode != RES_NONE) a.res = make_view(e, o.res_buf, o.res_coff, o.out_c);
-        else { a.res = a.out; a.res.p = nullptr; }
-        a.k = op.k; a.kpad = op.kpad; a.m = batch * a.out.h * a.out.w; a.max_n = e->max_batch; a.prec = e->prec;
-        if (op.has_x3h8) a.wgt_h8x3 = (const unsigned char*)e->d_weights + op.x3h8_w_off;
-        a.halo_bn = op.halo_bn;
-        snprintf(name, cap, "%s%s%s", conv_kernel_name(a, e->prec, op.kernel), op.fuse_pool >= 0 ? "+pool" : "",
-                 (op.ds_src >= 0 && ds_folded(e, layer, batch)) ? "+shortcut" : "");
+        ConvArgs a = conv_args_of(e, layer, batch);
+        const bool shortcut = fold_ds(e, layer, &a);
+        snprintf(name, cap, "%s%s%s", conv_kernel_name(a, op.kernel == CONV_STEM), op.fuse_pool >= 0 ? "+pool" : "", shortcut ? "+shortcut" : "");
     } else if (o.type == OP_DETECT_V8 && op.det_src[0] >= 0) {
         snprintf(name, cap, e->prec == PREC_X3 ? "detect_v8_fused_x3_kernel" : "detect_v8_fused_kernel");
     } else if (o.type == OP_DETECT_V5 && op.det_src[0] >= 0) {
@@ -1096,8 +1089,9 @@ int engine_run_op(adas_engine* e, int i, const float* d_in, int batch, hipStream
                                        b.f.res_mode != RES_NONE, e->prec, st);
                 break;
             }
-            const ConvArgs a = conv_args_of(e, i, batch);
-            err = launch_conv(a, e->prec, st);
+            ConvArgs a = conv_args_of(e, i, batch);
+            fold_ds(e, i, &a);
+            err = launch_conv(a, st);
             break;
         }
         case OP_MAXPOOL:
@@ -1458,28 +1452,33 @@ int adas_engine_launch_count(adas_engine* e, int batch) {
     return n;
 }
 
-int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch, int precision, int32_t* deps, int32_t* targets, uint64_t* items,
-                       int items_cap, int32_t summary[4]) {
-    ADAS_REQUIRE(layers && n_layers > 0 && batch > 0 && deps && targets && summary, ADAS_ERR_INVALID, "adas_debug_ml_plan: bad argument");
-    std::vector<ConvArgs> ls;
-    std::vector<int> ks;
+// The ConvArgs a layer description stands for at this batch (no device: the pointers are placeholders that are never read).
+static ConvArgs conv_args_of_desc(const adas_ml_layer_desc& d, int batch, int precision) {
     auto view = [](const adas_ml_view& v) {
         TView t;
         t.p = (void*)(uintptr_t)v.buf; t.cs = v.cs; t.coff = v.coff; t.c = v.c; t.h = v.h; t.w = v.w; t.f32 = 0;
         return t;
     };
+    ConvArgs a;
+    a.in = view(d.x); a.out = view(d.y);
+    if (d.res_mode != RES_NONE) a.res = view(d.res);
+    else { a.res = a.out; a.res.p = nullptr; }
+    a.wgt = (const void*)(uintptr_t)0x1000; a.bias = (const float*)(uintptr_t)0x1000;
+    a.n = batch; a.kh = a.kw = d.kernel == CONV_PW ? 1 : 3; a.stride = d.stride; a.pad = d.kernel == CONV_PW ? 0 : 1; a.act = d.act; a.res_mode = d.res_mode;
+    a.k = a.kh * a.kw * a.in.c; a.kpad = (a.kh * a.kw * ((a.in.c + 31) / 32 * 32) + 31) / 32 * 32; a.m = batch * a.out.h * a.out.w; a.max_n = batch; a.prec = precision;
+    a.halo_bn = d.halo_bn;
+    if (d.up_c > 0) { a.up = view(d.up); a.up_c = d.up_c; }
+    return a;
+}
+
+int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch, int precision, int32_t* deps, int32_t* targets, uint64_t* items,
+                       int items_cap, int32_t summary[4]) {
+    ADAS_REQUIRE(layers && n_layers > 0 && batch > 0 && deps && targets && summary, ADAS_ERR_INVALID, "adas_debug_ml_plan: bad argument");
+    std::vector<ConvArgs> ls;
+    std::vector<int> ks;
     for (int i = 0; i < n_layers; ++i) {
-        const adas_ml_layer_desc& d = layers[i];
-        ConvArgs a;
-        a.in = view(d.x); a.out = view(d.y);
-        if (d.res_mode != RES_NONE) a.res = view(d.res);
-        else { a.res = a.out; a.res.p = nullptr; }
-        a.wgt = (const void*)(uintptr_t)0x1000; a.bias = (const float*)(uintptr_t)0x1000;
-        a.n = batch; a.kh = a.kw = d.kernel == CONV_PW ? 1 : 3; a.stride = d.stride; a.pad = d.kernel == CONV_PW ? 0 : 1; a.act = d.act; a.res_mode = d.res_mode;
-        a.k = a.kh * a.kw * a.in.c; a.kpad = (a.kh * a.kw * ((a.in.c + 31) / 32 * 32) + 31) / 32 * 32; a.m = batch * a.out.h * a.out.w; a.max_n = batch; a.prec = precision;
-        a.halo_bn = d.halo_bn;
-        if (d.up_c > 0) { a.up = view(d.up); a.up_c = d.up_c; }
-        ls.push_back(a); ks.push_back(d.kernel);
+        ls.push_back(conv_args_of_desc(layers[i], batch, precision));
+        ks.push_back(layers[i].kernel);
     }
     std::string why;
     MlPlanInfo info;
@@ -1496,6 +1495,20 @@ int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch
         ADAS_REQUIRE(items_cap >= info.n_items, ADAS_ERR_CAPACITY, "adas_debug_ml_plan: %d items, room for %d", info.n_items, items_cap);
         for (int k = 0; k < info.n_items; ++k) items[k] = info.item_words[k];
     }
+    return ADAS_OK;
+}
+
+int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precision, char* name, int name_cap) {
+    ADAS_REQUIRE(layer && batch > 0 && precision >= PREC_BF16 && precision <= PREC_X3 && name && name_cap > 0, ADAS_ERR_INVALID,
+                 "adas_debug_conv_route: bad argument");
+    ConvArgs a = conv_args_of_desc(*layer, batch, precision);
+    const ConvPlan pl = plan_conv(precision, a.kh, a.kw, a.stride, a.pad, a.max_n, a.res_mode, a.in, a.out);
+    a.kpad = pl.kpad;
+    // the second weight packing of the split precision, where the engine would allocate it when it loads the layer
+    if (precision == PREC_X3 && pl.kernel != CONV_PW && pl.kernel != CONV_FC &&
+        (halo8_x3_shape_ok(a.kh, a.kw, a.stride, a.pad, a.in, a.out) || halo_s2p_x3_shape_ok(a.kh, a.kw, a.stride, a.pad, a.res_mode, a.in, a.out)))
+        a.wgt_h8x3 = (const void*)(uintptr_t)0x1000;
+    snprintf(name, name_cap, "%s", conv_kernel_name(a));
     return ADAS_OK;
 }
 

@@ -51,7 +51,7 @@ struct ConvArgs {
     const void* wgt_h8x3 = nullptr;
 };
 
-// Which kernel runs a conv and how its weights are packed.  Decided once at load time from static
+// How a conv's weights are packed and which family of kernels reads that packing.  Decided once at load time from static
 // shapes and re-derived identically at launch time.
 enum { CONV_GATHER = 0, CONV_HALO = 1, CONV_FC = 2, CONV_STEM = 3, CONV_PW = 4, CONV_STEM2 = 5 /* second conv of a fused YOLO stem */,
        CONV_PAIR = 6 /* either conv of a fused 3x3 -> 3x3 pair (conv_pair.hip) */,
@@ -64,17 +64,26 @@ struct ConvPlan {
 };
 ConvPlan plan_conv(int prec, int kh, int kw, int stride, int pad, int max_n, int res_mode, const TView& in, const TView& out);
 
+// Which kernel runs one launch of a conv: THE statement of the order of choice.  launch_conv switches on it, conv_kernel_name labels it,
+// the multi-layer / grouped planners (conv_ml.hip) and the shortcut fold (engine.cpp) ask it.  A route is returned only if its launcher
+// takes the launch: the *_applicable predicates below are exact, a launcher that refuses what its predicate accepted is an error.
+enum class ConvRoute { IGEMM, PWG, HALO, HALO_RW, S2P, H8, PW, FC,          // 16-bit and fp32
+                       X3_FC, X3_PW, H8X3, S2D_X3, S2P_X3, X3,              // split precision (X3: conv_x3.hip picks ksplit | igemm itself)
+                       INVALID };                                          // no kernel computes what these arguments ask for
+ConvRoute conv_route(const ConvArgs& a);   // derives the plan from `a`; INVALID too when a.kpad is not the plan's (weights packed for another)
+
 // conv_halo_rw.hip: persistent, weights-resident variant of the stride-1 halo kernel for Cin <= 64 (same weight packing)
-bool halo_rw_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out);
+bool halo_rw_applicable(const ConvArgs& a);
 hipError_t launch_conv_halo_rw(const ConvArgs& a, hipStream_t st);
 // conv_halo_s2.hip: stride-2 3x3 for Cout % 128 == 0 (parity-plane LDS window, 8 waves, same weight packing)
-bool halo_s2p_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out);
+bool halo_s2p_applicable(const ConvArgs& a);
 hipError_t launch_conv_halo_s2p(const ConvArgs& a, hipStream_t st);
 // ... and its split-precision form on conv_halo8_x3's weight slabs (ConvArgs::wgt_h8x3): shape_ok decides the packing at load time
 bool halo_s2p_x3_shape_ok(int kh, int kw, int stride, int pad, int res_mode, const TView& in, const TView& out);
-bool halo_s2p_x3_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out);
-hipError_t launch_conv_s2p_x3(const ConvArgs& a, hipStream_t st);   // (takes the layer to conv_s2d_x3_kernel, the LDS-DMA form, where that applies)
-bool halo_s2d_x3_applicable(int kh, int kw, int stride, int pad, int res_mode, int n, const TView& in, const TView& out);
+bool halo_s2p_x3_applicable(const ConvArgs& a);
+hipError_t launch_conv_s2p_x3(const ConvArgs& a, hipStream_t st);
+bool s2d_x3_fits(const ConvArgs& a);   // of the layers halo_s2p_x3_applicable takes: those conv_s2d_x3_kernel, the LDS-DMA form, runs
+hipError_t launch_conv_s2d_x3(const ConvArgs& a, hipStream_t st);
 // conv_halo.hip's tile plan (strip-linear tiles of halo_bm(S) output pixels), shared with conv_halo8.hip
 struct HaloPlan {
     int SW, NS, TPS, WW, maxpix;   // strip width, strips per row, tiles per strip, window width, window pixels
@@ -87,9 +96,9 @@ bool plan_halo(int Ho, int Wo, int S, HaloPlan* out, int maxpix_cap = 0, int bm 
 bool plan_halo_sw(int Ho, int Wo, int S, int SW, int maxpix_cap, HaloPlan* out, int bm = 0);   // one given strip width
 int halo_tile_pixels(const ConvArgs& a);   // conv_halo.hip: the tile size launch_conv_halo picks for this launch (128 on small stride-1 layers)
 // conv_halo8.hip: stride-1 3x3 for Cout % 128 == 0, Cin % 32 == 0: persistent, LDS-DMA fed, counted waits (same weight packing)
-bool halo8_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& res, int res_mode);
+bool halo8_applicable(const ConvArgs& a);
 // the same conv with its projection shortcut (1x1 stride 2 on `x`, no activation) folded in
-bool halo8_ds_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& x);
+bool halo8_ds_applicable(const ConvArgs& a, const TView& x);   // a: the conv without ds_*
 hipError_t launch_pack_weights_ds(const float* src, void* dst, int cout, int cin, int prec, hipStream_t st);   // src fp32 [cout][cin]
 hipError_t launch_conv_halo8(const ConvArgs& a, hipStream_t st);
 // conv_pair.hip: conv A (x -> t) and conv B (t -> y [+ x]) in one launch, t never written: 3x3 s1 SiLU on 16 or 32 channels
@@ -115,7 +124,7 @@ hipError_t launch_conv_c2f16(const TView& x, const TView& out, const void* w_cv1
                              const float* b_b, const void* w_cv2, const float* b_cv2, int n, int prec, hipStream_t st);
 bool pw_applicable(int prec, int kh, int kw, int stride, int pad, int res_mode, const TView& in, const TView& out);  // conv_pw.hip
 // conv_pwg.hip: 1x1 stride-1 convs conv_pw does not take (Cin > 512), a K-looped MFMA GEMM on the generic [cout_pad][K] weight packing
-bool pwg_applicable(int prec, int kh, int kw, int stride, int pad, const TView& in, const TView& out, const TView& res, int res_mode);
+bool pwg_applicable(const ConvArgs& a);
 hipError_t launch_conv_pwg(const ConvArgs& a, hipStream_t st);
 const char* pwg_kernel_name(int m, int cout);
 // conv_x3.hip: the split precision's convolution (any kernel size / stride, channel counts multiples of 8) and its G8 weight packing
@@ -124,14 +133,14 @@ const char* conv_x3_kernel_name(const ConvArgs& a);
 hipError_t launch_pack_weights_x3(const float* src, void* dst, int cout, int cout_pad, int taps, int cin, int cin_pad, int kpad, hipStream_t st);
 // conv_halo8_x3.hip: stride-1 3x3, Cout % 64 == 0, Cin % 32 == 0, in the split precision: persistent, LDS-DMA fed, half-chunk stream
 bool halo8_x3_shape_ok(int kh, int kw, int stride, int pad, const TView& in, const TView& out);   // static: gets the second weight packing
-bool halo8_x3_applicable(int kh, int kw, int stride, int pad, int n, const TView& in, const TView& out, const TView& res, int res_mode);
+bool halo8_x3_applicable(const ConvArgs& a);
 size_t halo8_x3_weight_bytes(int cout, int cin);
 hipError_t launch_pack_weights_h8x3(const float* src, void* dst, int cout, int cin, hipStream_t st);   // src fp32 [cout][9][cin]
 hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st);
-// returns hipSuccess or the launch error.  prec: PREC_*.
-hipError_t launch_conv(const ConvArgs& a, int prec, hipStream_t st);
-const char* conv_tile_name(const ConvArgs& a, int prec);
-const char* conv_kernel_name(const ConvArgs& a, int prec, int kernel);
+// returns hipSuccess or the launch error
+hipError_t launch_conv(const ConvArgs& a, hipStream_t st);
+// the kernel instantiation conv_route(a) stands for; stem: the layer is the engine's fused first layer (CONV_STEM), which has no route
+const char* conv_kernel_name(const ConvArgs& a, bool stem = false);
 
 hipError_t launch_input_nchw(const float* nchw, TView out, int n, int c_true, int prec, hipStream_t st);
 hipError_t launch_maxpool(TView in, TView out, int n, int k, int s, int p, int prec, hipStream_t st);
