@@ -150,6 +150,24 @@ int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch
  * adas_engine_layer_kernel gives the layer in an engine whose max_batch is `batch` (no device: tests/test_conv_route_cpu.py).  `kernel`
  * only tells 1x1 (4) from 3x3 (any other value); the kernel class comes from the plan. */
 int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precision, char* name, int name_cap);
+/* The load-time plan of an engine: what adas_engine_create decided before it touched a weight.  One row of ADAS_PLAN_COLS int64 per
+ * layer (rows[layer * ADAS_PLAN_COLS + column]); a link column holds a layer index or -1, an offset column bytes into the weight arena:
+ *    0 kernel (weight packing, CONV_* of csrc/kernels.h)   1 skip (launches nothing: fused into a neighbour)
+ *    2 fuse_pool   3 fuse_conv2 (stem: the max-pool / second conv in its launch)
+ *    4 ds_src   5 ds_user (3x3 conv <-> the 1x1 stride-2 projection shortcut it can carry)
+ *    6 up_src (1x1 conv: the upsample folded into its loads)   7..8 pool3 (max-pool: the two pools chained into its launch)
+ *    9 pair_b (first conv of a 3x3 pair: the second)   10..12 c2f (cv1 of a fused C2f block: conv A, conv B, cv2)
+ *   13..18 det_src (Detect: the 1x1 convs folded into the decode)   19 halo_bn   20 has_x3h8 (second fp16x3 packing)
+ *   21 k   22 kpad   23 cin_pad   24 cout_pad (0 for layers without packed conv weights)
+ *   25 w_off   26 b_off   27 ds_w_off   28 x3h8_w_off
+ * adas_engine_plan reads a live engine.  adas_debug_engine_plan needs no device: `tables` are the first `weights_off` bytes of a model
+ * container (header and the three tables), which it reads, validates and plans exactly as adas_engine_create does -- the same error codes
+ * and texts for a container that is refused -- without touching a weight (tests/test_engine_plan_cpu.py).  `rows` may be NULL to ask for
+ * n_ops alone; ADAS_ERR_CAPACITY when rows_cap (in rows) is too small. */
+#define ADAS_PLAN_COLS 29
+int adas_engine_plan(const adas_engine* e, int64_t* rows, int rows_cap, int32_t* n_ops, uint64_t* weight_bytes);
+int adas_debug_engine_plan(const void* tables, size_t bytes, int precision, int max_batch, int64_t* rows, int rows_cap, int32_t* n_ops,
+                           uint64_t* weight_bytes);
 /* Debug/parity tap: copy an intermediate activation (by layer index) to the host as NCHW fp32. */
 int adas_engine_fetch_activation(adas_engine* e, int layer, int batch, float* h_out_nchw, int64_t dims[4]);
 

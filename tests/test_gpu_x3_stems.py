@@ -10,7 +10,7 @@ operation and each with the kernel label that proves which kernel ran.
 - layernorm_kernel<T> (aux_kernels.hip) in all four precisions: rows far from zero (offset 100, spread ~1), lengths below one
   workgroup's 256 threads, ragged, CULane's 4,000 and above 8,192.
 
-ADAS_NO_STEM and ADAS_NO_STEM_POOL_X3 are read at every engine creation (engine.cpp) and are toggled here; ADAS_NO_STEM2_X3 and
+ADAS_NO_STEM and ADAS_NO_STEM_POOL_X3 are read at every engine creation (engine_load.cpp, fuse_stem) and are toggled here; ADAS_NO_STEM2_X3 and
 ADAS_STEMP_X3_WGS are read once per process and are not.
 """
 import importlib

@@ -153,7 +153,7 @@ def test_shuffle_ref_is_torch_channel_shuffle(C, g):
 
 @pytest.mark.parametrize("hw", [(13, 37), (3, 5), (1, 9), (20, 20), (49, 63)], ids=str)
 def test_spp_identity_under_minus_inf_padding(hw):
-    """engine.cpp runs SPP's 5 / 9 / 13 pools as the SPPF chain: 9x9 = 5x5 of 5x5, 13x13 = 5x5 of 5x5 of 5x5 under -inf padding, on ragged
+    """engine_load.cpp (fuse_pool_chains) runs SPP's 5 / 9 / 13 pools as the SPPF chain: 9x9 = 5x5 of 5x5, 13x13 = 5x5 of 5x5 of 5x5 under -inf padding, on ragged
     maps and on maps smaller than the window."""
     x = np.random.default_rng(1).standard_normal((2, 8) + hw) - 2.0
     p5 = R.maxpool_ref(x, 5, 1, 2)

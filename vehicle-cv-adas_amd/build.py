@@ -43,6 +43,7 @@ UNITS = [
     ("dw_attn.hip", []),
     ("fuse_ops.hip", []),
     ("engine.cpp", []),
+    ("engine_load.cpp", []),
     ("pipeline.cpp", []),
 ]
 EXTRA = os.environ.get("ADAS_CFLAGS", "").split()   # scratch builds only (e.g. -DADAS_HALO_PROF)

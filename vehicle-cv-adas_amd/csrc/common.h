@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/adas_hip.h"
 
 namespace adas {
@@ -10,6 +11,10 @@ void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // Parameters that a captured pipeline step bakes into its kernel arguments (post / decode / geometry configuration) carry a
 // process-wide generation: every setter bumps it, adas_pipeline_* re-captures when it moved since the capture.
+inline bool env_on(const char* name) {   // an environment switch: set to 1 (ADAS_NO_STEM=1)
+    const char* v = getenv(name);
+    return v && v[0] == '1';
+}
 unsigned long long config_generation();
 void bump_config_generation();
 }  // namespace adas

@@ -350,7 +350,7 @@ static bool c2f_x3_enabled() {   // ADAS_NO_C2F_X3=1: the block runs as its four
     return v == 1;
 }
 
-// the Bottleneck pair of such a block (engine.cpp's pair pass runs first and the C2f pass builds on its result): split precision, 16 channels;
+// the Bottleneck pair of such a block (engine_load.cpp's pair pass runs first and the C2f pass builds on its result): split precision, 16 channels;
 // a pair the C2f pass does not absorb is released again -- there is no stand-alone pair kernel in this precision
 bool pair_x3_candidate(int prec, int kh, int kw, int stride, int pad, int act, int res_mode, const TView& x, const TView& t, int kh2, int kw2, int stride2,
                        int pad2, int act2, int res_mode2, const TView& y) {

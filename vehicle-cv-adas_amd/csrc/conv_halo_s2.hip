@@ -938,7 +938,7 @@ static bool s2x_enabled() {
     return v == 1;
 }
 
-// static part (shapes): the conv also gets conv_halo8_x3's weight packing (engine.cpp)
+// static part (shapes): the conv also gets conv_halo8_x3's weight packing (engine_load.cpp, wants_x3h8_packing)
 bool halo_s2p_x3_shape_ok(int kh, int kw, int stride, int pad, int res_mode, const TView& in, const TView& out) {
     if (!s2x_enabled() || stride != 2 || kh != 3 || kw != 3 || pad != 1 || res_mode != RES_NONE) return false;
     if (in.f32 || out.f32 || out.h != (in.h + 2 - 3) / 2 + 1 || out.w != (in.w + 2 - 3) / 2 + 1) return false;

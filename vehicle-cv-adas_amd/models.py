@@ -133,6 +133,13 @@ class DictWeights:
         return a
 
 
+class ZeroWeights:
+    """All-zero parameters: a graph's tables (shapes, links, blob offsets) without drawing a single random number."""
+
+    def __call__(self, name, shape, kind, fill=None):
+        return np.zeros(shape, np.float32)
+
+
 class Graph:
     def __init__(self, name, in_c, in_h, in_w, wsrc):
         self.name, self.in_c, self.in_h, self.in_w = name, in_c, in_h, in_w
@@ -361,7 +368,8 @@ class Graph:
         self.outs.append((view.buf, int(offset), list(dims), name))
 
     # ---- serialisation
-    def tobytes(self):
+    def tables(self):
+        """Header, buffer, operator and output tables, padded to the weight blob's offset: all the engine needs to plan the graph."""
         parts = []
         nb, no, nout = len(self.bufs), len(self.ops), len(self.outs)
         woff = HDR_SIZE + nb * BUF_SIZE + no * OP_SIZE + nout * OUT_SIZE
@@ -386,8 +394,10 @@ class Graph:
             d = (list(dims) + [1] * 4)[:4]
             parts.append(struct.pack(OUT_FMT, buf, off, len(dims), *d, name.encode()[:31]))
         head = b"".join(parts)
-        head += b"\0" * (woff - len(head))
-        return head + bytes(self.blob)
+        return head + b"\0" * (woff - len(head))
+
+    def tobytes(self):
+        return self.tables() + bytes(self.blob)
 
     def save(self, path):
         with open(path, "wb") as f:
