@@ -99,7 +99,9 @@ int adas_engine_infer_device_packed(adas_engine* e, const uint16_t* d_input_nhwc
 const float* adas_engine_output_device(const adas_engine* e, int index);
 /* Algorithmic work of one frame: 2*MACs over conv+linear layers and weight bytes. */
 int adas_engine_stats(const adas_engine* e, double* flops_per_frame, double* weight_bytes, int* num_layers);
-/* Per-layer device timing of the last adas_engine_profile() call (hipEvents on the engine stream). */
+/* Per-layer device timing: `iters` forwards with one hipEvent behind every launch of the schedule (the null stream).  A launch's time,
+ * less the cost of the marker itself, goes to the layer that carries its label (adas_engine_layer_kernel); a layer that rides in another
+ * layer's launch, or that nothing computes, reads exactly 0. */
 int adas_engine_profile(adas_engine* e, const float* d_input_nchw, int batch, int iters, float* ms_per_layer,
                         int max_layers, int* num_layers);
 /* Pipeline-internal fast path of a v8-layout detector whose Detect head runs as the fused kernel (16-bit precisions): while a sink is
@@ -115,14 +117,21 @@ int adas_engine_set_detect_sink(adas_engine* e, float* d_best_conf, int32_t* d_b
 int adas_engine_layer_info(const adas_engine* e, int layer, char* name, int name_cap, double* flops, int* kind);
 /* Which kernel instantiation layer `layer` launches at `batch` frames (matches the rocprofv3 kernel name). */
 int adas_engine_layer_kernel(const adas_engine* e, int layer, int batch, char* name, int name_cap);
-/* Multi-layer launches (csrc/conv_ml.hip, round 5; OPT-IN: engines created with ADAS_ML=1 in the environment -- at 64 frames the
- * per-layer launches measured faster): at a given batch size, maximal runs of consecutive convolution layers that the
- * per-layer kernels conv_halo / conv_pw would take (the 40x40 / 20x20 layers of the YOLO graphs, the Detect branches) run as ONE
- * persistent launch each -- a table of (layer, tile, channel block) items behind per-layer, per-frame arrival counters -- with results
- * bit-identical to the per-layer launches.  adas_engine_prepare builds the device tables of a batch size
- * (adas_engine_infer_* and adas_pipeline_* call it themselves outside stream captures); adas_engine_ml_info reports what it decided;
- * adas_engine_ml_status synchronises and returns ADAS_ERR_HIP when a dependency wait of the last launch timed out (every wait is
- * bounded: a launch can fail, never hang); adas_engine_launch_count = kernel launches of one forward at that batch. */
+/* The launch schedule.  What one forward launches depends on the batch size (the kernel a conv resolves to does), so the engine decides
+ * it once per batch size: which layers launch on their own, which ride in another layer's launch (the load-time fusions, a projection
+ * shortcut folded at this batch), and which layers share a launch.  16-bit engines share launches in one of two ways, chosen by the
+ * environment when the engine is created:
+ *   grouped (the default; ADAS_NO_GROUP=1 keeps every layer its own launch): a run of consecutive 3x3 convs is launched level by
+ *     dependency level, the independent layers of a level (at most 8) as ONE plain launch -- bit-identical to the per-layer launches;
+ *   multi-layer (csrc/conv_ml.hip; OPT-IN, ADAS_ML=1 -- at 64 frames the per-layer launches measured faster): maximal runs
+ *     of consecutive convolution layers that conv_halo / conv_pw would take run as ONE persistent launch each -- a table of (layer,
+ *     tile, channel block) items behind per-layer, per-frame arrival counters -- bit-identical to the per-layer launches too.
+ * adas_engine_prepare decides the schedule of a batch size and builds its device tables (adas_engine_create does it for max_batch;
+ * adas_engine_infer_* and adas_pipeline_* call it themselves, outside stream captures; at most 16 batch sizes get shared launches, later
+ * ones one launch per layer).  At a batch size nothing was prepared for, a forward inside a stream capture and the queries below use the
+ * plain schedule (no shared launches).  adas_engine_launch_count = launches of one forward = steps of the schedule;
+ * adas_engine_ml_info reports the multi-layer launches; adas_engine_ml_status synchronises and returns ADAS_ERR_HIP when a dependency
+ * wait of the last launch timed out (every wait is bounded: a launch can fail, never hang). */
 int adas_engine_prepare(adas_engine* e, int batch);
 int adas_engine_ml_info(const adas_engine* e, int batch, int32_t* n_launches, int32_t* n_layers, int32_t* n_items);
 int adas_engine_ml_status(const adas_engine* e, int batch, uint32_t* error_word);
@@ -168,7 +177,25 @@ int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precis
 int adas_engine_plan(const adas_engine* e, int64_t* rows, int rows_cap, int32_t* n_ops, uint64_t* weight_bytes);
 int adas_debug_engine_plan(const void* tables, size_t bytes, int precision, int max_batch, int64_t* rows, int rows_cap, int32_t* n_ops,
                            uint64_t* weight_bytes);
-/* Debug/parity tap: copy an intermediate activation (by layer index) to the host as NCHW fp32. */
+/* The schedule of one batch size, layer by layer: step_of[layer] = the launch (0 .. n_steps - 1, in launch order) that computes the
+ * layer, or -1 where nothing does; role[layer] = what the layer is to the forward:
+ *    0 launches on its own                                 1 / 2 leads / rides in a grouped launch
+ *    3 / 4 leads / rides in a multi-layer launch           5 projection shortcut computed inside the conv that adds it
+ *    6 upsample folded into its consumer's loads           7 second / third pool of the SPPF pool launch
+ *    8 / 9 / 10 fused C2f block: cv1 (launches it), the Bottleneck's convs (stay in LDS), cv2 (materialised)
+ *   11 / 12 3x3 pair: first conv (launches it, stays in LDS), second conv
+ *   13 1x1 conv computed inside the Detect launch          14 / 15 / 16 fused stem: the conv (launches it), the input conversion, the pool / second conv
+ * A launch's first layer by role (0, 1, 3, 8, 11, 14) carries its label and its profiled time.  adas_engine_schedule reads a live engine
+ * (the prepared schedule, else the plain one).  adas_debug_engine_schedule needs no device: it reads, validates and plans `tables` as
+ * adas_debug_engine_plan does, decides the schedule with the mode the environment selects (ADAS_ML, ADAS_NO_GROUP) and also writes the
+ * labels adas_engine_layer_kernel would give (labels[layer * ADAS_LABEL_CAP], may be NULL) -- tests/test_engine_schedule_cpu.py.  All
+ * arrays may be NULL to ask for the counts alone; ADAS_ERR_CAPACITY when cap (in layers) is too small. */
+#define ADAS_LABEL_CAP 96
+int adas_engine_schedule(const adas_engine* e, int batch, int32_t* step_of, int32_t* role, int cap, int32_t* n_ops, int32_t* n_steps);
+int adas_debug_engine_schedule(const void* tables, size_t bytes, int precision, int max_batch, int batch, int32_t* step_of, int32_t* role,
+                               char* labels, int cap, int32_t* n_ops, int32_t* n_steps);
+/* Debug/parity tap: copy an intermediate activation (by layer index) to the host as NCHW fp32.  ADAS_ERR_INVALID for a layer whose
+ * role (above) leaves it no activation in memory: 5, 6, 8, 9, 11, 13, 14, 15. */
 int adas_engine_fetch_activation(adas_engine* e, int layer, int batch, float* h_out_nchw, int64_t dims[4]);
 
 /* ===================================================================================

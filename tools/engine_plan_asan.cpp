@@ -1,6 +1,6 @@
-// engine_plan_asan.cpp -- csrc/engine_load.cpp's read / validate / plan path under AddressSanitizer + UBSan, on the CPU, as a stand-alone
-// program: it is linked from engine_load.cpp compiled with the sanitizers (so the sanitizer runtime is the program's own) against
-// libadas_hip.so for the kernels' predicates, and plans every table file it is given.  No device is touched.  tools/engine_plan_asan.py
+// engine_plan_asan.cpp -- csrc/engine_load.cpp's read / validate / plan path and csrc/engine_schedule.cpp's plan_schedule under
+// AddressSanitizer + UBSan, on the CPU, as a stand-alone program: it is linked from those two files compiled with the sanitizers (so the sanitizer runtime is the program's own) against
+// libadas_hip.so for the kernels' predicates, and plans and schedules every table file it is given.  No device is touched.  tools/engine_plan_asan.py
 // builds it, writes the tables of three shipped graphs and the damaged tables of tests/test_engine_plan_cpu.py, and runs it.
 //   engine_plan_asan <file>.<precision>.tables ...     (precision: ADAS_PREC_* as a number; max_batch 64 and 1 each)
 // Exit status 0: every file was planned or refused with an error code; a sanitizer report ends the program with its own status.
@@ -11,7 +11,7 @@
 #include <vector>
 
 int main(int argc, char** argv) {
-    int planned = 0, refused = 0;
+    int planned = 0, refused = 0, scheduled = 0;
     for (int i = 1; i < argc; ++i) {
         FILE* f = fopen(argv[i], "rb");
         if (!f) { fprintf(stderr, "%s: cannot open\n", argv[i]); return 2; }
@@ -33,12 +33,21 @@ int main(int argc, char** argv) {
                 std::vector<int64_t> rows((size_t)n_ops * ADAS_PLAN_COLS);
                 rc = adas_debug_engine_plan(tables, in.size(), prec, max_batch, rows.data(), n_ops, &n_ops, &weight_bytes);
             }
+            // the launch schedule of the same tables (csrc/engine_schedule.cpp), at the engine's own batch size and at one frame
+            for (int batch : {max_batch, 1}) {
+                if (rc != ADAS_OK) break;
+                int32_t n_steps = 0;
+                std::vector<int32_t> step_of(n_ops), role(n_ops);
+                std::vector<char> labels((size_t)n_ops * ADAS_LABEL_CAP);
+                rc = adas_debug_engine_schedule(tables, in.size(), prec, max_batch, batch, step_of.data(), role.data(), labels.data(), n_ops, &n_ops, &n_steps);
+                if (rc == ADAS_OK) ++scheduled;
+            }
             if (rc == ADAS_OK) ++planned;
             else if (rc == ADAS_ERR_FORMAT) ++refused;
             else { fprintf(stderr, "%s: error %d: %s\n", argv[i], rc, adas_last_error()); free(tables); return 3; }
         }
         free(tables);
     }
-    printf("engine_plan_asan: %d planned, %d refused, no sanitizer report\n", planned, refused);
+    printf("engine_plan_asan: %d planned, %d schedules, %d refused, no sanitizer report\n", planned, scheduled, refused);
     return 0;
 }

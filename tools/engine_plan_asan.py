@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Host-code hygiene of the loader: csrc/engine_load.cpp's read / validate / plan path under AddressSanitizer + UBSan on the CPU.
+"""Host-code hygiene of the loader and the scheduler: csrc/engine_load.cpp's read / validate / plan path and csrc/engine_schedule.cpp's
+plan_schedule under AddressSanitizer + UBSan on the CPU.
 
     python tools/engine_plan_asan.py
 
-Builds tools/engine_plan_asan.cpp + csrc/engine_load.cpp with -fsanitize=address,undefined (host side only) into a stand-alone program in
+Builds tools/engine_plan_asan.cpp + csrc/engine_load.cpp + csrc/engine_schedule.cpp with -fsanitize=address,undefined (host side only) into a stand-alone program in
 vehicle-cv-adas_amd/_scratch/, linked against the product library for the kernels' predicates; writes the tables of three shipped graphs
 (four precisions each) and every damaged table of tests/test_engine_plan_cpu.py to files; runs the program on them.  No device is used, and
 nothing is loaded into python under a sanitizer.  The product library must be built (vehicle-cv-adas_amd/build.py)."""
@@ -26,6 +27,7 @@ def main():
     san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer"]
     subprocess.check_call([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-x", "hip", *san,
                            os.path.join(ROOT, "tools", "engine_plan_asan.cpp"), os.path.join(PKG, "csrc", "engine_load.cpp"),
+                           os.path.join(PKG, "csrc", "engine_schedule.cpp"),
                            "-L" + PKG, "-ladas_hip", "-Wl,-rpath," + PKG, "-o", exe])
     import test_engine_plan_cpu as T
     with tempfile.TemporaryDirectory() as tmp:

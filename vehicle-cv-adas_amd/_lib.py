@@ -138,6 +138,9 @@ _SIGS = {
     "adas_debug_conv_route": (C.c_int, [C.POINTER(MlLayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "adas_engine_plan": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "adas_debug_engine_plan": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "adas_engine_schedule": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "adas_debug_engine_schedule": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p,
+                                             C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "adas_engine_model_io_half": (C.c_int, [_P]),
     "adas_engine_infer_device_packed": (C.c_int, [_P, _P, C.c_int, _P]),
     "adas_engine_output_device": (_P, [_P, C.c_int]),

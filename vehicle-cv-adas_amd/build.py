@@ -43,6 +43,7 @@ UNITS = [
     ("dw_attn.hip", []),
     ("fuse_ops.hip", []),
     ("engine.cpp", []),
+    ("engine_schedule.cpp", []),
     ("engine_load.cpp", []),
     ("pipeline.cpp", []),
 ]

@@ -234,6 +234,16 @@ class HipEngine(EngineBase):
     def launch_count(self, batch=1):
         return int(L.lib().adas_engine_launch_count(self._h, int(batch)))
 
+    def schedule(self, batch=1):
+        """(step_of, role, n_steps) of one forward at `batch` frames (include/adas_hip.h adas_engine_schedule): per layer the launch that
+        computes it (-1: none) and its role."""
+        n = self.stats()["num_layers"]
+        step_of, role = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        n_ops, n_steps = C.c_int32(), C.c_int32()
+        i32 = C.POINTER(C.c_int32)
+        L.check(L.lib().adas_engine_schedule(self._h, int(batch), step_of.ctypes.data_as(i32), role.ctypes.data_as(i32), n, C.byref(n_ops), C.byref(n_steps)))
+        return step_of, role, n_steps.value
+
     def layer_index(self, name):
         for i in range(self.stats()["num_layers"]):
             if self.layer_info(i)[0] == name:

@@ -1,4 +1,4 @@
-// engine.h -- in-memory form of a loaded ADASHIP1 model (shared by engine_load.cpp, engine.cpp and pipeline.cpp).
+// engine.h -- in-memory form of a loaded ADASHIP1 model (shared by engine_load.cpp, engine_schedule.cpp, engine.cpp and pipeline.cpp).
 // File structs mirror the struct formats in vehicle-cv-adas_amd/models.py (little-endian, naturally aligned).
 #pragma once
 #include "common.h"
@@ -77,24 +77,42 @@ struct EngOp {
     int det_src[6] = {-1, -1, -1, -1, -1, -1};  // OP_DETECT_V8: the six 1x1 convs (cv2.i.2, cv3.i.2) folded into the decode launch, or -1;
                                                 // OP_DETECT_V5: the three per-level 1x1 convs (det_src[0..2])
 };
-// One multi-layer launch (conv_ml.hip): the non-skipped ops of [first, last] are all convs with a tile body there and run as ONE launch at
-// `first`'s position; decided per batch size (the kernels a layer resolves to, and with them its eligibility, depend on the batch).
-struct MlSeg {
-    int first = 0, last = 0, n_layers = 0, n_items = 0;
-    MlPlan* plan = nullptr;
-    std::vector<int> ops;     // the member ops, in launch order
+// What a layer is to one forward at a given batch size: the one classification the launch loop, the labels (adas_engine_layer_kernel),
+// the profiler and adas_engine_fetch_activation read (include/adas_hip.h documents the values: ADAS_ROLE_*).
+enum LayerRole {
+    ROLE_OWN = 0,          // launches on its own kernel, its output materialised
+    ROLE_GROUP_LEAD, ROLE_GROUP_MEMBER,   // first / further layer of a grouped launch of independent 3x3 convs
+    ROLE_ML_LEAD, ROLE_ML_MEMBER,         // first / further layer of a multi-layer launch
+    ROLE_IN_SHORTCUT_USER, // a projection shortcut computed inside the conv that adds it (at this batch)
+    ROLE_IN_CONSUMER_LOADS,// an upsample folded into its consumer's loads: nobody computes it
+    ROLE_IN_POOL3,         // second / third max-pool of the SPPF pool launch
+    ROLE_C2F_LEAD, ROLE_C2F_HIDDEN, ROLE_C2F_TAIL,   // cv1 (launches the block), the Bottleneck's convs (stay in LDS), cv2 (materialised)
+    ROLE_PAIR_FIRST, ROLE_IN_PAIR,        // first conv of a 3x3 pair (launches it, its output stays in LDS), the second
+    ROLE_IN_DETECT,        // a 1x1 conv computed inside the Detect launch
+    ROLE_STEM_LEAD, ROLE_STEM_INPUT, ROLE_STEM_TAIL, // the stem conv with a pool / second conv in its launch, the input conversion, that pool / conv
+    ROLE_COUNT
 };
-// A run of consecutive 3x3 halo convs re-ordered by dependency level, the layers of a level launched together (conv_ml.hip grouped launch:
-// independent layers, no synchronisation inside the launch).  Decided per batch size like the multi-layer launches.
-struct GroupStep {
-    MlGroup* group = nullptr;    // >= 2 independent layers in one launch, or
-    int op = -1;                 // one layer on its own kernel
-    std::vector<int> members;
+// does a layer of this role start a launch (the others ride in one, or are never computed)?
+inline bool role_launches(int r) {
+    return r == ROLE_OWN || r == ROLE_GROUP_LEAD || r == ROLE_ML_LEAD || r == ROLE_C2F_LEAD || r == ROLE_PAIR_FIRST || r == ROLE_STEM_LEAD;
+}
+// One launch of a forward.  OP: layer `lead` on its own kernel, with whatever the load-time plan fused into it.  GROUP: independent 3x3
+// halo convs of one dependency level of a run of consecutive layers as one plain launch.  ML: a run of convs as one persistent launch
+// (opt-in, ADAS_ML=1).  The kernels a layer resolves to depend on the batch, so a schedule holds for one batch size.
+struct Step {
+    enum Kind { OP, GROUP, ML } kind = OP;
+    int lead = -1;               // the layer that carries the label and the time
+    std::vector<int> members;    // layers computed by this launch, lead first
+    int run = -1;                // GROUP, and OP steps between them: the run of consecutive layers the step belongs to
+    MlGroup* group = nullptr;    // GROUP: device table (upload_schedule)
+    MlPlan* plan = nullptr;      // ML: device tables (upload_schedule)
+    bool folds_shortcut = false; // OP: the conv takes its projection shortcut into its launch at this batch
+    int ml_items = 0;            // ML: work items of the launch
 };
-struct GroupRun {
-    int first = 0, last = 0;
-    std::vector<GroupStep> steps;
-    std::vector<int> ops;
+struct Schedule {
+    std::vector<Step> steps;         // in launch order
+    std::vector<int> step_of;        // per layer: the step that computes it, or -1 (nothing does)
+    std::vector<uint8_t> role;       // per layer: LayerRole
 };
 struct EngOut {
     uint32_t buf, offset, ndim, dims[4];
@@ -103,9 +121,8 @@ struct EngOut {
 };
 
 // packed_in: d_in is the (c0,c1,c2,0) bf16 NHWC tensor of adas_preprocess_*_packed (fused first layer only)
-int engine_run_op(struct ::adas_engine* e, int i, const float* d_in, int batch, hipStream_t st, bool packed_in = false);
 int engine_forward(struct ::adas_engine* e, const float* d_in, int batch, hipStream_t st, bool packed_in = false);
-int engine_prepare(struct ::adas_engine* e, int batch);   // multi-layer launch tables of this batch size (never inside a stream capture)
+int engine_prepare(struct ::adas_engine* e, int batch);   // the schedule of this batch size and its device tables (never inside a stream capture)
 
 }  // namespace adas
 
@@ -119,13 +136,12 @@ struct adas_engine {
     void* d_weights = nullptr;
     float* d_input = nullptr;
     size_t weight_bytes = 0, act_bytes = 0;
-    std::vector<hipEvent_t> events;
-    std::vector<hipEvent_t> step_events;   // adas_engine_profile: one per step of a grouped run
+    std::vector<hipEvent_t> events;   // adas_engine_profile: one ahead of the first step and one behind every step
     hipStream_t last = 0;
-    std::map<int, std::vector<adas::MlSeg>> ml;   // batch -> multi-layer launches (adas_engine_prepare); absent: not prepared, per-layer launches
-    std::map<int, std::vector<adas::GroupRun>> groups;   // batch -> grouped launches of independent layers (default path)
-    bool group_on = false;                         // ADAS_NO_GROUP=1 at creation keeps every layer its own launch
-    bool ml_on = false;                            // multi-layer launches enabled for this engine (read from the environment at creation)
+    // how layers share launches, read from the environment at creation: ML (ADAS_ML=1, opt-in), else GROUPED (the default of the 16-bit
+    // precisions; ADAS_NO_GROUP=1 keeps every layer its own launch), else PLAIN
+    enum Mode { PLAIN, GROUPED, ML } mode = PLAIN;
+    std::map<int, adas::Schedule> schedules;       // batch -> what a forward launches (engine_prepare); absent: the plain schedule, decided on the spot
     std::vector<char> buf_aliased;                 // buffer takes part in an alias (Graph.alias): stays out of multi-layer launches
     float* sink_conf = nullptr;   // adas_engine_set_detect_sink: the fused v8 Detect writes per-anchor (best probability, class) here
     int* sink_cls = nullptr;      // instead of the head's class rows (pipeline steps)
@@ -148,7 +164,45 @@ inline TView make_view(const adas_engine* e, int buf, int coff, int c) {
     return v;
 }
 
+inline TView in_view(const adas_engine* e, const FileOp& o, int k = 0) { return make_view(e, o.in_buf[k], o.in_coff[k], o.in_c[k]); }
+inline TView out_view(const adas_engine* e, const FileOp& o) { return make_view(e, o.out_buf, o.out_coff, o.out_c); }
+
+// While a container is validated and planned (and a schedule decided without a device) its buffers and weights have no memory.  The
+// predicates only ever compare a view's pointer ("same buffer?") or ask whether a weight pointer is set, so each buffer stands in with an
+// identity of its own, an alias with its target's, the weight arena with one more; they are gone again before anything can take them for
+// device memory (free_engine).
+struct Placeholders {
+    adas_engine* e;
+    bool weights;
+    explicit Placeholders(adas_engine* e_) : e(e_), weights(!e_->d_weights) {
+        for (size_t bi = 0; bi < e->bufs.size(); ++bi) e->bufs[bi].d = (void*)(uintptr_t)((bi + 1) << 12);
+        for (auto& b : e->bufs)
+            if (b.alias_of >= 0) b.d = e->bufs[b.alias_of].d;
+        if (weights) e->d_weights = (void*)(uintptr_t)((e->bufs.size() + 1) << 12);
+    }
+    ~Placeholders() {
+        for (auto& b : e->bufs) b.d = nullptr;
+        if (weights) e->d_weights = nullptr;
+    }
+};
+
 int free_engine(::adas_engine* e);   // engine.cpp: everything the engine owns on the device, then the engine
+
+// ---- engine_schedule.cpp: what one forward at `batch` frames launches.  plan_schedule decides (no HIP call: it also runs on an engine
+// under Placeholders); fused_launches = false gives the plain schedule, one OP step per launching layer, whatever the engine's mode.
+// upload_schedule creates the device tables of the GROUP / ML steps (allocations and copies: never inside a stream capture).
+ConvArgs conv_args_of(const adas_engine* e, int i, int batch);        // a plain OP_CONV at this batch, without its folded shortcut
+void attach_shortcut(const adas_engine* e, int i, ConvArgs* a);      // ... the projection's arguments added (Step::folds_shortcut)
+Schedule plan_schedule(const adas_engine* e, int batch, bool fused_launches);
+void upload_schedule(const adas_engine* e, int batch, Schedule* s);
+void free_schedule(Schedule* s);
+// the schedule a forward at `batch` runs: the prepared one, or -- nothing prepared: a const query, a forward inside a stream capture --
+// the plain one, decided on the spot into *local
+const Schedule& schedule_at(const adas_engine* e, int batch, Schedule* local);
+void layer_label(const adas_engine* e, const Schedule& s, int layer, int batch, char* name, int cap);   // adas_engine_layer_kernel's string
+// adas_engine_schedule's outputs for a decided schedule; labels: n_ops x ADAS_LABEL_CAP bytes, or NULL
+int write_schedule_rows(const adas_engine* e, const Schedule& s, int batch, int32_t* step_of, int32_t* role, char* labels, int cap, int32_t* n_ops,
+                        int32_t* n_steps);
 // engine_load.cpp: does a conv the plan put on `kernel` also get the second fp16x3 packing (conv_halo8_x3.hip), the batch choosing at launch?
 bool wants_x3h8_packing(int precision, int kernel, int kh, int kw, int stride, int pad, int res_mode, const TView& in, const TView& out);
 

@@ -3,7 +3,7 @@
 //   validate_container   every refusal of a container, before a byte of device memory is asked for
 //   plan_engine          the fusion passes and the weight arena's layout: no HIP call, a pure function of (tables, precision, max_batch,
 //                        ADAS_NO_* switches) -- adas_debug_engine_plan runs the first three phases without a device
-//   allocate_and_upload  activation buffers, the weight arena, weights packed on the device, the launch tables of max_batch
+//   allocate_and_upload  activation buffers, the weight arena, weights packed on the device, the launch schedule of max_batch
 // Memory plan: every graph buffer gets its own HBM allocation sized for max_batch frames (the nets are tiny against 288 GB); weights are
 // packed once on the device into the compute type with K padded to 32 and Cout to 128 so the conv kernel needs no bounds checks on the
 // weight side.
@@ -54,21 +54,6 @@ struct Source {
 struct EngineFree { void operator()(adas_engine* e) const { free_engine(e); } };
 using EnginePtr = std::unique_ptr<adas_engine, EngineFree>;   // the engine under construction: freed unless it is released to the caller
 
-// While a container is validated and planned its buffers have no memory yet.  The predicates only ever compare a view's pointer ("same
-// buffer?"), so each buffer stands in with an identity of its own, an alias with its target's; they are gone again before anything can
-// take them for device memory (free_engine).
-struct Placeholders {
-    adas_engine* e;
-    explicit Placeholders(adas_engine* e_) : e(e_) {
-        for (size_t bi = 0; bi < e->bufs.size(); ++bi) e->bufs[bi].d = (void*)(uintptr_t)((bi + 1) << 12);
-        for (auto& b : e->bufs)
-            if (b.alias_of >= 0) b.d = e->bufs[b.alias_of].d;
-    }
-    ~Placeholders() { for (auto& b : e->bufs) b.d = nullptr; }
-};
-
-TView in_view(const adas_engine* e, const FileOp& o, int k = 0) { return make_view(e, o.in_buf[k], o.in_coff[k], o.in_c[k]); }
-TView out_view(const adas_engine* e, const FileOp& o) { return make_view(e, o.out_buf, o.out_coff, o.out_c); }
 std::string fixed_name(const char* s, size_t cap) { return std::string(s, strnlen(s, cap)); }
 
 // ---- phase 1: header, magic, tables.  `on_device`: the engine will run, so a device must be visible (asked after the magic check)
@@ -82,8 +67,7 @@ int read_container(Source& src, const char* label, bool on_device, int precision
     e->prec = precision;
     e->max_batch = max_batch;
     // multi-layer launches are opt-in (ADAS_ML=1): measured slower than the per-layer launches at 64 frames (profiles/r05/ml_*.txt)
-    e->ml_on = prec_is16(precision) && env_on("ADAS_ML");
-    e->group_on = prec_is16(precision) && !e->ml_on && !env_on("ADAS_NO_GROUP");
+    e->mode = !prec_is16(precision) ? adas_engine::PLAIN : env_on("ADAS_ML") ? adas_engine::ML : env_on("ADAS_NO_GROUP") ? adas_engine::PLAIN : adas_engine::GROUPED;
     e->hdr = hd;
     e->name = fixed_name(hd.name, sizeof(hd.name));
     const uint64_t table_bytes = (uint64_t)hd.n_bufs * sizeof(FileBuf) + (uint64_t)hd.n_ops * sizeof(FileOp) + (uint64_t)hd.n_outputs * sizeof(FileOut);
@@ -282,7 +266,7 @@ void fuse_stem(adas_engine* e, const Uses& u) {
 }
 
 // ---- pass 2, projection shortcut folded into the conv that adds it (ResNet layerN.0: conv2 + downsample).  Only the link is made here:
-// whether a launch takes it is decided per batch, because the kernel that can (conv_halo8.hip) is chosen by batch (engine.cpp fold_ds)
+// whether a launch takes it is decided per batch, because the kernel that can (conv_halo8.hip) is chosen by batch (engine_schedule.cpp folds_shortcut)
 void link_shortcuts(adas_engine* e, const Uses& u) {
     for (int ci = 0; ci < u.n_ops() && prec_is16(e->prec); ++ci) {
         const FileOp& c = u.op(ci);
@@ -671,8 +655,8 @@ int allocate_and_upload(adas_engine* e, Source& src, const char* label) {
     ADAS_REQUIRE(rc == ADAS_OK, rc, "[%s]: failed while loading weights (%s)", label, rc == ADAS_ERR_HIP ? hipGetErrorString(hipGetLastError()) : "bad blob");
     const size_t in_bytes = (size_t)e->max_batch * e->hdr.in_c * e->hdr.in_h * e->hdr.in_w * 4;
     if (hipMalloc((void**)&e->d_input, in_bytes) != hipSuccess) return hip_fail(hipGetLastError(), "hipMalloc(input staging)", __FILE__, __LINE__);
-    // the grouped / multi-layer launch tables of the engine's own batch size are built now, not on the first forward (device
-    // allocations and synchronous copies do not belong on the hot path; other batch sizes are prepared on first use, engine_forward)
+    // the schedule of the engine's own batch size and its grouped / multi-layer launch tables are built now, not on the first forward
+    // (device allocations and synchronous copies do not belong on the hot path; other batch sizes are prepared on first use, engine_forward)
     return engine_prepare(e, e->max_batch) == ADAS_OK ? ADAS_OK : ADAS_ERR_HIP;
 }
 
@@ -738,6 +722,23 @@ int adas_debug_engine_plan(const void* tables, size_t bytes, int precision, int 
     if (rc == ADAS_OK) rc = validate_container(e.get(), "tables");
     if (rc == ADAS_OK) rc = plan_engine(e.get(), "tables");
     if (rc == ADAS_OK) rc = write_plan_rows(e.get(), rows, rows_cap, n_ops, weight_bytes);
+    return rc;
+}
+
+int adas_debug_engine_schedule(const void* tables, size_t bytes, int precision, int max_batch, int batch, int32_t* step_of, int32_t* role, char* labels,
+                               int cap, int32_t* n_ops, int32_t* n_steps) {
+    ADAS_REQUIRE(tables && max_batch > 0 && batch > 0 && batch <= max_batch, ADAS_ERR_INVALID, "adas_debug_engine_schedule: bad argument");
+    ADAS_REQUIRE(known_precision(precision), ADAS_ERR_INVALID, "unknown precision %d", precision);
+    Source src(tables, bytes);
+    EnginePtr e;
+    int rc = read_container(src, "tables", false, precision, max_batch, e);
+    if (rc == ADAS_OK) rc = validate_container(e.get(), "tables");
+    if (rc == ADAS_OK) rc = plan_engine(e.get(), "tables");
+    if (rc != ADAS_OK) return rc;
+    Placeholders ids(e.get());
+    Schedule s = plan_schedule(e.get(), batch, true);
+    rc = write_schedule_rows(e.get(), s, batch, step_of, role, labels, cap, n_ops, n_steps);
+    free_schedule(&s);
     return rc;
 }
 

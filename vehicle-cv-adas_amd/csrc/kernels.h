@@ -65,7 +65,7 @@ struct ConvPlan {
 ConvPlan plan_conv(int prec, int kh, int kw, int stride, int pad, int max_n, int res_mode, const TView& in, const TView& out);
 
 // Which kernel runs one launch of a conv: THE statement of the order of choice.  launch_conv switches on it, conv_kernel_name labels it,
-// the multi-layer / grouped planners (conv_ml.hip) and the shortcut fold (engine.cpp) ask it.  A route is returned only if its launcher
+// the multi-layer / grouped planners (conv_ml.hip) and the shortcut fold (engine_schedule.cpp) ask it.  A route is returned only if its launcher
 // takes the launch: the *_applicable predicates below are exact, a launcher that refuses what its predicate accepted is an error.
 enum class ConvRoute { IGEMM, PWG, HALO, HALO_RW, S2P, H8, PW, FC,          // 16-bit and fp32
                        X3_FC, X3_PW, H8X3, S2D_X3, S2P_X3, X3,              // split precision (X3: conv_x3.hip picks ksplit | igemm itself)
