@@ -408,7 +408,8 @@ int adas_ufld1_decode_run(adas_ufld_decode* h, const float* d_out, size_t batch_
  * Ego-lane geometry on the decoder's device-resident points: replaces
  * LaneDetectBase.__update_lanes_status / __update_lanes_area / __adjust_lanes_points (ufldDetector/core.py:102-158),
  * PerspectiveTransformation.transformToBirdViewPoints and .calcCurveAndOffset (perspectiveTransformation.py:120-214,
- * without the drawing calls).  The homography itself stays a host decision (updateTransformParams, :39-86).
+ * without the drawing calls).  One homography for the whole batch (create / set_matrix), or one per frame from a device table
+ * (run_matrices: adas_birdview keeps updateTransformParams, :39-86, on the device per stream).
  * ----------------------------------------------------------------------------------- */
 typedef struct adas_lane_geometry adas_lane_geometry;
 typedef struct {
@@ -432,6 +433,10 @@ int adas_lane_geometry_set_matrix(adas_lane_geometry* h, const double* M9);
 /* Reads the lane points the decoder (v1 or v2 handle) left in HBM for frames [0, batch). Asynchronous.
  * adjust_lanes < 0: the value given at create. */
 int adas_lane_geometry_run(adas_lane_geometry* h, const adas_ufld_decode* decode, int adjust_lanes, int batch, void* stream);
+/* The same kernel text with frame f reading its homography from d_M + 9 f (device, [batch][9] row-major, e.g. the first table of
+ * adas_birdview_device_views) instead of the handle's matrix.  A plain launch: capturable, and a changed matrix needs no re-capture. */
+int adas_lane_geometry_run_matrices(adas_lane_geometry* h, const adas_ufld_decode* decode, int adjust_lanes, int batch, const double* d_M,
+                                    void* stream);
 /* area_points: room for [2*img_h][2] int32 (x,y); bird_points: [4][ADAS_UFLD_MAX_POINTS][2]; either may be NULL. */
 int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometry_result* res, int32_t* area_points,
                              int32_t* bird_points);
@@ -459,10 +464,63 @@ int adas_warp_set_matrix(adas_warp* h, int frame, const double* M9, int inverse_
  * copy is staged, and is not capturable into a graph (a run with no matrix changed since the last one is a plain launch).
  * d_dst_bgr may be NULL: the handle's own [max_batch][dst_h][dst_w][3] buffer is written. */
 int adas_warp_run(adas_warp* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, int batch, void* stream);
+/* The same kernel with frame f's matrix read from d_M_warp + 9 f (device, [batch][9], destination -> source: what set_matrix forms
+ * by inversion, e.g. the second table of adas_birdview_device_views).  The handle's host matrices are neither read nor copied: a plain
+ * launch, capturable into a graph -- with d_dst_bgr = NULL once the handle's own buffer exists (adas_warp_device_view allocates it). */
+int adas_warp_run_device_matrices(adas_warp* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const double* d_M_warp, int batch, void* stream);
 /* Frame `frame` of the handle's own buffer -> h_dst_bgr [dst_h][dst_w][3], after the last run's stream has drained.  A frame that no
  * run has written (frame >= the largest batch run with d_dst_bgr = NULL) is ADAS_ERR_INVALID. */
 int adas_warp_fetch(adas_warp* h, int frame, uint8_t* h_dst_bgr);
 int adas_warp_device_view(adas_warp* h, const uint8_t** d_dst_bgr);
+
+/* -----------------------------------------------------------------------------------
+ * Per-stream adaptive bird view: replaces PerspectiveTransformation.__init__ / .updateTransformParams
+ * (perspectiveTransformation.py:21-86) with one trapezoid per video stream kept on the device.  The host (its TaskConditions state
+ * machine, demo.py:287-292) only says WHICH re-anchoring rule a stream applies next; the kernel applies it if and only if the two ego
+ * lanes of that frame are detected (area_status, core.py:143-148), consumes the request either way, solves
+ * cv2.getPerspectiveTransform both ways in fp64 (csrc/birdview_core.h; agreement with LAPACK / cv2 to rounding, not bit for bit) and
+ * leaves every frame's matrices in device tables for adas_lane_geometry_run_matrices and adas_warp_run_device_matrices.
+ * An update whose trapezoid is degenerate (singular system, non-finite result, det M == 0) is REJECTED: the state stays bit for bit
+ * what it was and n_rejected counts it -- the reference raises or goes on with garbage there.
+ * ----------------------------------------------------------------------------------- */
+typedef struct adas_birdview adas_birdview;
+typedef struct {
+    int32_t img_w, img_h;   /* PerspectiveTransformation.img_size: the initial trapezoid and the destination corners (:24-34) */
+} adas_birdview_params;
+#define ADAS_BIRDVIEW_NONE 0
+#define ADAS_BIRDVIEW_DEFAULT 1  /* updateTransformParams(..., "Default") */
+#define ADAS_BIRDVIEW_TOP 2      /* "Top": the bottom corners move by -10 / +10 from where they ARE, every time it is applied */
+#define ADAS_BIRDVIEW_BOTTOM 3   /* "Bottom" */
+typedef struct {
+    float src[8];         /* frontal-view trapezoid, float32 as in the reference: tl, bl, br, tr as (x, y) */
+    double M[9];          /* frontal -> bird view, row-major */
+    double M_inv[9];      /* bird view -> frontal (transformToFrontalView) */
+    double M_warp[9];     /* inverse of M by the warp's own 3x3 inversion: the destination -> source matrix of the bird-view image */
+    int32_t n_updates;    /* requests applied */
+    int32_t n_rejected;   /* requests rejected as degenerate */
+} adas_birdview_state;
+/* max_frames: frames of one run the per-frame tables hold (n_streams x frames per stream), >= n_streams. */
+int adas_birdview_create(const adas_birdview_params* p, int n_streams, int max_frames, adas_birdview** out);
+int adas_birdview_destroy(adas_birdview* h);
+/* Back to PerspectiveTransformation(img_size); drops a queued request.  stream = -1: every stream.  Waits for the whole device. */
+int adas_birdview_reset(adas_birdview* h, int stream);
+/* Queues `mode` (ADAS_BIRDVIEW_*; any other value is consumed without effect, as the reference ignores an unknown type) for the
+ * stream's NEXT run only: one word stored into a device table by a launch on hip_stream, so it must be the stream the next run is
+ * ordered behind.  No configuration generation moves and no captured step is dropped.  A later request before the run replaces it. */
+int adas_birdview_request(adas_birdview* h, int stream, int mode, void* hip_stream);
+/* One launch, one wave per stream.  Frame b of stream s is frame b * n_streams + s of the decoder.  The queued mode meets frame 0 of
+ * the stream; frames are walked in temporal order and every frame's matrices go to row b * n_streams + s of the tables, so later
+ * frames of the run carry the updated state.  A plain launch: capturable. */
+int adas_birdview_run(adas_birdview* h, const adas_ufld_decode* decode, int n_streams, int n_frames, void* hip_stream);
+/* The live state of one stream.  Synchronises with the last run's stream. */
+int adas_birdview_fetch_stream(adas_birdview* h, int stream, adas_birdview_state* state);
+/* Row `frame` of the last run: M9, M_warp9 and applied (1: the request was applied on this frame, -1: rejected on it, 0: neither);
+ * any of the three may be NULL.  Synchronises. */
+int adas_birdview_fetch_frame(adas_birdview* h, int frame, double* M9, double* M_warp9, int32_t* applied);
+/* The mode still queued for a stream (0: none).  Waits for the whole device. */
+int adas_birdview_pending(adas_birdview* h, int stream, int32_t* mode);
+/* The per-frame tables, [max_frames][9] doubles each; before the first run every row holds the initial matrices. */
+int adas_birdview_device_views(adas_birdview* h, const double** d_M, const double** d_M_warp);
 
 /* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
@@ -557,6 +615,15 @@ int adas_pipeline_create(const adas_pipeline_desc* d, adas_pipeline** out);
 /* 1 when the steps feed the post-processing's per-anchor scan arrays from the fused Detect kernel (adas_engine_set_detect_sink). */
 int adas_pipeline_detect_sink(const adas_pipeline* p);
 int adas_pipeline_destroy(adas_pipeline* p);
+/* Optional stages on the lane branch, right behind the decode and inside the capture: adas_birdview_run, then
+ * adas_lane_geometry_run_matrices on its per-frame matrices (in place of the geometry handle's single matrix), then -- with a warp
+ * handle -- adas_warp_run_device_matrices from the step's u8 frames into the warp handle's own buffer.  Call before the first step
+ * (cached graphs are dropped).  Needs a lane engine, a decode and a geometry handle; the bird-view handle must hold n_streams streams
+ * and n_streams x micro_batch frames, the warp handle as many frames and the step's camera geometry as its source size.  With a warp
+ * attached the seam-tensor step is ADAS_ERR_INVALID (no frame to warp).  `warp` may be NULL.  The handles stay the caller's. */
+int adas_pipeline_attach_birdview(adas_pipeline* p, adas_birdview* bird, adas_warp* warp);
+/* adas_birdview_request on the pipeline's own stream: lands on the next step, which replays the same graph. */
+int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);
 /* The same step from camera frames: n_streams BGR u8 frames (src_h x src_w x 3, back to back) in HBM; each branch runs its

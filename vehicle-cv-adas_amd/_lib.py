@@ -70,6 +70,18 @@ class WarpParams(C.Structure):
     _fields_ = [("src_h", C.c_int32), ("src_w", C.c_int32), ("dst_h", C.c_int32), ("dst_w", C.c_int32)]
 
 
+class BirdviewParams(C.Structure):
+    _fields_ = [("img_w", C.c_int32), ("img_h", C.c_int32)]
+
+
+class BirdviewState(C.Structure):
+    _fields_ = [("src", C.c_float * 8), ("M", C.c_double * 9), ("M_inv", C.c_double * 9), ("M_warp", C.c_double * 9),
+                ("n_updates", C.c_int32), ("n_rejected", C.c_int32)]
+
+
+BIRDVIEW_MODES = {"Default": 1, "Top": 2, "Bottom": 3}     # ADAS_BIRDVIEW_*: updateTransformParams' type strings
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -197,6 +209,19 @@ _SIGS = {
     "adas_lane_geometry_set_matrix": (C.c_int, [_P, _P]),
     "adas_lane_geometry_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "adas_lane_geometry_fetch": (C.c_int, [_P, C.c_int, C.POINTER(LaneGeometryResult), _P, _P]),
+    "adas_lane_geometry_run_matrices": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "adas_warp_run_device_matrices": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "adas_birdview_create": (C.c_int, [C.POINTER(BirdviewParams), C.c_int, C.c_int, C.POINTER(_P)]),
+    "adas_birdview_destroy": (C.c_int, [_P]),
+    "adas_birdview_reset": (C.c_int, [_P, C.c_int]),
+    "adas_birdview_request": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "adas_birdview_run": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "adas_birdview_fetch_stream": (C.c_int, [_P, C.c_int, C.POINTER(BirdviewState)]),
+    "adas_birdview_fetch_frame": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int32)]),
+    "adas_birdview_pending": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "adas_birdview_device_views": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "adas_pipeline_attach_birdview": (C.c_int, [_P, _P, _P]),
+    "adas_pipeline_request_transform": (C.c_int, [_P, C.c_int, C.c_int]),
     "adas_warp_create": (C.c_int, [C.POINTER(WarpParams), C.c_int, C.POINTER(_P)]),
     "adas_warp_destroy": (C.c_int, [_P]),
     "adas_warp_set_matrix": (C.c_int, [_P, C.c_int, _P, C.c_int]),

@@ -22,6 +22,7 @@ UNITS = [
     ("post_kernels.hip", ["-ffp-contract=off"]),
     ("pre_kernels.hip", ["-ffp-contract=off"]),
     ("warp_kernels.hip", ["-ffp-contract=off"]),
+    ("birdview_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

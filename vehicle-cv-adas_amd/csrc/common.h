@@ -23,10 +23,17 @@ void bump_config_generation();
 struct adas_yolo_post;
 struct adas_ufld_decode;
 struct adas_lane_geometry;
+struct adas_birdview;
+struct adas_warp;
 namespace adas {
 int handle_max_batch(const ::adas_yolo_post* h);
 int handle_max_batch(const ::adas_ufld_decode* h);
 int handle_max_batch(const ::adas_lane_geometry* h);
+// the decoder's device arrays (post_kernels.hip): counts [B][4], detected [B][4], points [B][4][128][2]
+void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int** det, const int** pts);
+// what adas_pipeline_attach_birdview checks (birdview_kernels.hip, warp_kernels.hip); 0 for a null handle
+int birdview_capacity(const ::adas_birdview* h, int* n_streams, int* max_frames);
+int warp_geometry(const ::adas_warp* h, int* src_h, int* src_w, int* max_batch);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

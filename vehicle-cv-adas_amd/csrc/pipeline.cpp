@@ -10,6 +10,9 @@ struct adas_bytetrack;
 
 struct adas_pipeline {
     adas_pipeline_desc d;
+    // optional stages behind the lane decode (adas_pipeline_attach_birdview): per-stream adaptive homographies, and the bird-view image
+    adas_birdview* bird = nullptr;
+    adas_warp* bird_warp = nullptr;
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -122,7 +125,20 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             rc = adas_ufld_decode_run(p->d.decode, adas_engine_output_device(le, 0), adas_engine_output_device(le, 1),
                                       adas_engine_output_device(le, 2), adas_engine_output_device(le, 3), stride, stride, stride, stride, S, sl);
         if (rc) return rc;
-        if (p->d.geometry) {
+        if (p->bird) {   // this step's trapezoids first: the geometry and the image warp read frame f's matrices from the handle's tables
+            const double *d_M, *d_M_warp;
+            rc = adas_birdview_device_views(p->bird, &d_M, &d_M_warp);
+            if (rc) return rc;
+            rc = adas_birdview_run(p->bird, p->d.decode, NS, B, sl);
+            if (rc) return rc;
+            rc = adas_lane_geometry_run_matrices(p->d.geometry, p->d.decode, -1, S, d_M, sl);
+            if (rc) return rc;
+            if (p->bird_warp) {
+                ADAS_REQUIRE(p->fsrc.frames, ADAS_ERR_INVALID, "the bird-view image needs camera frames: use adas_pipeline_step_frames");
+                rc = adas_warp_run_device_matrices(p->bird_warp, p->fsrc.frames, nullptr, d_M_warp, S, sl);
+                if (rc) return rc;
+            }
+        } else if (p->d.geometry) {
             rc = adas_lane_geometry_run(p->d.geometry, p->d.decode, -1, S, sl);
             if (rc) return rc;
         }
@@ -243,6 +259,36 @@ int adas_pipeline_create(const adas_pipeline_desc* d, adas_pipeline** out) {
 }
 int adas_pipeline_detect_sink(const adas_pipeline* p) { return p && p->sink ? 1 : 0; }
 
+int adas_pipeline_attach_birdview(adas_pipeline* p, adas_birdview* bird, adas_warp* warp) {
+    ADAS_REQUIRE(p && bird, ADAS_ERR_INVALID, "adas_pipeline_attach_birdview: bad argument");
+    ADAS_REQUIRE(p->d.lane && p->d.decode && p->d.geometry, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_birdview: the pipeline needs a lane engine, a decode handle and a geometry handle");
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int bs = 0, bf = 0;
+    (void)adas::birdview_capacity(bird, &bs, &bf);
+    ADAS_REQUIRE(bs >= p->d.n_streams && bf >= frames, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_birdview: the handle holds %d streams / %d frames, a step has %d streams / %d frames", bs, bf, p->d.n_streams, frames);
+    if (warp) {
+        int sh = 0, sw = 0, wb = 0;
+        (void)adas::warp_geometry(warp, &sh, &sw, &wb);
+        ADAS_REQUIRE(wb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_birdview: the warp handle holds %d frames, a step has %d", wb, frames);
+        const uint8_t* own = nullptr;   // its buffer exists before the first (captured) step
+        int rc = adas_warp_device_view(warp, &own);
+        if (rc) return rc;
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->bird = bird;
+    p->bird_warp = warp;
+    return ADAS_OK;
+}
+
+int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode) {
+    ADAS_REQUIRE(p && p->bird, ADAS_ERR_INVALID, "adas_pipeline_request_transform: no bird-view handle attached");
+    ADAS_REQUIRE(stream >= 0 && stream < p->d.n_streams, ADAS_ERR_INVALID, "adas_pipeline_request_transform: stream %d of %d", stream, p->d.n_streams);
+    return adas_birdview_request(p->bird, stream, mode, p->st);   // ordered ahead of the next step on the pipeline's stream; no re-capture
+}
+
 int adas_pipeline_destroy(adas_pipeline* p) {
     if (!p) return ADAS_OK;
     drop_graphs(p);
@@ -314,6 +360,7 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
     ADAS_REQUIRE(p, ADAS_ERR_INVALID, "null pipeline");
     ADAS_REQUIRE(!p->d.detector || d_det, ADAS_ERR_INVALID, "detector input missing");
     ADAS_REQUIRE(!p->d.lane || d_lane, ADAS_ERR_INVALID, "lane input missing");
+    ADAS_REQUIRE(!p->bird_warp, ADAS_ERR_INVALID, "a bird-view image warp is attached: seam tensors carry no frame to warp, use adas_pipeline_step_frames");
     if (!(p->d.use_graph & 1)) {
         p->timed = true;
         return record_step(p, d_det, d_lane, true);
@@ -324,6 +371,12 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
 int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int src_h, int src_w, double lane_crop_ratio) {
     ADAS_REQUIRE(p && d_frames_bgr && src_h > 0 && src_w > 0, ADAS_ERR_INVALID, "adas_pipeline_step_frames: bad argument");
     ADAS_REQUIRE(!p->d.lane || (lane_crop_ratio > 0.0 && lane_crop_ratio <= 1.0), ADAS_ERR_INVALID, "lane crop ratio must be in (0, 1]");
+    if (p->bird_warp) {   // the warp reads the step's frames with its own source geometry
+        int sh = 0, sw = 0, wb = 0;
+        (void)adas::warp_geometry(p->bird_warp, &sh, &sw, &wb);
+        ADAS_REQUIRE(sh == src_h && sw == src_w, ADAS_ERR_INVALID, "the attached warp handle was created for %dx%d source frames, the step has %dx%d", sh, sw,
+                     src_h, src_w);
+    }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
     if (!p->det_in && !p->lane_in) {
         const char* env = getenv("ADAS_NO_PACKED_SEAM");

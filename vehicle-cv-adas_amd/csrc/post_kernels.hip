@@ -242,6 +242,26 @@ __global__ __launch_bounds__(256) void lane_geometry_kernel(LaneGeomDev d) {
     lane_geometry_frame(c, d.cfg, f, smem);
 }
 
+// the same frames, frame b with its own homography Mtab[b] (adas_birdview's per-frame table) in place of cfg.M
+__global__ __launch_bounds__(256) void lane_geometry_matrices_kernel(LaneGeomDev d, const double* __restrict__ Mtab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t b = blockIdx.x, H = d.cfg.img_h;
+    LaneGeomCfg cfg = d.cfg;
+    for (int k = 0; k < 9; ++k) cfg.M[k] = Mtab[b * 9 + k];   // workgroup-uniform
+    LaneGeomFrame f;
+    f.lane_cnt = d.lane_cnt + b * 4;
+    f.lane_det = d.lane_det + b * 4;
+    f.lane_pts = d.lane_pts + b * 4 * ADAS_LANE_MAXPTS * 2;
+    f.hdr = d.hdr + b * 8;
+    f.vals = d.vals + b * 2;
+    f.area = d.area + b * 4 * H;
+    f.bird = d.bird + b * 4 * ADAS_LANE_MAXPTS * 2;
+    f.fx = d.fx + b * 2 * H;
+    f.idx = d.idx + b * 2 * H;
+    Ctx c{(int)threadIdx.x, (int)blockDim.x};
+    lane_geometry_frame(c, cfg, f, smem);
+}
+
 // -------------------------------------------------------------------------------------
 struct BtDev {
     BtParams P;
@@ -492,6 +512,11 @@ namespace adas {
 int handle_max_batch(const ::adas_yolo_post* h) { return h ? h->max_batch : 0; }
 int handle_max_batch(const ::adas_ufld_decode* h) { return h ? h->max_batch : 0; }
 int handle_max_batch(const ::adas_lane_geometry* h) { return h ? h->max_batch : 0; }
+void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int** det, const int** pts) {
+    *cnt = h->dev.lane_cnt;
+    *det = h->dev.lane_det;
+    *pts = h->dev.lane_pts;
+}
 }  // namespace adas
 
 template <class T>
@@ -1152,7 +1177,8 @@ int adas_lane_geometry_create(const adas_lane_geometry_params* p, int max_batch,
     d.area = carve<int>(q, B * 4 * H);
     d.bird = carve<int>(q, B * 4 * ADAS_LANE_MAXPTS * 2);
     d.idx = carve<int>(q, B * 2 * H);
-    if (hipFuncSetAttribute((const void*)lane_geometry_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
+    if (hipFuncSetAttribute((const void*)lane_geometry_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)lane_geometry_matrices_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
         hipFree(h->arena);
         delete h;
         return hip_fail(hipGetLastError(), "hipFuncSetAttribute(lane_geometry_kernel)", __FILE__, __LINE__);
@@ -1185,6 +1211,20 @@ int adas_lane_geometry_run(adas_lane_geometry* h, const adas_ufld_decode* decode
     d.lane_det = decode->dev.lane_det;
     d.lane_pts = decode->dev.lane_pts;
     hipLaunchKernelGGL(lane_geometry_kernel, dim3(batch), dim3(256), lane_lds_bytes(d.cfg.img_h, d.cfg.bird_h), st, d);
+    ADAS_HIP_TRY(hipGetLastError());
+    return ADAS_OK;
+}
+int adas_lane_geometry_run_matrices(adas_lane_geometry* h, const adas_ufld_decode* decode, int adjust_lanes, int batch, const double* d_M, void* stream) {
+    ADAS_REQUIRE(h && decode && d_M && batch > 0 && batch <= h->max_batch && batch <= decode->max_batch, ADAS_ERR_INVALID,
+                 "adas_lane_geometry_run_matrices: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    h->last = st;
+    LaneGeomDev d = h->dev;
+    if (adjust_lanes >= 0) d.cfg.adjust = adjust_lanes ? 1 : 0;
+    d.lane_cnt = decode->dev.lane_cnt;
+    d.lane_det = decode->dev.lane_det;
+    d.lane_pts = decode->dev.lane_pts;
+    hipLaunchKernelGGL(lane_geometry_matrices_kernel, dim3(batch), dim3(256), lane_lds_bytes(d.cfg.img_h, d.cfg.bird_h), st, d, d_M);
     ADAS_HIP_TRY(hipGetLastError());
     return ADAS_OK;
 }

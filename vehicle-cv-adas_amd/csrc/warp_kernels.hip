@@ -103,6 +103,33 @@ static int warp_own_buffer(adas_warp* h) {
     return ADAS_OK;
 }
 
+namespace adas {
+int warp_geometry(const ::adas_warp* h, int* src_h, int* src_w, int* max_batch) {
+    if (!h) return 0;
+    *src_h = h->p.src_h;
+    *src_w = h->p.src_w;
+    *max_batch = h->max_batch;
+    return 1;
+}
+}  // namespace adas
+
+// frames [0, batch) of src through matrices M [batch][9] (device, destination -> source) into dst, or the handle's own buffer
+static int warp_launch(adas_warp* h, const uint8_t* src, uint8_t* dst, const double* M, int batch, hipStream_t st) {
+    WarpDev d;
+    d.src = src;
+    d.dst = dst ? dst : h->d_dst;
+    d.M = M;
+    d.sh = h->p.src_h; d.sw = h->p.src_w; d.dh = h->p.dst_h; d.dw = h->p.dst_w;
+    d.bw = warp_block_width(d.dh, d.dw);
+    d.rows = warp_rows();
+    d.runs = (d.dw + 3) / 4;
+    hipLaunchKernelGGL(warp_perspective_kernel, dim3((unsigned)((d.dh + d.rows - 1) / d.rows), (unsigned)batch), dim3(256), 0, st, d);
+    ADAS_HIP_TRY(hipGetLastError());
+    h->last = st;
+    if (!dst && batch > h->dst_frames) h->dst_frames = batch;
+    return ADAS_OK;
+}
+
 extern "C" {
 
 int adas_warp_create(const adas_warp_params* p, int max_batch, adas_warp** out) {
@@ -162,19 +189,19 @@ int adas_warp_run(adas_warp* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, in
         ADAS_HIP_TRY(hipMemcpyAsync(h->d_M + 9 * (size_t)f, &h->M[9 * (size_t)f], (size_t)(e - f) * 9 * sizeof(double), hipMemcpyHostToDevice, st));
         f = e;
     }
-    WarpDev d;
-    d.src = d_src_bgr;
-    d.dst = d_dst_bgr ? d_dst_bgr : h->d_dst;
-    d.M = h->d_M;
-    d.sh = h->p.src_h; d.sw = h->p.src_w; d.dh = h->p.dst_h; d.dw = h->p.dst_w;
-    d.bw = warp_block_width(d.dh, d.dw);
-    d.rows = warp_rows();
-    d.runs = (d.dw + 3) / 4;
-    hipLaunchKernelGGL(warp_perspective_kernel, dim3((unsigned)((d.dh + d.rows - 1) / d.rows), (unsigned)batch), dim3(256), 0, st, d);
-    ADAS_HIP_TRY(hipGetLastError());
-    h->last = st;
-    if (!d_dst_bgr && batch > h->dst_frames) h->dst_frames = batch;
-    return ADAS_OK;
+    return warp_launch(h, d_src_bgr, d_dst_bgr, h->d_M, batch, st);
+}
+
+int adas_warp_run_device_matrices(adas_warp* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const double* d_M_warp, int batch, void* stream) {
+    ADAS_REQUIRE(h && d_src_bgr && d_M_warp && batch > 0 && batch <= h->max_batch, ADAS_ERR_INVALID,
+                 "adas_warp_run_device_matrices: bad argument (batch %d, handle holds %d)", batch, h ? h->max_batch : 0);
+    ADAS_REQUIRE(adas_device_count() > 0, ADAS_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    // the handle's own buffer is allocated here only outside a capture: adas_warp_device_view beforehand makes the run a plain launch
+    if (!d_dst_bgr) {
+        int rc = warp_own_buffer(h);
+        if (rc) return rc;
+    }
+    return warp_launch(h, d_src_bgr, d_dst_bgr, d_M_warp, batch, (hipStream_t)stream);
 }
 
 int adas_warp_fetch(adas_warp* h, int frame, uint8_t* h_dst_bgr) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -20,17 +20,24 @@ CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
 class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
-                 max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1):
+                 max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
+                 birdview=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
-        them in order.  Throughput mode for few streams per GPU."""
+        them in order.  Throughput mode for few streams per GPU.
+        birdview: None, or dict(image=bool): one adaptive bird-view trapezoid per stream on the device (postproc.BirdView with
+        img_size = geometry["bird_wh"]); the geometry then reads every frame's own matrix, request_transform(stream, mode) re-anchors a
+        stream on its next step, and with image=True step_frames also warps every frame into the bird view (birdview_image).
+        Needs geometry=; geometry["M"] is then only the handle's stand-alone matrix."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
-        self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = None
+        self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = None
+        if birdview is not None and (geometry is None or not lane_model):
+            raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:
             self.det = HipEngine(det_model, precision, n_streams)
             ishape = self.det.get_engine_input_shape()
@@ -66,6 +73,12 @@ class AdasPipeline:
         h = C.c_void_p()
         L.check(L.lib().adas_pipeline_create(C.byref(d), C.byref(h)))
         self.h = h.value
+        if birdview is not None:
+            bw, bh = (int(v) for v in geometry["bird_wh"])
+            self.birdview = BirdView((bw, bh), n_tracks, n_streams)
+            if dict(birdview).get("image", False):
+                self.warp = PerspectiveWarp(src_hw, (bh, bw), n_streams)
+            L.check(L.lib().adas_pipeline_attach_birdview(self.h, self.birdview.h, self.warp.h if self.warp else None))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -92,6 +105,21 @@ class AdasPipeline:
         staging buffers, overlapped with the previous step's compute."""
         L.check(L.lib().adas_pipeline_step_frames_host(self.h, h_frames_ptr, int(src_hw[0]), int(src_hw[1]), float(lane_crop_ratio)))
 
+    def request_transform(self, stream, mode_name):
+        """updateTransformParams(..., type=mode_name) for local stream `stream` on its NEXT step ("Default" | "Top" | "Bottom"): applied
+        there if that frame's two ego lanes are detected, consumed either way; None or any other name is consumed without effect, as the
+        reference ignores it (TaskConditions.transform_status can be None).  No re-capture."""
+        if self.birdview is None:
+            raise ValueError("the pipeline was created without birdview=")
+        m = BirdView.MODES.get(mode_name, -1) if (mode_name is None or isinstance(mode_name, str)) else int(mode_name)
+        L.check(L.lib().adas_pipeline_request_transform(self.h, int(stream), m))
+
+    def birdview_image(self, frame=0):
+        """The bird-view image of frame `frame` of the last step_frames (after sync()): (bird_h, bird_w, 3) uint8."""
+        if self.warp is None:
+            raise ValueError("the pipeline was created without birdview=dict(image=True)")
+        return self.warp.fetch(frame)
+
     def wait_upload(self):
         """Block until the last step_frames_host upload has read its host buffer (then the buffer may be refilled)."""
         L.check(L.lib().adas_pipeline_wait_upload(self.h))
@@ -115,7 +143,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

@@ -6,6 +6,7 @@ UfldDecode    <- UltrafastLaneDetectorV2.__process_output (ultrafastLaneDetector
 DeviceTracker <- BYTETracker.update/reset (ObjectTracker/byteTrack/byteTracker.py:62-200)
 PerspectiveWarp <- cv2.warpPerspective in PerspectiveTransformation.transformToBirdView / transformToFrontalView
                  (ufldDetector/perspectiveTransformation.py:89-117)
+BirdView      <- PerspectiveTransformation.__init__ / updateTransformParams (perspectiveTransformation.py:21-86), one per stream
 """
 import ctypes as C
 
@@ -286,6 +287,10 @@ class LaneGeometry:
     def run(self, decode, adjust_lanes=True, batch=1, stream=None):
         L.check(L.lib().adas_lane_geometry_run(self.h, decode.h, 1 if adjust_lanes else 0, batch, stream))
 
+    def run_matrices(self, decode, d_M_ptr, adjust_lanes=True, batch=1, stream=None):
+        """run() with frame f reading its homography from the device table d_M_ptr [batch][9] (BirdView.device_views()[0])."""
+        L.check(L.lib().adas_lane_geometry_run_matrices(self.h, decode.h, 1 if adjust_lanes else 0, batch, d_M_ptr, stream))
+
     def fetch(self, frame=0):
         res = L.LaneGeometryResult()
         area = np.zeros((2 * self.img_h, 2), np.int32)
@@ -327,6 +332,11 @@ class PerspectiveWarp:
         """src_ptr: device pointer of [batch][src_h][src_w][3] u8.  dst_ptr=None writes the handle's own buffer (fetch / device_view)."""
         L.check(L.lib().adas_warp_run(self.h, src_ptr, dst_ptr, int(batch), stream))
 
+    def run_device_matrices(self, src_ptr, d_M_warp_ptr, batch=1, dst_ptr=None, stream=None):
+        """run() with frame f's destination -> source matrix read from the device table d_M_warp_ptr [batch][9]
+        (BirdView.device_views()[1]); set_matrix plays no part.  A plain launch."""
+        L.check(L.lib().adas_warp_run_device_matrices(self.h, src_ptr, dst_ptr, d_M_warp_ptr, int(batch), stream))
+
     def fetch(self, frame=0):
         out = np.empty((self.dst_hw[0], self.dst_hw[1], 3), np.uint8)
         L.check(L.lib().adas_warp_fetch(self.h, int(frame), L.ptr(out)))
@@ -340,6 +350,64 @@ class PerspectiveWarp:
     def close(self):
         if getattr(self, "h", None):
             L.lib().adas_warp_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class BirdView:
+    """One PerspectiveTransformation trapezoid per video stream kept on the device (perspectiveTransformation.py:21-86): request()
+    queues updateTransformParams' type for a stream's next run, run() applies it where that frame's two ego lanes are detected and
+    leaves every frame's matrices in device tables (device_views) for LaneGeometry.run_matrices / PerspectiveWarp.run_device_matrices."""
+    MODES = L.BIRDVIEW_MODES
+
+    def __init__(self, img_size, n_streams=1, max_frames=None):
+        p = L.BirdviewParams(int(img_size[0]), int(img_size[1]))
+        self.img_size, self.n_streams = (p.img_w, p.img_h), int(n_streams)
+        self.max_frames = int(max_frames) if max_frames else self.n_streams
+        h = C.c_void_p()
+        L.check(L.lib().adas_birdview_create(C.byref(p), self.n_streams, self.max_frames, C.byref(h)))
+        self.h = h.value
+
+    def request(self, stream, mode, hip_stream=None):
+        """mode: "Default" | "Top" | "Bottom" (or its number); anything else is consumed by the next run without effect, as the
+        reference ignores an unknown type."""
+        m = self.MODES.get(mode, -1) if (mode is None or isinstance(mode, str)) else int(mode)
+        L.check(L.lib().adas_birdview_request(self.h, int(stream), m, hip_stream))
+
+    def run(self, decode, n_streams=None, n_frames=1, stream=None):
+        L.check(L.lib().adas_birdview_run(self.h, decode.h, int(n_streams or self.n_streams), int(n_frames), stream))
+
+    def fetch_stream(self, stream=0):
+        s = L.BirdviewState()
+        L.check(L.lib().adas_birdview_fetch_stream(self.h, int(stream), C.byref(s)))
+        return dict(src=np.array(s.src, np.float32).reshape(4, 2), M=np.array(s.M, np.float64).reshape(3, 3),
+                    M_inv=np.array(s.M_inv, np.float64).reshape(3, 3), M_warp=np.array(s.M_warp, np.float64).reshape(3, 3),
+                    n_updates=int(s.n_updates), n_rejected=int(s.n_rejected))
+
+    def fetch_frame(self, frame=0):
+        M, Mw, a = np.zeros(9, np.float64), np.zeros(9, np.float64), C.c_int32()
+        L.check(L.lib().adas_birdview_fetch_frame(self.h, int(frame), L.ptr(M), L.ptr(Mw), C.byref(a)))
+        return dict(M=M.reshape(3, 3), M_warp=Mw.reshape(3, 3), applied=int(a.value))
+
+    def pending(self, stream=0):
+        """The mode still queued for the stream (0: none)."""
+        m = C.c_int32()
+        L.check(L.lib().adas_birdview_pending(self.h, int(stream), C.byref(m)))
+        return int(m.value)
+
+    def device_views(self):
+        """(d_M, d_M_warp): device pointers of the per-frame tables, [max_frames][9] float64 each."""
+        a, b = C.c_void_p(), C.c_void_p()
+        L.check(L.lib().adas_birdview_device_views(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def reset(self, stream=-1):
+        L.check(L.lib().adas_birdview_reset(self.h, int(stream)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_birdview_destroy(self.h)
             self.h = None
 
     __del__ = close
