@@ -440,6 +440,11 @@ int adas_lane_geometry_run_matrices(adas_lane_geometry* h, const adas_ufld_decod
 /* area_points: room for [2*img_h][2] int32 (x,y); bird_points: [4][ADAS_UFLD_MAX_POINTS][2]; either may be NULL. */
 int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometry_result* res, int32_t* area_points,
                              int32_t* bird_points);
+/* Device views of the results for GPU-resident consumers (adas_analysis_run): per frame 8 header words (area_status, n_area_left,
+ * n_area_right, direction, bird_counts[4]: the int32 fields of adas_lane_geometry_result in order), 2 doubles (curvature, offset) and
+ * the area polygon, frame f's (x, y) pairs at d_area + f * area_stride int32 (room for 2 * img_h points). */
+int adas_lane_geometry_device_views(adas_lane_geometry* h, const int32_t** d_header, const double** d_values, const int32_t** d_area,
+                                    int32_t* area_stride);
 
 /* -----------------------------------------------------------------------------------
  * Bird-view image: replaces the cv2.warpPerspective calls of PerspectiveTransformation.transformToBirdView /
@@ -521,6 +526,117 @@ int adas_birdview_fetch_frame(adas_birdview* h, int frame, double* M9, double* M
 int adas_birdview_pending(adas_birdview* h, int stream, int32_t* mode);
 /* The per-frame tables, [max_frames][9] doubles each; before the first run every row holds the initial matrices. */
 int adas_birdview_device_views(adas_birdview* h, const double** d_M, const double** d_M_warp);
+
+/* -----------------------------------------------------------------------------------
+ * Distance, collision and warning state per stream: replaces the last block of the reference's loop (demo.py:284-296) --
+ * SingleCamDistanceMeasure.updateDistance / calcCollisionPoint (ObjectDetector/distanceMeasure.py:50-93) and TaskConditions
+ * .UpdateCollisionStatus / UpdateOffsetStatus / UpdateRouteStatus / CheckStatus (taskConditions.py:88-312) -- with one state machine
+ * per video stream kept on the device (csrc/analysis_core.h).  Per frame: the three updates in the reference's order, then CheckStatus()
+ * FOR THE NEXT FRAME (the reference calls it at the start of that frame; nothing in between touches what it reads); its result is the
+ * stream's request word: the new transform_status (ADAS_BIRDVIEW_*) when it returned true, else ADAS_BIRDVIEW_NONE.  A new or reset
+ * stream is TaskConditions() after its first CheckStatus(), which returns true with "Default": the owner of a bird view queues that one.
+ * Defined where the reference leaves it to chance: a window that mixes directions picks R before L before F (what its
+ * max(set(...), key=...) returns under PYTHONHASHSEED=0); a frame whose curvature is not finite (the reference raises) counts as a frame
+ * without a curve estimate, in n_nonfinite.
+ * ----------------------------------------------------------------------------------- */
+typedef struct adas_analysis adas_analysis;
+typedef struct {
+    double focal;               /* SingleCamDistanceMeasure.f: 100 (distanceMeasure.py:21) */
+    double y_limit;             /* boxes whose bottom lies below this row are not measured: 650 (:62) */
+    double distance_thres;      /* UpdateCollisionStatus: 1.5 */
+    double offset_thres;        /* UpdateOffsetStatus: 0.65 */
+    double curvae_thres;        /* UpdateRouteStatus: 500 */
+    double calib_curvae_thres;  /* _calibration_curve: 15000 */
+    int32_t calib_frequency;    /* _calibration_curve: 3 */
+    int32_t n_classes;          /* entries of h_ref_height */
+    const double* h_ref_height; /* [n_classes] (host, copied): RefSizeDict[label][0] in inches for the detector's class ids, 0 for a class
+                                 * outside object_list (the device never sees a label string) */
+    int32_t max_points;         /* survivors read and distance points kept per frame, 1..2048 (512) */
+    int32_t max_poly;           /* points of a frame's ego-lane polygon, 1..8640 (1440 = 2 x 720 rows) */
+} adas_analysis_params;
+#define ADAS_COLLISION_UNKNOWN 0 /* CollisionType (ObjectDetector/utils.py:8-12) */
+#define ADAS_COLLISION_NORMAL 1
+#define ADAS_COLLISION_PROMPT 2
+#define ADAS_COLLISION_WARNING 3
+#define ADAS_OFFSET_UNKNOWN 0    /* OffsetType (ufldDetector/utils.py:10-14) */
+#define ADAS_OFFSET_RIGHT 1
+#define ADAS_OFFSET_LEFT 2
+#define ADAS_OFFSET_CENTER 3
+#define ADAS_CURVATURE_UNKNOWN 0 /* CurvatureType (ufldDetector/utils.py:16-22) */
+#define ADAS_CURVATURE_STRAIGHT 1
+#define ADAS_CURVATURE_EASY_LEFT 2
+#define ADAS_CURVATURE_HARD_LEFT 3
+#define ADAS_CURVATURE_EASY_RIGHT 4
+#define ADAS_CURVATURE_HARD_RIGHT 5
+#define ADAS_ANALYSIS_OVERFLOW 1  /* frame flags: the detector frame reported a capacity overflow (adas_yolo_counts.flags bit0) */
+#define ADAS_ANALYSIS_NONFINITE 2 /* the frame's curvature was not finite */
+#define ADAS_ANALYSIS_TRUNCATED 4 /* more survivors than max_points: the rest was not read */
+typedef struct {                  /* one stream's TaskConditions (taskConditions.py:90-101) */
+    int32_t collision_msg, offset_msg, curvature_msg;  /* ADAS_COLLISION_* / ADAS_OFFSET_* / ADAS_CURVATURE_* */
+    int32_t toggle_status, transform_status;           /* ADAS_BIRDVIEW_* (NONE = Python's None) */
+    int32_t oscillator[2];                             /* toggle_oscillator_status */
+    int32_t counter_offset, counter_curvae, counter_birdview; /* toggle_status_counter */
+    int32_t n_collision, n_offset, n_curvature;        /* lengths of the three windows */
+    int32_t n_nonfinite;                               /* frames whose curvature was not finite */
+    double collision_record[5], offset_record[5];      /* the windows, oldest entry first */
+    double curvature_record[10];
+    int32_t direction_record[10];                      /* direction (adas_lane_geometry_result.direction) of each curvature entry */
+} adas_analysis_state;
+typedef struct {                  /* what one frame hands TaskConditions */
+    int32_t has_point;            /* calcCollisionPoint returned a point ... */
+    int32_t area;                 /* lane_info.area_status */
+    int32_t has_offset;           /* vehicle_offset is not None */
+    int32_t has_curvature;        /* vehicle_curvature is not None */
+    int32_t direction;            /* 0: vehicle_direction is None, 1 "L", 2 "R", 3 "F" */
+    int32_t reserved;
+    double distance;              /* ... and its metres */
+    double offset, curvature;
+} adas_analysis_input;
+typedef struct {                  /* one frame of the last run */
+    int32_t n_points;             /* distance points (adas_analysis_fetch_points) */
+    int32_t has_collision;        /* 0: calcCollisionPoint is None */
+    int32_t collision_x, collision_y;
+    double collision_d;
+    int32_t collision_index;      /* the point's index among the frame's distance points, -1: none */
+    int32_t collision_msg, offset_msg, curvature_msg;  /* after the frame's three updates */
+    int32_t toggle_status, transform_status;           /* after the updates, before the next frame's CheckStatus() */
+    int32_t oscillator[2];
+    int32_t counters[3];          /* Offset, Curvae, BirdViewAngle */
+    int32_t check;                /* CheckStatus() for the next frame */
+    int32_t request;              /* the word written for it: the new transform_status if check, else ADAS_BIRDVIEW_NONE */
+    int32_t flags;                /* ADAS_ANALYSIS_* */
+} adas_analysis_frame;
+/* The reference's constants; no classes (n_classes 0, h_ref_height NULL), max_points 512, max_poly 1440. */
+int adas_analysis_default_params(adas_analysis_params* p);
+/* max_frames: frames of one run the per-frame tables hold (n_streams x frames per stream), >= n_streams. */
+int adas_analysis_create(const adas_analysis_params* p, int n_streams, int max_frames, adas_analysis** out);
+int adas_analysis_destroy(adas_analysis* h);
+/* Back to TaskConditions() after its first CheckStatus(); stream = -1: every stream.  Waits for the whole device.  In a pipeline with a
+ * bird view (adas_pipeline_attach_analysis) it also queues that stream's "Default" request. */
+int adas_analysis_reset(adas_analysis* h, int stream);
+/* One launch, one workgroup per stream, on the handles' device arrays: the survivors of adas_yolo_post_device_views, the area polygon
+ * and results of adas_lane_geometry_device_views.  Frame b of stream s is frame b * n_streams + s of both; the frames of a stream are
+ * walked in temporal order.  bird may be NULL; otherwise each stream's request word is stored into that handle's pending table, where
+ * its next adas_birdview_run consumes it (order the two launches on one stream, or by events).  A plain launch: capturable. */
+int adas_analysis_run(adas_analysis* h, adas_yolo_post* post, adas_lane_geometry* geometry, adas_birdview* bird, int n_streams, int n_frames,
+                      void* stream);
+/* The same kernel on raw device arrays: d_xyxy [frames][det_stride][4] fp64 of the int-truncated corners, d_cls [frames][det_stride],
+ * d_counts [frames][4] laid out as the adas_yolo_counts record: n_keep survivors are read, flags bit0 is reported; d_poly [frames][poly_cap][2] with
+ * d_poly_counts [frames]; one adas_lane_geometry_result per frame (area_status, direction, curvature and offset are read); d_request
+ * [n_streams] may be NULL. */
+int adas_analysis_run_arrays(adas_analysis* h, const double* d_xyxy, const int32_t* d_cls, const int32_t* d_counts, int det_stride,
+                             const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const adas_lane_geometry_result* d_geometry,
+                             int32_t* d_request, int n_streams, int n_frames, void* stream);
+/* The state machine alone, for replays and callers with their own geometry: h_inputs [n_streams * n_frames] (host), frame b of stream s at
+ * b * n_streams + s.  Copied on `stream` ahead of the launch from the caller's memory: not capturable. */
+int adas_analysis_run_inputs(adas_analysis* h, const adas_analysis_input* h_inputs, int n_streams, int n_frames, void* stream);
+/* The live state of one stream.  Synchronises with the last run's stream. */
+int adas_analysis_fetch_stream(adas_analysis* h, int stream, adas_analysis_state* state);
+/* Row `frame` of the last run.  Synchronises. */
+int adas_analysis_fetch_frame(adas_analysis* h, int frame, adas_analysis_frame* out);
+/* The first n distance points of that frame in survivor order: xy [n][2] (x centre, y bottom), d [n] metres; either may be NULL.
+ * ADAS_ERR_INVALID after adas_analysis_run_inputs (no points). */
+int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double* d, int n);
 
 /* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
@@ -622,8 +738,18 @@ int adas_pipeline_destroy(adas_pipeline* p);
  * and n_streams x micro_batch frames, the warp handle as many frames and the step's camera geometry as its source size.  With a warp
  * attached the seam-tensor step is ADAS_ERR_INVALID (no frame to warp).  `warp` may be NULL.  The handles stay the caller's. */
 int adas_pipeline_attach_birdview(adas_pipeline* p, adas_birdview* bird, adas_warp* warp);
-/* adas_birdview_request on the pipeline's own stream: lands on the next step, which replays the same graph. */
+/* adas_birdview_request on the pipeline's own stream: lands on the next step, which replays the same graph.  ADAS_ERR_INVALID while an
+ * analysis handle is attached: the device then owns the requests. */
 int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode);
+/* Optional last stage of the step: adas_analysis_run on the pipeline's main stream behind the join of the two branches, inside the
+ * capture.  Needs a detector with its post handle and a lane engine with decode and geometry handles; the analysis handle must hold
+ * n_streams streams and n_streams x micro_batch frames.  With a bird-view handle attached (in either order) the stage stores each stream's
+ * request word into that handle's pending table, the next step's adas_birdview_run consumes it (ordered through that step's own fork),
+ * every stream's initial "Default" is queued now and again by adas_analysis_reset, and adas_pipeline_request_transform is refused; that
+ * combination needs micro_batch <= 1 (frame b's request could not reach frame b + 1 inside one step).  Call before the first step (cached
+ * graphs are dropped).  Without it the step, its graph and its launch count are unchanged.  The handle stays the caller's and must outlive
+ * the pipeline. */
+int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);
 /* The same step from camera frames: n_streams BGR u8 frames (src_h x src_w x 3, back to back) in HBM; each branch runs its

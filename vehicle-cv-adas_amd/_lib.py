@@ -82,6 +82,37 @@ class BirdviewState(C.Structure):
 BIRDVIEW_MODES = {"Default": 1, "Top": 2, "Bottom": 3}     # ADAS_BIRDVIEW_*: updateTransformParams' type strings
 
 
+class AnalysisParams(C.Structure):
+    _fields_ = [("focal", C.c_double), ("y_limit", C.c_double), ("distance_thres", C.c_double), ("offset_thres", C.c_double),
+                ("curvae_thres", C.c_double), ("calib_curvae_thres", C.c_double), ("calib_frequency", C.c_int32), ("n_classes", C.c_int32),
+                ("h_ref_height", C.c_void_p), ("max_points", C.c_int32), ("max_poly", C.c_int32)]
+
+
+class AnalysisState(C.Structure):
+    _fields_ = [("collision_msg", C.c_int32), ("offset_msg", C.c_int32), ("curvature_msg", C.c_int32), ("toggle_status", C.c_int32),
+                ("transform_status", C.c_int32), ("oscillator", C.c_int32 * 2), ("counter_offset", C.c_int32), ("counter_curvae", C.c_int32),
+                ("counter_birdview", C.c_int32), ("n_collision", C.c_int32), ("n_offset", C.c_int32), ("n_curvature", C.c_int32),
+                ("n_nonfinite", C.c_int32), ("collision_record", C.c_double * 5), ("offset_record", C.c_double * 5),
+                ("curvature_record", C.c_double * 10), ("direction_record", C.c_int32 * 10)]
+
+
+class AnalysisInput(C.Structure):
+    _fields_ = [("has_point", C.c_int32), ("area", C.c_int32), ("has_offset", C.c_int32), ("has_curvature", C.c_int32), ("direction", C.c_int32),
+                ("reserved", C.c_int32), ("distance", C.c_double), ("offset", C.c_double), ("curvature", C.c_double)]
+
+
+class AnalysisFrame(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("has_collision", C.c_int32), ("collision_x", C.c_int32), ("collision_y", C.c_int32),
+                ("collision_d", C.c_double), ("collision_index", C.c_int32), ("collision_msg", C.c_int32), ("offset_msg", C.c_int32),
+                ("curvature_msg", C.c_int32), ("toggle_status", C.c_int32), ("transform_status", C.c_int32), ("oscillator", C.c_int32 * 2),
+                ("counters", C.c_int32 * 3), ("check", C.c_int32), ("request", C.c_int32), ("flags", C.c_int32)]
+
+
+ANALYSIS_INPUT_DTYPE = np.dtype([("has_point", "i4"), ("area", "i4"), ("has_offset", "i4"), ("has_curvature", "i4"), ("direction", "i4"),
+                                 ("reserved", "i4"), ("distance", "f8"), ("offset", "f8"), ("curvature", "f8")])
+ANALYSIS_OVERFLOW, ANALYSIS_NONFINITE, ANALYSIS_TRUNCATED = 1, 2, 4     # adas_analysis_frame.flags
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -221,6 +252,18 @@ _SIGS = {
     "adas_birdview_pending": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
     "adas_birdview_device_views": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "adas_pipeline_attach_birdview": (C.c_int, [_P, _P, _P]),
+    "adas_pipeline_attach_analysis": (C.c_int, [_P, _P]),
+    "adas_lane_geometry_device_views": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "adas_analysis_default_params": (C.c_int, [C.POINTER(AnalysisParams)]),
+    "adas_analysis_create": (C.c_int, [C.POINTER(AnalysisParams), C.c_int, C.c_int, C.POINTER(_P)]),
+    "adas_analysis_destroy": (C.c_int, [_P]),
+    "adas_analysis_reset": (C.c_int, [_P, C.c_int]),
+    "adas_analysis_run": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_analysis_run_arrays": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_analysis_run_inputs": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "adas_analysis_fetch_stream": (C.c_int, [_P, C.c_int, C.POINTER(AnalysisState)]),
+    "adas_analysis_fetch_frame": (C.c_int, [_P, C.c_int, C.POINTER(AnalysisFrame)]),
+    "adas_analysis_fetch_points": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
     "adas_pipeline_request_transform": (C.c_int, [_P, C.c_int, C.c_int]),
     "adas_warp_create": (C.c_int, [C.POINTER(WarpParams), C.c_int, C.POINTER(_P)]),
     "adas_warp_destroy": (C.c_int, [_P]),

@@ -23,6 +23,7 @@ UNITS = [
     ("pre_kernels.hip", ["-ffp-contract=off"]),
     ("warp_kernels.hip", ["-ffp-contract=off"]),
     ("birdview_kernels.hip", ["-ffp-contract=off"]),
+    ("analysis_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

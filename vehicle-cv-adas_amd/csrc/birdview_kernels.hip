@@ -116,6 +116,7 @@ int birdview_capacity(const ::adas_birdview* h, int* n_streams, int* max_frames)
     if (max_frames) *max_frames = h->max_frames;
     return 1;
 }
+int* birdview_request_table(::adas_birdview* h) { return h ? h->dev.request : nullptr; }
 }  // namespace adas
 
 static int birdview_reset_streams(adas_birdview* h, int first, int count) {

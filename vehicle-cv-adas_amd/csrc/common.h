@@ -25,6 +25,7 @@ struct adas_ufld_decode;
 struct adas_lane_geometry;
 struct adas_birdview;
 struct adas_warp;
+struct adas_analysis;
 namespace adas {
 int handle_max_batch(const ::adas_yolo_post* h);
 int handle_max_batch(const ::adas_ufld_decode* h);
@@ -34,6 +35,12 @@ void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int**
 // what adas_pipeline_attach_birdview checks (birdview_kernels.hip, warp_kernels.hip); 0 for a null handle
 int birdview_capacity(const ::adas_birdview* h, int* n_streams, int* max_frames);
 int warp_geometry(const ::adas_warp* h, int* src_h, int* src_w, int* max_batch);
+// the bird view's pending-request table, [n_streams] words (birdview_kernels.hip): the analysis stage stores each stream's next request there
+int* birdview_request_table(::adas_birdview* h);
+// what adas_pipeline_attach_analysis checks and does (analysis_kernels.hip): the handle's capacity; bind = remember the bird view whose
+// requests the handle now owns and queue every stream's initial "Default" on hip_stream (bird may be null: unbind)
+int analysis_capacity(const ::adas_analysis* h, int* n_streams, int* max_frames);
+int analysis_bind_birdview(::adas_analysis* h, ::adas_birdview* bird, int n_streams, void* hip_stream);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

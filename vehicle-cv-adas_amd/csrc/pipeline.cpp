@@ -13,6 +13,8 @@ struct adas_pipeline {
     // optional stages behind the lane decode (adas_pipeline_attach_birdview): per-stream adaptive homographies, and the bird-view image
     adas_birdview* bird = nullptr;
     adas_warp* bird_warp = nullptr;
+    // optional last stage behind the join of the two branches (adas_pipeline_attach_analysis): distance, collision and warning state
+    adas_analysis* analysis = nullptr;
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -161,6 +163,10 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
         ADAS_HIP_TRY(hipEventRecord(p->ev_join, sl));
         ADAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
     }
+    if (p->analysis) {   // reads both branches' results; its request words meet the NEXT step's adas_birdview_run, ordered through that step's fork
+        rc = adas_analysis_run(p->analysis, p->d.post, p->d.geometry, p->bird, NS, B, st);
+        if (rc) return rc;
+    }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
     return ADAS_OK;
 }
@@ -276,15 +282,38 @@ int adas_pipeline_attach_birdview(adas_pipeline* p, adas_birdview* bird, adas_wa
         int rc = adas_warp_device_view(warp, &own);
         if (rc) return rc;
     }
+    ADAS_REQUIRE(!p->analysis || p->d.micro_batch <= 1, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_birdview: an analysis handle is attached and micro_batch is %d: a frame's request cannot reach the next frame "
+                 "inside one step", p->d.micro_batch);
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
     p->bird = bird;
     p->bird_warp = warp;
+    if (p->analysis) return adas::analysis_bind_birdview(p->analysis, bird, p->d.n_streams, p->st);
     return ADAS_OK;
+}
+
+int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis) {
+    ADAS_REQUIRE(p && analysis, ADAS_ERR_INVALID, "adas_pipeline_attach_analysis: bad argument");
+    ADAS_REQUIRE(p->d.detector && p->d.post && p->d.lane && p->d.decode && p->d.geometry, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_analysis: the pipeline needs a detector with its post handle and a lane engine with decode and geometry handles");
+    ADAS_REQUIRE(!p->bird || p->d.micro_batch <= 1, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_analysis: a bird-view handle is attached and micro_batch is %d: a frame's request cannot reach the next frame "
+                 "inside one step", p->d.micro_batch);
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int as = 0, af = 0;
+    (void)adas::analysis_capacity(analysis, &as, &af);
+    ADAS_REQUIRE(as >= p->d.n_streams && af >= frames, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_analysis: the handle holds %d streams / %d frames, a step has %d streams / %d frames", as, af, p->d.n_streams, frames);
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->analysis = analysis;
+    return adas::analysis_bind_birdview(analysis, p->bird, p->d.n_streams, p->st);
 }
 
 int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode) {
     ADAS_REQUIRE(p && p->bird, ADAS_ERR_INVALID, "adas_pipeline_request_transform: no bird-view handle attached");
+    ADAS_REQUIRE(!p->analysis, ADAS_ERR_INVALID, "adas_pipeline_request_transform: an analysis handle is attached, the device owns the requests");
     ADAS_REQUIRE(stream >= 0 && stream < p->d.n_streams, ADAS_ERR_INVALID, "adas_pipeline_request_transform: stream %d of %d", stream, p->d.n_streams);
     return adas_birdview_request(p->bird, stream, mode, p->st);   // ordered ahead of the next step on the pipeline's stream; no re-capture
 }
@@ -292,6 +321,7 @@ int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode) {
 int adas_pipeline_destroy(adas_pipeline* p) {
     if (!p) return ADAS_OK;
     drop_graphs(p);
+    if (p->analysis) (void)adas::analysis_bind_birdview(p->analysis, nullptr, 0, nullptr);   // its reset no longer queues on this pipeline's stream
     for (auto& e : p->ev)
         if (e) (void)hipEventDestroy(e);
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);

@@ -1250,6 +1250,14 @@ int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometr
     if (bird_points) memcpy(bird_points, h->h_msg + 12, 4 * ADAS_LANE_MAXPTS * 2 * 4);
     return ADAS_OK;
 }
+int adas_lane_geometry_device_views(adas_lane_geometry* h, const int32_t** d_header, const double** d_values, const int32_t** d_area, int32_t* area_stride) {
+    ADAS_REQUIRE(h && d_header && d_values && d_area && area_stride, ADAS_ERR_INVALID, "adas_lane_geometry_device_views: bad argument");
+    *d_header = h->dev.hdr;
+    *d_values = h->dev.vals;
+    *d_area = h->dev.area;
+    *area_stride = 4 * h->dev.cfg.img_h;
+    return ADAS_OK;
+}
 
 // ------------------------------------------------------------------------------- ByteTrack
 int adas_bytetrack_create(const adas_bytetrack_params* p, int n_streams, adas_bytetrack** out) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None):
+                 birdview=None, analysis=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -29,13 +29,18 @@ class AdasPipeline:
         birdview: None, or dict(image=bool): one adaptive bird-view trapezoid per stream on the device (postproc.BirdView with
         img_size = geometry["bird_wh"]); the geometry then reads every frame's own matrix, request_transform(stream, mode) re-anchors a
         stream on its next step, and with image=True step_frames also warps every frame into the bird view (birdview_image).
-        Needs geometry=; geometry["M"] is then only the handle's stand-alone matrix."""
+        Needs geometry=; geometry["M"] is then only the handle's stand-alone matrix.
+        analysis: None, or dict(class_names=[...], object_list=...): distance points, the collision point and the FCWS / LDWS / LKAS state
+        machine per stream as the step's last stage (postproc.Analysis; `.analysis.fetch_stream(s)` / `.fetch_frame(f)` after sync()).
+        class_names are the detector's labels by class id, object_list the measured ones (default: the reference's six); further keys go
+        to Analysis (ref_height=: the per-class table of inches itself, in place of the two label lists).  Needs det_model=, lane_model= and geometry=.  With birdview= the device then owns the
+        re-anchoring requests (request_transform raises) and micro_batch must be 1."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
-        self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = None
+        self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:
@@ -79,6 +84,14 @@ class AdasPipeline:
             if dict(birdview).get("image", False):
                 self.warp = PerspectiveWarp(src_hw, (bh, bw), n_streams)
             L.check(L.lib().adas_pipeline_attach_birdview(self.h, self.birdview.h, self.warp.h if self.warp else None))
+        if analysis is not None:
+            kw = dict(analysis)
+            if "class_names" not in kw and "ref_height" not in kw:
+                raise ValueError("analysis= needs class_names: the detector's label of every class id (or ref_height: the per-class table)")
+            kw.setdefault("max_points", min(int(max_candidates), 2048))
+            kw.setdefault("max_poly", 2 * int(src_hw[0]))
+            self.analysis = Analysis(n_streams=n_tracks, max_frames=n_streams, **kw)
+            L.check(L.lib().adas_pipeline_attach_analysis(self.h, self.analysis.h))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -143,7 +156,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

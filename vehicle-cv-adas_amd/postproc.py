@@ -291,6 +291,13 @@ class LaneGeometry:
         """run() with frame f reading its homography from the device table d_M_ptr [batch][9] (BirdView.device_views()[0])."""
         L.check(L.lib().adas_lane_geometry_run_matrices(self.h, decode.h, 1 if adjust_lanes else 0, batch, d_M_ptr, stream))
 
+    def device_views(self):
+        """(d_header, d_values, d_area, area_stride): per frame 8 int32 (area_status, n_left, n_right, direction, bird counts), 2 float64
+        (curvature, offset) and the area polygon at d_area + frame * area_stride int32."""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        L.check(L.lib().adas_lane_geometry_device_views(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return a.value, b.value, c.value, int(n.value)
+
     def fetch(self, frame=0):
         res = L.LaneGeometryResult()
         area = np.zeros((2 * self.img_h, 2), np.int32)
@@ -408,6 +415,122 @@ class BirdView:
     def close(self):
         if getattr(self, "h", None):
             L.lib().adas_birdview_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class Analysis:
+    """SingleCamDistanceMeasure + TaskConditions per video stream on the device (distanceMeasure.py:50-93, taskConditions.py:88-312;
+    demo.py:284-296): distance points, the collision point inside the ego-lane polygon, the three warning messages and the bird view's
+    re-anchoring toggle.  fetch_stream / fetch_frame return analysis.CollisionType / OffsetType / CurvatureType members and
+    "Default" | "Top" | "Bottom" | None."""
+    MODES = (None, "Default", "Top", "Bottom")
+    DIRECTIONS = (None, "L", "R", "F")
+    OBJECT_LIST = ("person", "bicycle", "car", "motorbike", "bus", "truck")     # SingleCamDistanceMeasure's default
+
+    def __init__(self, class_names=(), object_list=None, n_streams=1, max_frames=None, max_points=512, max_poly=1440, ref_height=None, **constants):
+        """class_names: the detector's label of every class id; object_list: the labels that are measured (default: the reference's six).
+        A class gets RefSizeDict[label][0] inches when its label is in both, else 0 (not measured); ref_height= gives that per-class table
+        directly instead.  constants: focal, y_limit, distance_thres, offset_thres, curvae_thres, calib_frequency, calib_curvae_thres."""
+        from . import analysis as A
+        self._A = A
+        self._collision = (A.CollisionType.UNKNOWN, A.CollisionType.NORMAL, A.CollisionType.PROMPT, A.CollisionType.WARNING)
+        self._offset = (A.OffsetType.UNKNOWN, A.OffsetType.RIGHT, A.OffsetType.LEFT, A.OffsetType.CENTER)
+        self._curvature = (A.CurvatureType.UNKNOWN, A.CurvatureType.STRAIGHT, A.CurvatureType.EASY_LEFT, A.CurvatureType.HARD_LEFT,
+                           A.CurvatureType.EASY_RIGHT, A.CurvatureType.HARD_RIGHT)
+        objects = list(self.OBJECT_LIST if object_list is None else object_list)
+        sizes = A.SingleCamDistanceMeasure.RefSizeDict
+        if ref_height is None:
+            ref_height = [float(sizes[n][0]) if (n in objects and n in sizes) else 0.0 for n in class_names]
+        self.ref_height = np.ascontiguousarray(ref_height, np.float64).reshape(-1)
+        p = L.AnalysisParams()
+        L.check(L.lib().adas_analysis_default_params(C.byref(p)))
+        for k, v in constants.items():
+            if not hasattr(p, k) or k in ("n_classes", "h_ref_height", "max_points", "max_poly"):
+                raise TypeError("unknown analysis constant %r" % k)
+            setattr(p, k, v)
+        p.n_classes, p.h_ref_height = len(self.ref_height), (self.ref_height.ctypes.data if len(self.ref_height) else None)
+        p.max_points, p.max_poly = int(max_points), int(max_poly)
+        self.n_streams, self.max_points = int(n_streams), int(max_points)
+        self.max_frames = int(max_frames) if max_frames else self.n_streams
+        h = C.c_void_p()
+        L.check(L.lib().adas_analysis_create(C.byref(p), self.n_streams, self.max_frames, C.byref(h)))
+        self.h = h.value
+
+    def run(self, post, geometry, birdview=None, n_streams=None, n_frames=1, stream=None):
+        """One launch on the handles' device arrays (YoloPost, LaneGeometry); with birdview= every stream's request lands in that BirdView's
+        pending table for its next run."""
+        L.check(L.lib().adas_analysis_run(self.h, post.h, geometry.h, birdview.h if birdview else None, int(n_streams or self.n_streams), int(n_frames),
+                                          stream))
+
+    def run_arrays(self, d_xyxy, d_cls, d_counts, det_stride, d_poly, poly_cap, d_poly_counts, d_geometry, d_request=None, n_streams=None, n_frames=1,
+                   stream=None):
+        """The same kernel on raw device pointers (adas_analysis_run_arrays)."""
+        L.check(L.lib().adas_analysis_run_arrays(self.h, d_xyxy, d_cls, d_counts, int(det_stride), d_poly, int(poly_cap), d_poly_counts, d_geometry,
+                                                 d_request, int(n_streams or self.n_streams), int(n_frames), stream))
+
+    @staticmethod
+    def make_inputs(frames):
+        """[(collision point or its metres or None, area_status, offset or None, direction "L" | "R" | "F" | None, curvature or None), ...] ->
+        the table run_inputs takes."""
+        t = np.zeros(len(frames), L.ANALYSIS_INPUT_DTYPE)
+        for r, (dist, area, off, direction, curv) in zip(t, frames):
+            if dist is not None:
+                r["has_point"], r["distance"] = 1, float(dist[2] if isinstance(dist, (list, tuple, np.ndarray)) else dist)
+            r["area"] = 1 if area else 0
+            if off is not None:
+                r["has_offset"], r["offset"] = 1, float(off)
+            if curv is not None:
+                r["has_curvature"], r["curvature"] = 1, float(curv)
+            r["direction"] = Analysis.DIRECTIONS.index(direction)
+        return t
+
+    def run_inputs(self, inputs, n_streams=None, n_frames=1, stream=None):
+        """The state machine alone: inputs = make_inputs(...) (or that dtype), frame b of stream s at b * n_streams + s."""
+        t = np.ascontiguousarray(inputs, L.ANALYSIS_INPUT_DTYPE)
+        ns = int(n_streams or self.n_streams)
+        if len(t) != ns * int(n_frames):
+            raise ValueError("%d inputs for %d streams x %d frames" % (len(t), ns, n_frames))
+        L.check(L.lib().adas_analysis_run_inputs(self.h, L.ptr(t), ns, int(n_frames), stream))
+
+    def fetch_stream(self, stream=0):
+        s = L.AnalysisState()
+        L.check(L.lib().adas_analysis_fetch_stream(self.h, int(stream), C.byref(s)))
+        nc = int(s.n_curvature)
+        return dict(collision_msg=self._collision[s.collision_msg], offset_msg=self._offset[s.offset_msg], curvature_msg=self._curvature[s.curvature_msg],
+                    toggle_status=self.MODES[s.toggle_status], transform_status=self.MODES[s.transform_status],
+                    toggle_oscillator_status=[bool(v) for v in s.oscillator],
+                    toggle_status_counter={"Offset": int(s.counter_offset), "Curvae": int(s.counter_curvae), "BirdViewAngle": int(s.counter_birdview)},
+                    vehicle_collision_record=[float(v) for v in s.collision_record[:s.n_collision]],
+                    vehicle_offset_record=[float(v) for v in s.offset_record[:s.n_offset]],
+                    vehicle_curvature_record=[[self.DIRECTIONS[s.direction_record[k]], float(s.curvature_record[k])] for k in range(nc)],
+                    n_nonfinite=int(s.n_nonfinite))
+
+    def fetch_frame(self, frame=0):
+        f = L.AnalysisFrame()
+        L.check(L.lib().adas_analysis_fetch_frame(self.h, int(frame), C.byref(f)))
+        return dict(n_points=int(f.n_points), collision_point=[int(f.collision_x), int(f.collision_y), float(f.collision_d)] if f.has_collision else None,
+                    collision_index=int(f.collision_index), collision_msg=self._collision[f.collision_msg], offset_msg=self._offset[f.offset_msg],
+                    curvature_msg=self._curvature[f.curvature_msg], toggle_status=self.MODES[f.toggle_status],
+                    transform_status=self.MODES[f.transform_status], toggle_oscillator_status=[bool(v) for v in f.oscillator],
+                    toggle_status_counter=dict(zip(("Offset", "Curvae", "BirdViewAngle"), (int(v) for v in f.counters))), check=bool(f.check),
+                    request=self.MODES[f.request], flags=int(f.flags))
+
+    def fetch_points(self, frame=0, n=None):
+        """distance_points of the frame as the reference lists them: [[x, y, metres], ...] in survivor order."""
+        if n is None:
+            n = self.fetch_frame(frame)["n_points"]
+        xy, d = np.zeros((n, 2), np.int32), np.zeros(n, np.float64)
+        L.check(L.lib().adas_analysis_fetch_points(self.h, int(frame), L.ptr(xy), L.ptr(d), int(n)))
+        return [[int(x), int(y), float(v)] for (x, y), v in zip(xy, d)]
+
+    def reset(self, stream=-1):
+        L.check(L.lib().adas_analysis_reset(self.h, int(stream)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_analysis_destroy(self.h)
             self.h = None
 
     __del__ = close
