@@ -638,6 +638,78 @@ int adas_analysis_fetch_frame(adas_analysis* h, int frame, adas_analysis_frame* 
  * ADAS_ERR_INVALID after adas_analysis_run_inputs (no points). */
 int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double* d, int n);
 
+/* -----------------------------------------------------------------------------------
+ * Lane overlay: the part of the reference's Draw* block (demo.py:300-305) that needs nothing but pixels, on frames that already sit
+ * in HBM -- UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame (ultrafastLaneDetectorV2.py:196-218, the same in v1), the
+ * discs of SingleCamDistanceMeasure.DrawDetectedOnFrame (distanceMeasure.py:98) and PerspectiveTransformation.DrawDetectedOnBirdView
+ * (perspectiveTransformation.py:217-226): two whole-frame cv2.addWeighted passes, a cv2.fillPoly and filled cv2.circles.
+ * NOT drawn: text (putText / getTextSize), thick lines (cornerRect, arrowedLine, trajectories) and the UI panels.
+ * The pixel rules are modelled on OpenCV 4.5's drawing.cpp / arithm and defined in csrc/overlay_core.h (restated in NumPy,
+ * tests/overlay_ref.py); parity with a real cv2 build is UNPINNED, and lines are not clipped before they are walked (OpenCV clips the
+ * segment first and restarts the error term).  Per frame f, S0 = the source frame:
+ *   1 LANES     lanes 0..3 in order, each point a disc of lane_radius in lane_colors[lane] -- offset_color for lane 1 when the frame's
+ *               offset type is RIGHT and for lane 2 when it is LEFT; the last disc over a pixel wins; S1 = blend(colour, lane_alpha, S0)
+ *               on disc pixels.  Every decoded point is drawn, detected lane or not.
+ *   2 AREA      if area_status and the polygon is not empty: S2 = blend(S1, area_alpha, area colour) on the polygon (edges + even-odd
+ *               interior).  A vertex with |x| or |y| > 32767 skips the frame's fill and sets ADAS_OVERLAY_POLY_RANGE in its flags.
+ *   3 DISTANCE  a disc of distance_radius in distance_color, written, at every distance point (needs an analysis handle).
+ *   4 BIRD      on the bird-view image, in place: discs of bird_radius at the geometry's bird points, lane order and colours of 1, written.
+ * With an analysis handle the offset type and the area colour (collision_colors[collision_msg]) are the frame's row after its three
+ * updates; without one the offset type is UNKNOWN and the colour is area_color.  The frame goes to a buffer of its own
+ * (frame_show = frame.copy()); every output byte depends on the same input byte and geometry only, so dst == src is legal.
+ * Three launches for the frame (coverage, one streaming pass with 16-byte accesses, coverage clean-up), two for the bird view; all plain:
+ * capturable.  Nothing is capped: lanes hold at most ADAS_UFLD_MAX_POINTS points, polygons and distance points as many as their sources.
+ * ----------------------------------------------------------------------------------- */
+typedef struct adas_overlay adas_overlay;
+typedef struct {
+    int32_t src_h, src_w;      /* frames: [frames][src_h][src_w][3] u8 BGR; the warp's limits (1..4320 rows, 1..16384 columns) */
+    int32_t bird_h, bird_w;    /* the bird-view image; 0, 0: no bird view */
+    int32_t lane_radius, distance_radius, bird_radius; /* 3, 4, 10; each 0..64 */
+    int32_t reserved;
+    double lane_alpha, area_alpha;  /* 0.3, 0.85 */
+    uint8_t lane_colors[4][3];      /* (255,0,0), (46,139,87), (50,205,50), (0,255,255): written to channels 0, 1, 2 as given */
+    uint8_t offset_color[3];        /* (0,0,255) */
+    uint8_t area_color[3];          /* DrawAreaOnFrame's default (255,191,0) */
+    uint8_t collision_colors[4][3]; /* CollisionDict (demo.py:33-38) by ADAS_COLLISION_*: (0,255,255), (0,255,0), (0,102,255), (0,0,255) */
+    uint8_t distance_color[3];      /* (255,255,255) */
+    uint8_t pad[7];
+} adas_overlay_params;
+#define ADAS_OVERLAY_LANES 1
+#define ADAS_OVERLAY_AREA 2
+#define ADAS_OVERLAY_DISTANCE 4
+#define ADAS_OVERLAY_BIRD 8
+#define ADAS_OVERLAY_POLY_RANGE 1 /* frame flags: a polygon vertex outside +-32767, the frame's fill was skipped */
+/* The reference's radii, alphas and colours; the four sizes are 0. */
+int adas_overlay_default_params(adas_overlay_params* p);
+/* max_batch frames per run.  Allocates the coverage planes (src_h x src_w / 8 bytes per frame, plus a detail plane of src_h x src_w
+ * bytes that is read only where something is drawn; the same for the bird view). */
+int adas_overlay_create(const adas_overlay_params* p, int max_batch, adas_overlay** out);
+int adas_overlay_destroy(adas_overlay* h);
+/* Radii, alphas and colours of `p` replace the handle's (its sizes are ignored); takes effect with the next run, and a captured
+ * pipeline step is re-captured. */
+int adas_overlay_set_style(adas_overlay* h, const adas_overlay_params* p);
+/* Frames [0, n_streams * n_frames) of d_src_bgr -> d_dst_bgr (NULL: the handle's own buffer; d_src_bgr itself: in place) with the stages
+ * of `stages` drawn from the handles' device arrays; frame b of stream s is frame b * n_streams + s of every handle.  LANES needs
+ * `decode` (4 lanes: a decoder with num_lanes != 4 is ADAS_ERR_INVALID), AREA and BIRD need `geometry`, DISTANCE needs `analysis`,
+ * BIRD needs d_bird_bgr ([frames][bird_h][bird_w][3], drawn in place).  With stages & 7 == 0 no frame is written.  Asynchronous. */
+int adas_overlay_run(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
+                     adas_analysis* analysis, uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream);
+/* The same kernels on raw device arrays, any of which may be NULL with its stage off: d_lane_points [frames][4][ADAS_UFLD_MAX_POINTS][2]
+ * int32 (x, y) + d_lane_counts [frames][4]; d_poly [frames][poly_cap][2] + d_poly_counts [frames] + d_area_status [frames];
+ * d_offset_type [frames] (ADAS_OFFSET_*; NULL: UNKNOWN); d_area_bgr [frames][3] u8 (NULL: area_color); d_dist_points [frames][dist_cap][2]
+ * + d_dist_counts [frames]; d_bird_points [frames][4][ADAS_UFLD_MAX_POINTS][2] + d_bird_counts [frames][4]. */
+int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points, const int32_t* d_lane_counts,
+                            const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
+                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
+                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
+                            int n_frames, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_bgr [src_h][src_w][3], after the last run's stream has drained.  A frame that no run
+ * has written is ADAS_ERR_INVALID. */
+int adas_overlay_fetch(adas_overlay* h, int frame, uint8_t* h_bgr);
+int adas_overlay_device_view(adas_overlay* h, const uint8_t** d_bgr);
+/* ADAS_OVERLAY_* flags of frame `frame` of the last run.  Synchronises. */
+int adas_overlay_fetch_flags(adas_overlay* h, int frame, int32_t* flags);
+
 /* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
@@ -750,6 +822,19 @@ int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode);
  * graphs are dropped).  Without it the step, its graph and its launch count are unchanged.  The handle stays the caller's and must outlive
  * the pipeline. */
 int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis);
+/* Optional drawing stage, last on the pipeline's main stream (behind adas_analysis_run, or behind the join of the two branches when no
+ * analysis handle is attached) and inside the capture: adas_overlay_run from the step's u8 frames into the overlay handle's own buffer
+ * (adas_overlay_fetch), with the attached analysis handle if there is one.  Needs a lane engine with decode (4 lanes) and geometry
+ * handles.  The stages drawn are LANES and AREA, DISTANCE when an analysis handle is attached by the time of the step, and BIRD when a
+ * bird view with its warp is (the discs land on the warp handle's own buffer, behind adas_warp_run_device_matrices; the overlay's bird
+ * size must then be the warp's destination size); adas_pipeline_set_overlay_stages narrows them.  The overlay handle must hold
+ * n_streams x micro_batch frames and the step's camera geometry as its source size.  With an overlay attached the seam-tensor step is
+ * ADAS_ERR_INVALID (no frame to draw on).  Call before the first step (cached graphs are dropped).  Without it the step, its graph and
+ * its launch count are unchanged.  The handle stays the caller's. */
+int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay);
+/* The stages (ADAS_OVERLAY_*) the attached overlay draws; one that lacks its handle (DISTANCE without an analysis handle, BIRD without a
+ * warp) is ADAS_ERR_INVALID at the step.  Cached graphs are dropped. */
+int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);
 /* The same step from camera frames: n_streams BGR u8 frames (src_h x src_w x 3, back to back) in HBM; each branch runs its

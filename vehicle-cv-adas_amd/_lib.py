@@ -113,6 +113,18 @@ ANALYSIS_INPUT_DTYPE = np.dtype([("has_point", "i4"), ("area", "i4"), ("has_offs
 ANALYSIS_OVERFLOW, ANALYSIS_NONFINITE, ANALYSIS_TRUNCATED = 1, 2, 4     # adas_analysis_frame.flags
 
 
+class OverlayParams(C.Structure):
+    _fields_ = [("src_h", C.c_int32), ("src_w", C.c_int32), ("bird_h", C.c_int32), ("bird_w", C.c_int32), ("lane_radius", C.c_int32),
+                ("distance_radius", C.c_int32), ("bird_radius", C.c_int32), ("reserved", C.c_int32), ("lane_alpha", C.c_double),
+                ("area_alpha", C.c_double), ("lane_colors", (C.c_uint8 * 3) * 4), ("offset_color", C.c_uint8 * 3), ("area_color", C.c_uint8 * 3),
+                ("collision_colors", (C.c_uint8 * 3) * 4), ("distance_color", C.c_uint8 * 3), ("pad", C.c_uint8 * 7)]
+
+
+OVERLAY_LANES, OVERLAY_AREA, OVERLAY_DISTANCE, OVERLAY_BIRD = 1, 2, 4, 8     # adas_overlay_run's stages
+OVERLAY_STAGES = {"lanes": OVERLAY_LANES, "area": OVERLAY_AREA, "distance": OVERLAY_DISTANCE, "bird": OVERLAY_BIRD}
+OVERLAY_POLY_RANGE = 1                                                       # adas_overlay_fetch_flags
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -265,6 +277,17 @@ _SIGS = {
     "adas_analysis_fetch_frame": (C.c_int, [_P, C.c_int, C.POINTER(AnalysisFrame)]),
     "adas_analysis_fetch_points": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
     "adas_pipeline_request_transform": (C.c_int, [_P, C.c_int, C.c_int]),
+    "adas_overlay_default_params": (C.c_int, [C.POINTER(OverlayParams)]),
+    "adas_overlay_create": (C.c_int, [C.POINTER(OverlayParams), C.c_int, C.POINTER(_P)]),
+    "adas_overlay_destroy": (C.c_int, [_P]),
+    "adas_overlay_set_style": (C.c_int, [_P, C.POINTER(OverlayParams)]),
+    "adas_overlay_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_arrays": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_overlay_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_overlay_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_overlay_fetch_flags": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "adas_pipeline_attach_overlay": (C.c_int, [_P, _P]),
+    "adas_pipeline_set_overlay_stages": (C.c_int, [_P, C.c_int]),
     "adas_warp_create": (C.c_int, [C.POINTER(WarpParams), C.c_int, C.POINTER(_P)]),
     "adas_warp_destroy": (C.c_int, [_P]),
     "adas_warp_set_matrix": (C.c_int, [_P, C.c_int, _P, C.c_int]),

@@ -10,8 +10,9 @@ They take what `detectors.py` produces (RectInfo list, LaneInfo) -- a few hundre
 run on the host: after GPU-resident decode/NMS/tracking this is per-frame scalar bookkeeping (<0.2 ms), not a kernel.
 The one per-pixel step, transformToBirdView / transformToFrontalView (cv2.warpPerspective of the whole frame, :89-117), runs on
 the device (csrc/warp_kernels.hip); the library is imported when one of the two is first called, so this module and everything
-else in it work without it.  Same public names and call shapes as the reference so demo.py:284-296 reads unchanged; every
-Draw* method is out of scope (cv2).
+else in it work without it.  Same public names and call shapes as the reference so demo.py:284-296 reads unchanged.  Of the
+Draw* methods, PerspectiveTransformation.DrawDetectedOnBirdView (filled discs) runs on the device (csrc/overlay_kernels.hip); the ones
+that draw text, thick lines or arrows stay out of scope (cv2).
 
 Third-party arithmetic restated here (parity UNPINNED against real OpenCV, cv2 is absent): `perspective_matrix`
 (cv2.getPerspectiveTransform: the 8x8 linear system of the four point pairs, solved in float64) and `point_in_polygon`
@@ -206,9 +207,21 @@ class PerspectiveTransformation:
         """Bird-view image -> frontal-view image of img_size (:106-117)."""
         return self._warp_image(img, self.M_inv, flags)
 
+    def DrawDetectedOnBirdView(self, image, lanes_points, type=None) -> None:
+        """perspectiveTransformation.py:217-226: a filled disc of radius 10 at every (int(x), int(y)) of lanes_points, lane by lane in
+        lane_colors (lane 1 red when `type` is OffsetType.RIGHT, lane 2 when LEFT), written in place.  image: HxWx3 uint8 ndarray or a
+        StagedFrame.  On the device (postproc.LaneOverlay); OpenCV's disc restated, parity unpinned."""
+        from . import postproc            # lazy, as the warp
+        if getattr(self, "_painter", None) is None:
+            self._painter = postproc.OverlayPainter()
+        self._painter.lanes(image, lanes_points, type, bird=True)
+
     def close(self):
         """Releases the device warp handle and the frame buffer the two image methods created (they are created again on the next call).
         A no-op when neither method has been called."""
+        if getattr(self, "_painter", None) is not None:
+            self._painter.close()
+            self._painter = None
         if self._warp is not None:
             self._warp.close()
         if self._warp_src is not None:

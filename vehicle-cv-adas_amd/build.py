@@ -24,6 +24,7 @@ UNITS = [
     ("warp_kernels.hip", ["-ffp-contract=off"]),
     ("birdview_kernels.hip", ["-ffp-contract=off"]),
     ("analysis_kernels.hip", ["-ffp-contract=off"]),
+    ("overlay_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

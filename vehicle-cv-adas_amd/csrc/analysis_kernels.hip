@@ -187,6 +187,12 @@ int analysis_capacity(const ::adas_analysis* h, int* n_streams, int* max_frames)
     if (max_frames) *max_frames = h->max_frames;
     return 1;
 }
+void analysis_frame_views(const ::adas_analysis* h, const int** frames, int* stride, const int** pts_xy, int* max_points) {
+    *frames = (const int*)h->dev.frames;
+    *stride = (int)(sizeof(AnalysisFrame) / 4);
+    *pts_xy = h->dev.pts_xy;
+    *max_points = h->dev.max_points;
+}
 int analysis_bind_birdview(::adas_analysis* h, ::adas_birdview* bird, int n_streams, void* hip_stream) {
     h->bird = bird;
     h->bird_stream = (hipStream_t)hip_stream;

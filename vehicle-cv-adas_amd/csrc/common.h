@@ -42,6 +42,16 @@ int* birdview_request_table(::adas_birdview* h);
 int analysis_capacity(const ::adas_analysis* h, int* n_streams, int* max_frames);
 int analysis_bind_birdview(::adas_analysis* h, ::adas_birdview* bird, int n_streams, void* hip_stream);
 }  // namespace adas
+// what the overlay stage reads of the other handles (overlay_kernels.hip) and what adas_pipeline_attach_overlay checks
+struct adas_overlay;
+namespace adas {
+int decode_num_lanes(const ::adas_ufld_decode* h);                       // lanes of the decoded tensors (4 for UFLD v1)
+const int* geometry_bird_points(const ::adas_lane_geometry* h);         // [B][4][128][2]; the counts are header words 4..7
+// the analysis handle's frame records (int32 words, `stride` words apart) and distance points [max_frames][max_points][2]
+void analysis_frame_views(const ::adas_analysis* h, const int** frames, int* stride, const int** pts_xy, int* max_points);
+void warp_dst_geometry(const ::adas_warp* h, int* dst_h, int* dst_w);
+int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_h, int* bird_w, int* max_batch);
+}  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \
     do {                                                                        \

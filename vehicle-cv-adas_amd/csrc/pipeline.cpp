@@ -15,6 +15,9 @@ struct adas_pipeline {
     adas_warp* bird_warp = nullptr;
     // optional last stage behind the join of the two branches (adas_pipeline_attach_analysis): distance, collision and warning state
     adas_analysis* analysis = nullptr;
+    // optional drawing stage behind it (adas_pipeline_attach_overlay): discs, area polygon and alpha blends into the overlay handle's buffer
+    adas_overlay* overlay = nullptr;
+    int overlay_stages = -1;   // ADAS_OVERLAY_*; -1: everything the attached handles allow
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -167,6 +170,26 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
         rc = adas_analysis_run(p->analysis, p->d.post, p->d.geometry, p->bird, NS, B, st);
         if (rc) return rc;
     }
+    if (p->overlay) {   // behind the join: the lane branch's points, polygon and warped bird view, and this frame's analysis row, are all there
+        ADAS_REQUIRE(p->fsrc.frames, ADAS_ERR_INVALID, "the overlay needs camera frames: use adas_pipeline_step_frames");
+        int stages = p->overlay_stages;
+        if (stages < 0)
+            stages = ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | (p->analysis ? ADAS_OVERLAY_DISTANCE : 0) | (p->bird_warp ? ADAS_OVERLAY_BIRD : 0);
+        ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || p->analysis, ADAS_ERR_INVALID, "the overlay's distance stage needs an attached analysis handle");
+        ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || p->bird_warp, ADAS_ERR_INVALID, "the overlay's bird stage needs an attached bird view with its warp");
+        const uint8_t* bird_img = nullptr;
+        if (stages & ADAS_OVERLAY_BIRD) {
+            int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0, wh = 0, ww = 0;
+            (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
+            adas::warp_dst_geometry(p->bird_warp, &wh, &ww);
+            ADAS_REQUIRE(obh == wh && obw == ww, ADAS_ERR_INVALID, "the overlay handle was created for a %dx%d bird view, the attached warp writes %dx%d", obh, obw,
+                         wh, ww);
+            rc = adas_warp_device_view(p->bird_warp, &bird_img);
+            if (rc) return rc;
+        }
+        rc = adas_overlay_run(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, const_cast<uint8_t*>(bird_img), stages, NS, B, st);
+        if (rc) return rc;
+    }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
     return ADAS_OK;
 }
@@ -311,6 +334,42 @@ int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis) {
     return adas::analysis_bind_birdview(analysis, p->bird, p->d.n_streams, p->st);
 }
 
+int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
+    ADAS_REQUIRE(p && overlay, ADAS_ERR_INVALID, "adas_pipeline_attach_overlay: bad argument");
+    ADAS_REQUIRE(p->d.lane && p->d.decode && p->d.geometry, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_overlay: the pipeline needs a lane engine, a decode handle and a geometry handle");
+    ADAS_REQUIRE(adas::decode_num_lanes(p->d.decode) == 4, ADAS_ERR_INVALID,
+                 "adas_pipeline_attach_overlay: the decoder has num_lanes = %d (CurveLanes); the overlay draws the reference's four lane colours, num_lanes "
+                 "must be 4", adas::decode_num_lanes(p->d.decode));
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0;
+    (void)adas::overlay_geometry(overlay, &oh, &ow, &obh, &obw, &ob);
+    ADAS_REQUIRE(ob >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_overlay: the overlay handle holds %d frames, a step has %d", ob, frames);
+    if (p->bird_warp && obh > 0) {
+        int wh = 0, ww = 0;
+        adas::warp_dst_geometry(p->bird_warp, &wh, &ww);
+        ADAS_REQUIRE(obh == wh && obw == ww, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_overlay: the overlay handle was created for a %dx%d bird view, the attached warp writes %dx%d", obh, obw, wh, ww);
+    }
+    const uint8_t* own = nullptr;   // its buffer exists before the first (captured) step
+    int rc = adas_overlay_device_view(overlay, &own);
+    if (rc) return rc;
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->overlay = overlay;
+    p->overlay_stages = -1;
+    return ADAS_OK;
+}
+
+int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
+    ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: no overlay handle attached");
+    ADAS_REQUIRE(stages >= 0 && !(stages & ~15), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: unknown stage bits 0x%x", stages);
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->overlay_stages = stages;
+    return ADAS_OK;
+}
+
 int adas_pipeline_request_transform(adas_pipeline* p, int stream, int mode) {
     ADAS_REQUIRE(p && p->bird, ADAS_ERR_INVALID, "adas_pipeline_request_transform: no bird-view handle attached");
     ADAS_REQUIRE(!p->analysis, ADAS_ERR_INVALID, "adas_pipeline_request_transform: an analysis handle is attached, the device owns the requests");
@@ -391,6 +450,7 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
     ADAS_REQUIRE(!p->d.detector || d_det, ADAS_ERR_INVALID, "detector input missing");
     ADAS_REQUIRE(!p->d.lane || d_lane, ADAS_ERR_INVALID, "lane input missing");
     ADAS_REQUIRE(!p->bird_warp, ADAS_ERR_INVALID, "a bird-view image warp is attached: seam tensors carry no frame to warp, use adas_pipeline_step_frames");
+    ADAS_REQUIRE(!p->overlay, ADAS_ERR_INVALID, "an overlay is attached: seam tensors carry no frame to draw on, use adas_pipeline_step_frames");
     if (!(p->d.use_graph & 1)) {
         p->timed = true;
         return record_step(p, d_det, d_lane, true);
@@ -406,6 +466,12 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
         (void)adas::warp_geometry(p->bird_warp, &sh, &sw, &wb);
         ADAS_REQUIRE(sh == src_h && sw == src_w, ADAS_ERR_INVALID, "the attached warp handle was created for %dx%d source frames, the step has %dx%d", sh, sw,
                      src_h, src_w);
+    }
+    if (p->overlay) {   // so does the overlay
+        int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0;
+        (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
+        ADAS_REQUIRE(oh == src_h && ow == src_w, ADAS_ERR_INVALID, "the attached overlay handle was created for %dx%d frames, the step has %dx%d", oh, ow, src_h,
+                     src_w);
     }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
     if (!p->det_in && !p->lane_in) {

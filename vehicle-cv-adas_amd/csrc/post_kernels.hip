@@ -512,6 +512,8 @@ namespace adas {
 int handle_max_batch(const ::adas_yolo_post* h) { return h ? h->max_batch : 0; }
 int handle_max_batch(const ::adas_ufld_decode* h) { return h ? h->max_batch : 0; }
 int handle_max_batch(const ::adas_lane_geometry* h) { return h ? h->max_batch : 0; }
+int decode_num_lanes(const ::adas_ufld_decode* h) { return !h ? 0 : (h->v1 ? 4 : h->p.num_lanes); }
+const int* geometry_bird_points(const ::adas_lane_geometry* h) { return h->dev.bird; }
 void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int** det, const int** pts) {
     *cnt = h->dev.lane_cnt;
     *det = h->dev.lane_det;

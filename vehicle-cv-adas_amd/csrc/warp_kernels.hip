@@ -111,6 +111,10 @@ int warp_geometry(const ::adas_warp* h, int* src_h, int* src_w, int* max_batch) 
     *max_batch = h->max_batch;
     return 1;
 }
+void warp_dst_geometry(const ::adas_warp* h, int* dst_h, int* dst_w) {
+    *dst_h = h->p.dst_h;
+    *dst_w = h->p.dst_w;
+}
 }  // namespace adas
 
 // frames [0, batch) of src through matrices M [batch][9] (device, destination -> source) into dst, or the handle's own buffer

@@ -10,7 +10,9 @@ Same public surface (`_defaults` / `set_defaults`, `DetectFrame(frame)`, `.objec
 `update(bboxes, scores, class_ids, frame)`, `reset()`), but a frame makes one trip to the GPU: the BGR u8
 frame is uploaded, letterbox/normalise (pre_kernels.hip), the network (MFMA conv engine), decode + NMS /
 lane decode (post_kernels.hip) all run in HBM, and only the survivors (<= 2 KB) come back.
-Drawing (`Draw*OnFrame`) and everything cv2 is out of scope.
+Of the reference's drawing, the lane detectors' `DrawDetectedOnFrame` / `DrawAreaOnFrame` run on the device (csrc/overlay_kernels.hip:
+filled discs, the ego-lane polygon and the alpha blends, restated from OpenCV 4.5 with parity unpinned); text, thick lines, arrows,
+trajectories, the UI panels and everything else cv2 stay out of scope.
 
 What stays on the host is what the reference keeps there and SURVEY 8a marks "host": RectInfo construction and
 LaneDetectBase.__update_lanes_status/__update_lanes_area (core.py:102-158: ego-lane polyfit, <1 ms).
@@ -27,7 +29,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import OnnxEngine, TensorRTEngine, EfficientdetEngine
-from .postproc import YoloPost, EffdetPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, letterbox
+from .postproc import YoloPost, EffdetPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, OverlayPainter, letterbox
 
 
 class ObjectModelType(Enum):       # ObjectDetector/utils.py:15-23
@@ -590,7 +592,28 @@ class UltrafastLaneDetectorV2(_Defaults):
                 l, r = lanes_points[index - 1], lanes_points[index]
             self.lane_info._area_points = np.vstack((l, np.flipud(r)))
 
+    # ---- drawing: the reference's two methods on the device (postproc.LaneOverlay), in place on `image` as the reference writes image[:]
+    def DrawDetectedOnFrame(self, image, type=None, alpha: float = 0.3) -> None:
+        """ultrafastLaneDetectorV2.py:196-209: a disc of radius 3 on every point of lane_info.lanes_points, lane by lane in lane_colors
+        (lane 1 red when `type` is OffsetType.RIGHT, lane 2 when LEFT), blended over the image at `alpha`.  image: HxWx3 uint8 ndarray
+        (written in place) or a StagedFrame (drawn where it sits in HBM)."""
+        if getattr(self, "_painter", None) is None:
+            self._painter = OverlayPainter()
+        self._painter.lanes(image, self.lane_info.lanes_points, type, alpha)
+
+    def DrawAreaOnFrame(self, image, color: tuple = (255, 191, 0), alpha: float = 0.85) -> None:
+        """ultrafastLaneDetectorV2.py:211-218: lane_info.area_points filled (cv2.fillPoly) in `color` and blended at `alpha`, when
+        lane_info.area_status."""
+        if not self.lane_info.area_status:
+            return
+        if getattr(self, "_painter", None) is None:
+            self._painter = OverlayPainter()
+        self._painter.area(image, self.lane_info.area_points, color, alpha)
+
     def close(self):
+        if getattr(self, "_painter", None) is not None:
+            self._painter.close()
+            self._painter = None
         if getattr(self, "_geometry", None) is not None:
             self._geometry.close()
             self._geometry = None

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None):
+                 birdview=None, analysis=None, overlay=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -34,13 +34,28 @@ class AdasPipeline:
         machine per stream as the step's last stage (postproc.Analysis; `.analysis.fetch_stream(s)` / `.fetch_frame(f)` after sync()).
         class_names are the detector's labels by class id, object_list the measured ones (default: the reference's six); further keys go
         to Analysis (ref_height=: the per-class table of inches itself, in place of the two label lists).  Needs det_model=, lane_model= and geometry=.  With birdview= the device then owns the
-        re-anchoring requests (request_transform raises) and micro_batch must be 1."""
+        re-anchoring requests (request_transform raises) and micro_batch must be 1.
+        overlay: None, or dict(stages=("lanes", "area", "distance", "bird") or a subset / mask, plus LaneOverlay's style keys): the lane
+        overlay as the step's very last stage, drawn from step_frames' frames into a buffer of its own (overlay_image(frame) after sync()):
+        lane-point discs and the ego-lane polygon alpha-blended, distance-point discs, and the discs on the bird-view image -- no text, thick
+        lines, arrows, trajectories or panels.  Needs lane_model= and geometry=; the distance stage needs analysis=, the bird stage
+        birdview=dict(image=True).  stages=None: every stage the pipeline has the handles for."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
+        self.overlay = None
+        if overlay is not None:
+            if geometry is None or not lane_model:
+                raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
+            ov_stages = dict(overlay).get("stages")
+            ov_mask = None if ov_stages is None else LaneOverlay.stage_mask(ov_stages)
+            if ov_mask is not None and ov_mask & L.OVERLAY_DISTANCE and analysis is None:
+                raise ValueError("the overlay's distance stage needs analysis= (the distance points it draws)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_BIRD and not (birdview is not None and dict(birdview).get("image", False)):
+                raise ValueError("the overlay's bird stage needs birdview=dict(image=True) (the bird-view image it draws on)")
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:
@@ -92,6 +107,12 @@ class AdasPipeline:
             kw.setdefault("max_poly", 2 * int(src_hw[0]))
             self.analysis = Analysis(n_streams=n_tracks, max_frames=n_streams, **kw)
             L.check(L.lib().adas_pipeline_attach_analysis(self.h, self.analysis.h))
+        if overlay is not None:
+            style = {k: v for k, v in dict(overlay).items() if k != "stages"}
+            self.overlay = LaneOverlay(src_hw, self.warp.dst_hw if self.warp else None, n_streams, **style)
+            L.check(L.lib().adas_pipeline_attach_overlay(self.h, self.overlay.h))
+            if ov_mask is not None:
+                L.check(L.lib().adas_pipeline_set_overlay_stages(self.h, ov_mask))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -133,6 +154,12 @@ class AdasPipeline:
             raise ValueError("the pipeline was created without birdview=dict(image=True)")
         return self.warp.fetch(frame)
 
+    def overlay_image(self, frame=0):
+        """frame_show of frame `frame` of the last step_frames (after sync()): (src_h, src_w, 3) uint8, the frame with the overlay drawn."""
+        if self.overlay is None:
+            raise ValueError("the pipeline was created without overlay=")
+        return self.overlay.fetch(frame)
+
     def wait_upload(self):
         """Block until the last step_frames_host upload has read its host buffer (then the buffer may be refilled)."""
         L.check(L.lib().adas_pipeline_wait_upload(self.h))
@@ -156,7 +183,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

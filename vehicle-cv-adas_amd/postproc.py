@@ -536,6 +536,198 @@ class Analysis:
     __del__ = close
 
 
+class LaneOverlay:
+    """The pixel part of the reference's Draw* block on frames resident in HBM (adas_overlay_*): discs of radius 3 on every lane point
+    blended at alpha 0.3 (UltrafastLaneDetectorV2.DrawDetectedOnFrame), the ego-lane polygon blended at 0.85 (DrawAreaOnFrame), white
+    discs of radius 4 on the distance points (SingleCamDistanceMeasure.DrawDetectedOnFrame) and discs of radius 10 on the bird-view
+    image (PerspectiveTransformation.DrawDetectedOnBirdView).  Text, thick lines, arrows, trajectories and the UI panels are not drawn.
+    The pixel rules are csrc/overlay_core.h (modelled on OpenCV 4.5; parity with a real cv2 build is unpinned, lines are not clipped
+    before they are walked)."""
+    STAGES = L.OVERLAY_STAGES
+
+    def __init__(self, src_hw, bird_hw=None, max_batch=1, **style):
+        """style: lane_radius, distance_radius, bird_radius, lane_alpha, area_alpha, lane_colors (4 BGR tuples), offset_color,
+        area_color, collision_colors (4), distance_color."""
+        self.p = L.OverlayParams()
+        L.check(L.lib().adas_overlay_default_params(C.byref(self.p)))
+        self.p.src_h, self.p.src_w = int(src_hw[0]), int(src_hw[1])
+        if bird_hw is not None:
+            self.p.bird_h, self.p.bird_w = int(bird_hw[0]), int(bird_hw[1])
+        self._apply(style)
+        self.src_hw, self.bird_hw, self.max_batch = (self.p.src_h, self.p.src_w), (self.p.bird_h, self.p.bird_w), int(max_batch)
+        h = C.c_void_p()
+        L.check(L.lib().adas_overlay_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+
+    def _apply(self, style):
+        for k, v in style.items():
+            if k in ("lane_colors", "collision_colors"):
+                for i, c in enumerate(v):
+                    for j in range(3):
+                        getattr(self.p, k)[i][j] = int(c[j])
+            elif k in ("offset_color", "area_color", "distance_color"):
+                for j in range(3):
+                    getattr(self.p, k)[j] = int(v[j])
+            elif k in ("lane_radius", "distance_radius", "bird_radius", "lane_alpha", "area_alpha"):
+                setattr(self.p, k, v)
+            else:
+                raise TypeError("unknown overlay style %r" % k)
+
+    @classmethod
+    def stage_mask(cls, stages):
+        """An int, or names out of "lanes", "area", "distance", "bird"."""
+        if isinstance(stages, int):
+            return stages
+        names = [stages] if isinstance(stages, str) else list(stages)
+        for n in names:
+            if n not in cls.STAGES:
+                raise ValueError("unknown overlay stage %r (one of %s)" % (n, ", ".join(cls.STAGES)))
+        m = 0
+        for n in names:
+            m |= cls.STAGES[n]
+        return m
+
+    def set_style(self, **style):
+        """Radii, alphas and colours from the next run on."""
+        self._apply(style)
+        L.check(L.lib().adas_overlay_set_style(self.h, C.byref(self.p)))
+
+    def run(self, src_ptr, decode=None, geometry=None, analysis=None, bird_ptr=None, stages=None, n_streams=1, n_frames=1, dst_ptr=None, stream=None):
+        """Frames [0, n_streams * n_frames) of the device pointer src_ptr -> dst_ptr (None: the handle's own buffer; src_ptr: in place), drawn
+        from the handles' device arrays (UfldDecode / Ufld1Decode, LaneGeometry, Analysis).  stages=None: every stage whose handle is given."""
+        if stages is None:
+            stages = ((L.OVERLAY_LANES if decode else 0) | (L.OVERLAY_AREA if geometry else 0) | (L.OVERLAY_DISTANCE if analysis else 0) |
+                      (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0))
+        L.check(L.lib().adas_overlay_run(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
+                                         analysis.h if analysis else None, bird_ptr, self.stage_mask(stages), int(n_streams), int(n_frames), stream))
+
+    def run_arrays(self, src_ptr, n_frames=1, lane_points=None, lane_counts=None, poly=None, poly_cap=0, poly_counts=None, area_status=None,
+                   offset_type=None, area_bgr=None, dist_points=None, dist_cap=0, dist_counts=None, bird_points=None, bird_counts=None,
+                   bird_ptr=None, stages=None, dst_ptr=None, stream=None):
+        """The same kernels on raw device pointers (adas_overlay_run_arrays).  stages=None: every stage whose arrays are given."""
+        if stages is None:
+            stages = ((L.OVERLAY_LANES if lane_points else 0) | (L.OVERLAY_AREA if poly else 0) | (L.OVERLAY_DISTANCE if dist_points else 0) |
+                      (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0))
+        L.check(L.lib().adas_overlay_run_arrays(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
+                                                offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts, bird_ptr,
+                                                self.stage_mask(stages), int(n_frames), stream))
+
+    def fetch(self, frame=0):
+        out = np.empty((self.src_hw[0], self.src_hw[1], 3), np.uint8)
+        L.check(L.lib().adas_overlay_fetch(self.h, int(frame), L.ptr(out)))
+        return out
+
+    def device_view(self):
+        p = C.c_void_p()
+        L.check(L.lib().adas_overlay_device_view(self.h, C.byref(p)))
+        return p.value
+
+    def flags(self, frame=0):
+        """ADAS_OVERLAY_* flags of the frame in the last run (L.OVERLAY_POLY_RANGE: a polygon vertex outside +-32767, the fill was skipped)."""
+        f = C.c_int32()
+        L.check(L.lib().adas_overlay_fetch_flags(self.h, int(frame), C.byref(f)))
+        return int(f.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_overlay_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class OverlayPainter:
+    """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
+    analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
+    An ndarray is uploaded, drawn in place on the device and copied back into image[:]; a StagedFrame is drawn where it sits."""
+    OFFSETS = {"UNKNOWN": 0, "RIGHT": 1, "LEFT": 2, "CENTER": 3}
+
+    def __init__(self):
+        self.ov = None
+        self.key = None
+        self.buf = None
+
+    def _target(self, image):
+        staged = hasattr(image, "ptr") and not isinstance(image, np.ndarray)
+        if staged:
+            hw = (int(image.height), int(image.width))
+        else:
+            if not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3):
+                raise Exception("image must be an HxWx3 uint8 BGR ndarray (or a StagedFrame), got %r" % (getattr(image, "shape", image),))
+            hw = (int(image.shape[0]), int(image.shape[1]))
+        if self.key != hw:
+            if self.ov is not None:
+                self.ov.close()
+            self.ov = LaneOverlay(hw, hw, 1)
+            self.key = hw
+        if staged:
+            return image.ptr, None
+        n = hw[0] * hw[1] * 3
+        if self.buf is None or self.buf.nbytes < n:
+            if self.buf is not None:
+                self.buf.free()
+            self.buf = L.DeviceBuffer(n)
+        self.buf.upload(image)
+        return self.buf.ptr, image
+
+    def _finish(self, ptr, image):
+        if image is not None:
+            image[:] = self.buf.download(image.shape, np.uint8)
+        else:
+            L.check(L.lib().adas_synchronize())     # the caller's staged frame is drawn when the method returns
+
+    @classmethod
+    def _offset(cls, type):
+        return cls.OFFSETS.get(getattr(type, "name", type), 0) if not isinstance(type, int) else int(type)
+
+    @staticmethod
+    def _lane_table(lanes_points):
+        pts, cnt = np.zeros((4, L.UFLD_MAX_POINTS, 2), np.int32), np.zeros(4, np.int32)
+        for l, lane in enumerate(list(lanes_points)[:4]):
+            a = np.asarray(lane if lane is not None else [], np.float64).reshape(-1, 2)[:L.UFLD_MAX_POINTS]
+            pts[l, :len(a)], cnt[l] = a.astype(np.int64).astype(np.int32), len(a)     # int(x), int(y)
+        return pts, cnt
+
+    def lanes(self, image, lanes_points, type=None, alpha=0.3, bird=False):
+        ptr, host = self._target(image)
+        pts, cnt = self._lane_table(lanes_points)
+        d_pts, d_cnt = L.DeviceBuffer.from_array(pts), L.DeviceBuffer.from_array(cnt)
+        d_off = L.DeviceBuffer.from_array(np.array([self._offset(type)], np.int32))
+        try:
+            if bird:
+                self.ov.run_arrays(None, 1, offset_type=d_off.ptr, bird_points=d_pts.ptr, bird_counts=d_cnt.ptr, bird_ptr=ptr, stages=L.OVERLAY_BIRD)
+            else:
+                self.ov.set_style(lane_alpha=float(alpha))
+                self.ov.run_arrays(ptr, 1, lane_points=d_pts.ptr, lane_counts=d_cnt.ptr, offset_type=d_off.ptr, stages=L.OVERLAY_LANES, dst_ptr=ptr)
+            self._finish(ptr, host)
+        finally:
+            for b in (d_pts, d_cnt, d_off):
+                b.free()
+
+    def area(self, image, area_points, color=(255, 191, 0), alpha=0.85):
+        ptr, host = self._target(image)
+        poly = np.ascontiguousarray(np.asarray(area_points, np.float64).reshape(-1, 2).astype(np.int64).astype(np.int32))
+        if len(poly) == 0:
+            return
+        d_poly = L.DeviceBuffer.from_array(poly)
+        d_meta = L.DeviceBuffer.from_array(np.array([len(poly), 1], np.int32))
+        try:
+            self.ov.set_style(area_alpha=float(alpha), area_color=tuple(int(c) for c in color))
+            self.ov.run_arrays(ptr, 1, poly=d_poly.ptr, poly_cap=len(poly), poly_counts=d_meta.ptr, area_status=d_meta.ptr + 4, stages=L.OVERLAY_AREA,
+                               dst_ptr=ptr)
+            self._finish(ptr, host)
+        finally:
+            d_poly.free()
+            d_meta.free()
+
+    def close(self):
+        if self.ov is not None:
+            self.ov.close()
+        if self.buf is not None:
+            self.buf.free()
+        self.ov = self.key = self.buf = None
+
+
 class DeviceTracker:
     """n_streams independent ByteTrack instances living on the GPU."""
 
