@@ -643,7 +643,8 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * in HBM -- UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame (ultrafastLaneDetectorV2.py:196-218, the same in v1), the
  * discs of SingleCamDistanceMeasure.DrawDetectedOnFrame (distanceMeasure.py:98) and PerspectiveTransformation.DrawDetectedOnBirdView
  * (perspectiveTransformation.py:217-226): two whole-frame cv2.addWeighted passes, a cv2.fillPoly and filled cv2.circles.
- * NOT drawn: text (putText / getTextSize), thick lines (cornerRect, arrowedLine, trajectories) and the UI panels.
+ * NOT drawn: text (putText / getTextSize), arrows and trajectories (arrowedLine, thick circles) and the UI panels; the boxes of the
+ * detector and the tracker are the object layer below.
  * The pixel rules are modelled on OpenCV 4.5's drawing.cpp / arithm and defined in csrc/overlay_core.h (restated in NumPy,
  * tests/overlay_ref.py); parity with a real cv2 build is UNPINNED, and lines are not clipped before they are walked (OpenCV clips the
  * segment first and restarts the error term).  Per frame f, S0 = the source frame:
@@ -659,6 +660,22 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * (frame_show = frame.copy()); every output byte depends on the same input byte and geometry only, so dst == src is legal.
  * Three launches for the frame (coverage, one streaming pass with 16-byte accesses, coverage clean-up), two for the bird view; all plain:
  * capturable.  Nothing is capped: lanes hold at most ADAS_UFLD_MAX_POINTS points, polygons and distance points as many as their sources.
+ *
+ * The object layer: two more stages, off unless asked for, drawn between AREA and DISTANCE in the reference's order (demo.py:299-305).
+ *   16 DETECTIONS  YoloDetector / EfficientdetDetector.DrawDetectedOnFrame's boxes (yoloDetector.py:170-191): per survivor, in _object_info
+ *               order, ObjectDetectBase.cornerRect (ObjectDetector/core.py:94-113) on RectInfo.tolist() in the class colour -- the outline
+ *               (rt = 1) and eight corner arms (t = 5) of length max(1, int(min(ymax - ymin, xmax - xmin) * 0.2)), written.
+ *   32 TRACKS   the box part of BYTETracker.DrawTrackedOnFrame (byteTracker.py:202-215, plot_bbox, ObjectTracker/core.py:226-245): every
+ *               track of tracked_stracks, in list order, that is activated and has tlwh[2] * tlwh[3] > min_box_area: tlwh.astype(int),
+ *               clamped to the image (x1 = max(0, tx), x2 = min(W, tx + tw), the same in y), cv2.rectangle((x1, y1), (x2, y2), thickness 2)
+ *               written, then addWeighted(region, 0.6, colour, 0.4, 1.0) on columns x1 .. x2 - 1, rows y1 .. y2 - 1.  One divergence: with
+ *               x2 <= x1 or y2 <= y1 nothing is tinted (the reference slices from the end, or raises on the empty crop).
+ * A class id outside the colour table is the reference's 'unknown': black.  Where boxes overlap the result is the sequential fold of the
+ * reference's calls; the distance discs still lie over everything.  The pixel rules are D6-D9 of csrc/overlay_core.h (a thick axis-aligned
+ * segment is a body plus two end discs; modelled on OpenCV 4.5's ThickLine, parity UNPINNED).  NOT drawn: text, the label's background
+ * rectangle, key points, plot_trajectories' thick circles, plot_directions' arrows, DrawTransformFrontalViewArea's slanted thick lines, the
+ * UI panels.  One more launch (the boxes' records) when one of the two stages is on, none when both are off; nothing is capped below the
+ * sources' capacities (max_candidates per frame, max_tracks per stream).
  * ----------------------------------------------------------------------------------- */
 typedef struct adas_overlay adas_overlay;
 typedef struct {
@@ -678,6 +695,8 @@ typedef struct {
 #define ADAS_OVERLAY_AREA 2
 #define ADAS_OVERLAY_DISTANCE 4
 #define ADAS_OVERLAY_BIRD 8
+#define ADAS_OVERLAY_DETECTIONS 16 /* adas_overlay_run_objects / _run_arrays_objects / adas_pipeline_set_overlay_stages only */
+#define ADAS_OVERLAY_TRACKS 32
 #define ADAS_OVERLAY_POLY_RANGE 1 /* frame flags: a polygon vertex outside +-32767, the frame's fill was skipped */
 /* The reference's radii, alphas and colours; the four sizes are 0. */
 int adas_overlay_default_params(adas_overlay_params* p);
@@ -703,6 +722,37 @@ int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* 
                             const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
                             const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
                             int n_frames, void* stream);
+/* The object layer's run-time style; the tint's weights (0.6, 0.4, + 1.0) are plot_bbox's and fixed. */
+typedef struct {
+    double min_box_area;         /* BYTETracker.min_box_area, 10: a track is drawn when tlwh[2] * tlwh[3] > min_box_area */
+    int32_t det_rect_thickness;  /* cornerRect's rt, 1 */
+    int32_t det_arm_thickness;   /* cornerRect's t, 5 */
+    int32_t track_thickness;     /* plot_bbox's rectangle, 2; each thickness 1 .. 127 */
+    int32_t reserved;
+} adas_overlay_object_style;
+int adas_overlay_default_object_style(adas_overlay_object_style* p);
+/* Takes effect with the next run; a captured pipeline step is re-captured. */
+int adas_overlay_set_object_style(adas_overlay* h, const adas_overlay_object_style* p);
+/* The class colours of one stage (which: ADAS_OVERLAY_DETECTIONS -- colors_dict by class id, yoloDetector.py:93-94 -- or ADAS_OVERLAY_TRACKS --
+ * class_colors, ObjectTracker/core.py:83-93), n BGR triples written to channels 0, 1, 2 as given.  With no table set (or n = 0) every
+ * object is 'unknown', black.  Takes effect with the next run; a captured pipeline step is re-captured.  Waits for the device. */
+int adas_overlay_set_class_colors(adas_overlay* h, int which, const uint8_t (*bgr)[3], int n);
+/* adas_overlay_run plus the two stages of the object layer: DETECTIONS reads `post`'s survivors (frame index as for the other handles),
+ * TRACKS reads `tracker`'s live table, stream s for frame s -- the table holds the last frame only, so TRACKS needs n_frames == 1.  A stage
+ * without its handle is ADAS_ERR_INVALID, by name.  post / tracker may be NULL with their stages off. */
+int adas_overlay_run_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
+                             adas_analysis* analysis, adas_yolo_post* post, struct adas_bytetrack* tracker, uint8_t* d_bird_bgr, int stages, int n_streams,
+                             int n_frames, void* stream);
+/* adas_overlay_run_arrays plus: d_det_xyxy [frames][det_cap][4] int32 (xmin, ymin, xmax, ymax) + d_det_cls [frames][det_cap] + d_det_counts
+ * [frames]; d_trk_tlwh [frames][trk_cap][4] fp64 + d_trk_cls [frames][trk_cap] + d_trk_counts [frames], rows already filtered to activated
+ * tracked tracks in list order -- the area gate is applied on the device. */
+int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points,
+                                    const int32_t* d_lane_counts, const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts,
+                                    const int32_t* d_area_status, const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points,
+                                    int dist_cap, const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts,
+                                    uint8_t* d_bird_bgr, const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts,
+                                    const double* d_trk_tlwh, int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages,
+                                    int n_frames, void* stream);
 /* Frame `frame` of the handle's own buffer -> h_bgr [src_h][src_w][3], after the last run's stream has drained.  A frame that no run
  * has written is ADAS_ERR_INVALID. */
 int adas_overlay_fetch(adas_overlay* h, int frame, uint8_t* h_bgr);
@@ -833,7 +883,9 @@ int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis);
  * its launch count are unchanged.  The handle stays the caller's. */
 int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay);
 /* The stages (ADAS_OVERLAY_*) the attached overlay draws; one that lacks its handle (DISTANCE without an analysis handle, BIRD without a
- * warp) is ADAS_ERR_INVALID at the step.  Cached graphs are dropped. */
+ * warp, DETECTIONS without a detector, TRACKS without a tracker) is ADAS_ERR_INVALID at the step.  The default set holds neither
+ * DETECTIONS nor TRACKS.  DETECTIONS draws the step's survivors, TRACKS the tracker's table after this step's update; TRACKS with
+ * micro_batch > 1 is ADAS_ERR_INVALID at the step (the live table holds the last frame only).  Cached graphs are dropped. */
 int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);

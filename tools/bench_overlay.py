@@ -6,9 +6,11 @@ drawing on the host:
     polygon of 840 vertices, 16 distance points, 4 x 72 bird points), timed with the library's events on the null stream against
     hipMemcpyAsync device-to-device of the same frames between the same events, in alternation.  The copy is the yardstick: the
     streaming pass moves the same bytes plus the coverage words.  The frame stages alone (no bird view) and an empty scene (the pass as a
-    pure copy plus the preparation and clean-up launches) are timed the same way to show where the time goes.
+    pure copy plus the preparation and clean-up launches) are timed the same way to show where the time goes.  So is the object layer:
+    the frame stages plus --detections cornerRect boxes per frame, plus --tracks tracked boxes (rectangle and tint), and all six stages.
 (b) fused step: two pipelines of the same two networks, bird-view image and analysis in ONE process, stepped from the same camera frames
-    in alternation: `off` as it was, `on` with overlay= (all four stages).  A window is --steps steps between two host clock readings with
+    in alternation: `off` as it was, `on` with overlay= (all four stages), `obj` with the detections and tracks stages as well.  A window is
+    --steps steps between two host clock readings with
     the pipeline drained at both ends; median window of --rounds, with the fastest and the slowest.
 (c) the host loop the stage replaces, on the `off` pipeline: sync, fetch every frame's lanes, polygon, analysis row, distance points and
     bird view, and draw with the NumPy restatement (tests/overlay_ref.py) -- --host-steps steps, per step.
@@ -36,6 +38,9 @@ ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--host-steps", type=int, default=2)
 ap.add_argument("--precision", default=None)
 ap.add_argument("--box-score", type=float, default=0.1)
+ap.add_argument("--detections", type=int, default=24, help="boxes per frame of the detections stage in (a)")
+ap.add_argument("--tracks", type=int, default=16, help="boxes per frame of the tracks stage in (a)")
+ap.add_argument("--no-objects", action="store_true", help="leave the object layer's variants out of (a)'s alternation and (b)")
 ap.add_argument("--standalone-only", action="store_true", help="(a) alone, e.g. under a kernel trace")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "overlay_ab.txt"))
 a = ap.parse_args()
@@ -75,7 +80,18 @@ kw = {k: b.ptr for k, b in bufs.items()}
 kw.update(poly_cap=len(poly1), dist_cap=16)
 zero = L.DeviceBuffer.from_array(np.zeros(4 * S, np.int32))
 kw_empty = dict(kw, lane_counts=zero.ptr, poly_counts=zero.ptr, dist_counts=zero.ptr, bird_counts=zero.ptr)
+ND, NT = a.detections, a.tracks            # the object layer's boxes: vehicle-sized, in the lower two thirds of the frame
+bx, by = rng.integers(-40, W - 60, (S, ND + NT)), rng.integers(220, H - 60, (S, ND + NT))
+bw, bh = rng.integers(60, 300, (S, ND + NT)), rng.integers(50, 220, (S, ND + NT))
+obj = dict(det_xyxy=np.stack([bx, by, bx + bw, by + bh], 2)[:, :ND].astype(np.int32), det_cls=rng.integers(0, 80, (S, ND)).astype(np.int32),
+           det_counts=np.full(S, ND, np.int32), trk_tlwh=np.stack([bx, by, bw, bh], 2)[:, ND:].astype(np.float64) + 0.5,
+           trk_cls=rng.integers(0, 80, (S, NT)).astype(np.int32), trk_counts=np.full(S, NT, np.int32))
+obufs = {k: L.DeviceBuffer.from_array(np.ascontiguousarray(v)) for k, v in obj.items()}
+okw = dict(kw, det_cap=ND, trk_cap=NT, **{k: b.ptr for k, b in obufs.items()})
+CLASS_COLORS = rng.integers(0, 256, (80, 3)).tolist()
 ov = PP.LaneOverlay((H, W), (H, W), S)
+ov.set_class_colors("detections", CLASS_COLORS)
+ov.set_class_colors("tracks", CLASS_COLORS)
 dst = ov.device_view()
 bird = L.DeviceBuffer.from_array(cams[1])
 timer = L.StreamTimer()
@@ -91,7 +107,14 @@ def timed(fn):
 variants = [("copy", lambda: hip.hipMemcpyAsync(dst, cam[0].ptr, nbytes, D2D, None)),
             ("overlay, all stages", lambda: ov.run_arrays(cam[0].ptr, S, bird_ptr=bird.ptr, stages=15, **kw)),
             ("overlay, frame stages", lambda: ov.run_arrays(cam[0].ptr, S, stages=7, **kw)),
-            ("overlay, empty scene", lambda: ov.run_arrays(cam[0].ptr, S, stages=7, **kw_empty))]
+            ("overlay, empty scene", lambda: ov.run_arrays(cam[0].ptr, S, stages=7, **kw_empty)),
+            ("frame stages + detections", lambda: ov.run_arrays(cam[0].ptr, S, stages=7 | 16, **okw)),
+            ("frame stages + tracks", lambda: ov.run_arrays(cam[0].ptr, S, stages=7 | 32, **okw)),
+            ("all six stages", lambda: ov.run_arrays(cam[0].ptr, S, bird_ptr=bird.ptr, stages=63, **okw))]
+OBJECT_LINES = ("frame stages + detections", "frame stages + tracks", "all six stages")
+if a.no_objects:
+    variants = [v for v in variants if v[0] not in OBJECT_LINES]
+    OBJECT_LINES = ()
 for _, fn in variants:                     # warm-up
     fn()
 L.check(L.lib().adas_synchronize())
@@ -105,15 +128,28 @@ lines = ["tools/bench_overlay.py on one MI355X (gfx950).", "",
          "(a) stand-alone, %d frames of 1280x720 (%.1f MB read + %.1f MB written), %d rounds of %d calls between two events on the null stream,"
          % (S, nbytes / 1e6, nbytes / 1e6, a.rounds, a.iters),
          "    alternated in one process; us per call, median round (fastest, slowest); %.1f %% of a frame's pixels are drawn on." % (100 * drawn), ""]
+share = {}
+for name, st in (("detections", 16), ("tracks", 32)):
+    ov.run_arrays(cam[0].ptr, S, stages=st, **okw)
+    share[name] = float((ov.fetch(0) != cams[0][0]).any(axis=2).mean())
 cm = median(us["copy"])[0]
 for n, _ in variants:
+    if n in OBJECT_LINES:
+        continue
     m, lo, hi = median(us[n])
     lines.append("    %-22s %9.1f us  (%.1f, %.1f)  %5.2f TB/s of frame bytes  %.2f x the copy" % (n, m, lo, hi, 2 * nbytes / m / 1e6, m / cm))
 allm, frm, emp = (median(us[n])[0] for n in ("overlay, all stages", "overlay, frame stages", "overlay, empty scene"))
 lines += ["", "    ratio to the copy: %.2f (expected within 1.5).  The empty scene (a mark launch with nothing to mark, the streaming pass as a pure"
           % (allm / cm), "    copy + its ANY-plane reads, the clean-up pass over the ANY plane) costs %.1f us = %.2f x the copy; having something to draw adds"
           % (emp, emp / cm), "    %.1f us to the three frame launches; the bird view's two launches add %.1f us." % (frm - emp, allm - frm)]
-for b in list(bufs.values()) + [zero, bird]:
+if OBJECT_LINES:
+    lines += ["", "    the object layer: %d detections per frame (cornerRect: outline and eight arms, %.1f %% of a frame's pixels) and %d tracked boxes per frame"
+              % (ND, 100 * share["detections"], NT), "    (thickness-2 rectangle and the tinted region, %.1f %% of a frame's pixels), one record-building launch more:"
+              % (100 * share["tracks"]), ""]
+for n in OBJECT_LINES:
+    m, lo, hi = median(us[n])
+    lines.append("    %-26s %9.1f us  (%.1f, %.1f)  %5.2f x the copy  %+8.1f us on this run's frame stages" % (n, m, lo, hi, m / cm, m - frm))
+for b in list(bufs.values()) + list(obufs.values()) + [zero, bird]:
     b.free()
 ov.close(); timer.close()
 
@@ -150,7 +186,11 @@ Mh = A.PerspectiveTransformation(IMG).M
 car = A.SingleCamDistanceMeasure.RefSizeDict["car"][0]
 pkw = dict(n_streams=S, precision=a.precision, src_hw=(H, W), use_graph=True, track=True, box_score=a.box_score, max_candidates=512,
            geometry=dict(bird_wh=IMG, M=Mh), birdview=dict(image=True), analysis=dict(ref_height=[car] * 80))
-pipes = [("off", PL.AdasPipeline(det_path, lane_path, **pkw)), ("on", PL.AdasPipeline(det_path, lane_path, overlay=dict(), **pkw))]
+pipes = [("off", PL.AdasPipeline(det_path, lane_path, **pkw)), ("on", PL.AdasPipeline(det_path, lane_path, overlay=dict(), **pkw)),
+         ("obj", PL.AdasPipeline(det_path, lane_path, overlay=dict(stages=("lanes", "area", "distance", "bird", "detections", "tracks"),
+                                                                    detection_colors=CLASS_COLORS, track_colors=CLASS_COLORS), **pkw))]
+if a.no_objects:
+    pipes.pop()[1].close()
 count = {n: 0 for n, _ in pipes}
 OFF = {"UNKNOWN": 0, "RIGHT": 1, "LEFT": 2, "CENTER": 3}
 COL = {"UNKNOWN": 0, "NORMAL": 1, "PROMPT": 2, "WARNING": 3}
@@ -193,7 +233,7 @@ for _ in range(a.rounds):
 host = []
 same = True
 for k in range(a.host_steps):
-    for name, p in pipes:
+    for name, p in pipes[:2]:
         p.step_frames(cam[k % 2].ptr, (H, W), 0.6)
     t, shown = host_loop(pipes[0][1], cams[k % 2])
     host.append(t)
@@ -211,6 +251,8 @@ for name, _ in pipes:
 hm, hlo, hhi = median(host)
 lines += ["", "    on - off = %+8.1f us per step (five plain launches behind the analysis stage, inside the capture); the stand-alone run takes %.1f us"
           % ((med["on"] - med["off"]) * 1e3, allm),
+          ] + (["    obj - on  = %+8.1f us per step (the detections and tracks stages: the step's survivors and its tracked tracks, one launch more)"
+                % ((med["obj"] - med["on"]) * 1e3)] if "obj" in med else []) + [
           "", "(c) the host loop the stage replaces, on the `off` pipeline after a sync: per stream 5 fetches (lanes, geometry, analysis row, distance",
           "    points, bird view) and the NumPy restatement's drawing of both images: %.1f ms per step of %d streams (fastest %.1f, slowest %.1f; %d steps),"
           % (hm, S, hlo, hhi, a.host_steps),

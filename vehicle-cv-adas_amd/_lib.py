@@ -120,8 +120,15 @@ class OverlayParams(C.Structure):
                 ("collision_colors", (C.c_uint8 * 3) * 4), ("distance_color", C.c_uint8 * 3), ("pad", C.c_uint8 * 7)]
 
 
+class OverlayObjectStyle(C.Structure):
+    _fields_ = [("min_box_area", C.c_double), ("det_rect_thickness", C.c_int32), ("det_arm_thickness", C.c_int32), ("track_thickness", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 OVERLAY_LANES, OVERLAY_AREA, OVERLAY_DISTANCE, OVERLAY_BIRD = 1, 2, 4, 8     # adas_overlay_run's stages
-OVERLAY_STAGES = {"lanes": OVERLAY_LANES, "area": OVERLAY_AREA, "distance": OVERLAY_DISTANCE, "bird": OVERLAY_BIRD}
+OVERLAY_DETECTIONS, OVERLAY_TRACKS = 16, 32                                  # the object layer: adas_overlay_run_objects / _run_arrays_objects
+OVERLAY_STAGES = {"lanes": OVERLAY_LANES, "area": OVERLAY_AREA, "distance": OVERLAY_DISTANCE, "bird": OVERLAY_BIRD,
+                  "detections": OVERLAY_DETECTIONS, "tracks": OVERLAY_TRACKS}
 OVERLAY_POLY_RANGE = 1                                                       # adas_overlay_fetch_flags
 
 
@@ -283,6 +290,12 @@ _SIGS = {
     "adas_overlay_set_style": (C.c_int, [_P, C.POINTER(OverlayParams)]),
     "adas_overlay_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "adas_overlay_run_arrays": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_objects": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_arrays_objects": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
+                                                  _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_overlay_default_object_style": (C.c_int, [C.POINTER(OverlayObjectStyle)]),
+    "adas_overlay_set_object_style": (C.c_int, [_P, C.POINTER(OverlayObjectStyle)]),
+    "adas_overlay_set_class_colors": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "adas_overlay_fetch": (C.c_int, [_P, C.c_int, _P]),
     "adas_overlay_device_view": (C.c_int, [_P, C.POINTER(_P)]),
     "adas_overlay_fetch_flags": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),

@@ -26,6 +26,7 @@ struct adas_lane_geometry;
 struct adas_birdview;
 struct adas_warp;
 struct adas_analysis;
+struct adas_bytetrack;
 namespace adas {
 int handle_max_batch(const ::adas_yolo_post* h);
 int handle_max_batch(const ::adas_ufld_decode* h);
@@ -51,6 +52,14 @@ const int* geometry_bird_points(const ::adas_lane_geometry* h);         // [B][4
 void analysis_frame_views(const ::adas_analysis* h, const int** frames, int* stride, const int** pts_xy, int* max_points);
 void warp_dst_geometry(const ::adas_warp* h, int* dst_h, int* dst_w);
 int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_h, int* bird_w, int* max_batch);
+// what the overlay's object layer reads (post_kernels.hip): the survivors as RectInfo.tolist() corners [B][cap][4] with classes [B][cap] and
+// counts [B][4] (n_keep is word 2); the tracker's live table, stream s at + s * stream_bytes: its header, and its rows in the layout of
+// adas_track, the tracked list first and in list order
+void post_survivor_views(const ::adas_yolo_post* h, const int** xyxy_int, const int** cls, const int** counts, int* cap);
+void tracker_live_views(const ::adas_bytetrack* h, const unsigned char** hdr, const unsigned char** out, size_t* stream_bytes, int* n_streams,
+                        int* max_tracks);
+// room for the records of det_cap + trk_cap boxes per frame, ahead of a captured step (overlay_kernels.hip)
+int overlay_reserve_objects(::adas_overlay* h, int det_cap, int trk_cap);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

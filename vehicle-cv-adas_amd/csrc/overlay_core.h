@@ -17,6 +17,18 @@
 //              a pair fills ceil(Xl / 65536) .. floor(Xr / 65536).  Pixel q of a row is inside some pair exactly when the number of
 //              crossings below q * 65536 is odd or a crossing equals q * 65536 (the number of crossings of a closed contour on a row is
 //              even), so no sort is needed: overlay_poly_edge_row toggles one bit per crossing and a prefix XOR over the row does the rest.
+// The object layer (boxes of the detector and of the tracker: ObjectDetectBase.cornerRect, ObjectDetector/core.py:94-113, and the box part of
+// ObjectTrackBase.plot_bbox, ObjectTracker/core.py:226-245) adds, under the same terms (the definitions are the authority, parity unpinned):
+//   D6 thick   axis-aligned segment (ax, ay) - (bx, by) of thickness t >= 2, R = (t + 1) >> 1: the body, the segment's pixels along its axis
+//              (both ends) by -R .. +R across it, plus a D2 disc of radius R on each endpoint (OpenCV 4.5's ThickLine: a quad of half-width
+//              t / 2 filled with both borders, end caps of radius (t * 32768 + 32768) >> 16).  A zero-length segment is its two coinciding
+//              discs.  On a row the body and the caps are one run (overlay_seg_row).  t == 1 is the D3 line: R = 0 gives the same pixels;
+//   D7 outline the edges (x1,y1)-(x2,y1), (x2,y1)-(x2,y2), (x2,y2)-(x1,y2), (x1,y2)-(x1,y1): D3 lines for t == 1, D6 segments for t >= 2;
+//   D8 tint    r = rintf(((float)a * af + (float)b * bf) + g), a the pixel, b the colour, af = (float)0.6, bf = (float)0.4 (given, not
+//              1 - af), g = 1.0f: two separately rounded products, two adds in that order, no contraction, ties to even, saturated;
+//   D9 fold    v0 = the pixel after AREA.  Detections in order: inside detection i's outline or corner arms, v = colour_i.  Tracks in order:
+//              inside track k's outline v = colour_k, then inside its tint region v = D8(v, colour_k).  DISTANCE still overrides everything.
+//              Where boxes overlap the result is this sequential fold (overlay_object_ops / overlay_object_channel per record).
 // Nothing here loops for a number of steps given by a coordinate; all coordinate arithmetic is int64.
 // Like warp_core.h the header also compiles for the host (tests/hostemu/emu_overlay.cpp).
 #pragma once
@@ -34,6 +46,14 @@
 #endif
 #endif
 
+#if !defined(ADAS_HDI)   // the object layer's rules are inlined into the kernels: a box passed by reference must not end up in scratch
+#if defined(__HIPCC__)
+#define ADAS_HDI __host__ __device__ __forceinline__
+#else
+#define ADAS_HDI inline
+#endif
+#endif
+
 namespace adas {
 
 #define ADAS_OVERLAY_MAX_RADIUS 64     // hw tables are [ADAS_OVERLAY_MAX_RADIUS + 1]
@@ -43,6 +63,8 @@ namespace adas {
 #define OV_BIT_LANE0 1u    // lanes 0..3: bits 0..3
 #define OV_BIT_AREA 16u
 #define OV_BIT_DIST 32u
+#define OV_BIT_DET 64u     // some detection draws here
+#define OV_BIT_TRK 128u    // some track draws or tints here
 
 // ---------------------------------------------------------------------------------------------------------------- D1
 struct OverlayAlpha {
@@ -203,6 +225,188 @@ ADAS_HD int overlay_pixel(int s, uint32_t bits, int c, const OverlayStyle& st) {
         v = st.lane_direct ? k : overlay_blend(k, v, st.lane_w);
     }
     if (bits & OV_BIT_AREA) v = overlay_blend(v, (int)((st.area >> (8 * c)) & 0xffu), st.area_w);
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- D6
+#define ADAS_OVERLAY_MAX_THICKNESS (2 * ADAS_OVERLAY_MAX_RADIUS - 1)   // R = (t + 1) >> 1 <= ADAS_OVERLAY_MAX_RADIUS
+ADAS_HDI int overlay_seg_radius(int t) { return t >= 2 ? (t + 1) >> 1 : 0; }   // t == 1: the thin line (D3); axis-aligned, R = 0 gives its pixels
+// the pixels of the segment (ax, ay) - (bx, by), ax == bx or ay == by, on row y: false when it has none, else the run xl .. xr (unclipped).
+// hw: overlay_disc_halfwidths(R).  Body and caps of a row are one run: a horizontal body ax .. bx grows by the caps' hw[|y - ay|] on either
+// side; a vertical body is -R .. +R on its rows and a cap's row beyond its ends.
+ADAS_HDI bool overlay_seg_row(long long ax, long long ay, long long bx, long long by, int R, const int* hw, long long y, long long* xl,
+                             long long* xr) {
+    if (ay == by) {   // horizontal, or zero length: two coinciding discs
+        const long long j = y < ay ? ay - y : y - ay;
+        if (j > R) return false;
+        *xl = (ax < bx ? ax : bx) - hw[j];
+        *xr = (ax < bx ? bx : ax) + hw[j];
+        return true;
+    }
+    const long long y0 = ay < by ? ay : by, y1 = ay < by ? by : ay;
+    if (y >= y0 && y <= y1) {
+        *xl = ax - R;
+        *xr = ax + R;
+        return true;
+    }
+    const long long j = y < y0 ? y0 - y : y - y1;
+    if (j > R) return false;
+    *xl = ax - hw[j];
+    *xr = ax + hw[j];
+    return true;
+}
+ADAS_HDI bool overlay_seg_hit(long long ax, long long ay, long long bx, long long by, int R, const int* hw, int x, int y) {
+    long long xl, xr;
+    return overlay_seg_row(ax, ay, bx, by, R, hw, y, &xl, &xr) && x >= xl && x <= xr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- D7
+// edge k (0 .. 3) of the outline through (x1, y1), (x2, y1), (x2, y2), (x1, y2)
+ADAS_HDI void overlay_rect_edge(long long x1, long long y1, long long x2, long long y2, int k, long long* ax, long long* ay, long long* bx,
+                               long long* by) {
+    *ax = (k == 0 || k == 3) ? x1 : x2;
+    *ay = k < 2 ? y1 : y2;
+    *bx = k < 2 ? x2 : x1;
+    *by = (k == 0 || k == 3) ? y1 : y2;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- D8
+ADAS_HDI int overlay_tint(int a, int b) {
+    const float af = (float)0.6, bf = (float)0.4, g = 1.0f;
+    const float pa = (float)a * af;
+    const float pb = (float)b * bf;
+    const float s = pa + pb;
+    const float t = s + g;
+    const float r = rintf(t);   // ties to even
+    return r < 0.f ? 0 : (r > 255.f ? 255 : (int)r);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- D9
+#define OV_OBJ_NONE 0    // nothing is drawn (a track that is not activated, or fails the area gate)
+#define OV_OBJ_DET 1     // cornerRect: the outline (thickness rect_t) and eight corner arms of length l (thickness arm_t), written
+#define OV_OBJ_TRACK 2   // plot_bbox: the outline (thickness track_t), written, then the region x1 .. x2 - 1, y1 .. y2 - 1 tinted
+struct OverlayObject {           // one box, 48 bytes
+    int kind;
+    int x1, y1, x2, y2;          // a detection's RectInfo.tolist(); a track's clamped corners
+    int l;                       // the arms' length (detections)
+    uint32_t colour;             // packed as overlay_pack_bgr does
+    int bx0, by0, bx1, by1;      // every pixel the box can touch, inside the image; empty (bx0 > bx1) when it touches none
+    int pad;
+};
+#define OV_SEG_RECT 0     // a detection's outline
+#define OV_SEG_ARM 1      // its corner arms
+#define OV_SEG_TRACK 2    // a track's outline
+struct OverlayObjStyle {
+    int radii;            // overlay_seg_radius of the three thicknesses, 8 bits each: OV_SEG_RECT lowest (one word: chosen by a shift)
+    const int* hw;        // their overlay_disc_halfwidths: table w at hw + w * hw_stride
+    int hw_stride;
+};
+ADAS_HDI int overlay_obj_radii(int rect_t, int arm_t, int track_t) {
+    return overlay_seg_radius(rect_t) | (overlay_seg_radius(arm_t) << 8) | (overlay_seg_radius(track_t) << 16);
+}
+ADAS_HDI int overlay_obj_radius(const OverlayObjStyle& s, int which) { return (s.radii >> (8 * which)) & 0xff; }
+ADAS_HDI int overlay_trunc_i32(double v) {        // astype(int) for what an image can hold: toward zero, saturated, NaN -> 0
+    if (!(v == v)) return 0;
+    if (v >= 2147483647.0) return 2147483647;
+    if (v <= -2147483648.0) return -2147483647 - 1;
+    return (int)v;
+}
+ADAS_HDI uint32_t overlay_class_colour(int cls, const uint32_t* table, int n) {   // outside the table: 'unknown', black
+    return (table && cls >= 0 && cls < n) ? table[cls] : 0u;
+}
+ADAS_HDI void overlay_object_bounds(OverlayObject* o, long long grow, int W, int H) {
+    long long x0 = (o->x1 < o->x2 ? o->x1 : o->x2) - grow, x1 = (o->x1 < o->x2 ? o->x2 : o->x1) + grow;
+    long long y0 = (o->y1 < o->y2 ? o->y1 : o->y2) - grow, y1 = (o->y1 < o->y2 ? o->y2 : o->y1) + grow;
+    if (x0 < 0) x0 = 0;
+    if (y0 < 0) y0 = 0;
+    if (x1 > W - 1) x1 = W - 1;
+    if (y1 > H - 1) y1 = H - 1;
+    if (x0 > x1 || y0 > y1) {
+        x0 = y0 = 1;
+        x1 = y1 = 0;
+    }
+    o->bx0 = (int)x0; o->by0 = (int)y0; o->bx1 = (int)x1; o->by1 = (int)y1;
+}
+// cornerRect's box: l = max(1, int(min(ymax - ymin, xmax - xmin) * 0.2)), an fp64 product truncated toward zero
+ADAS_HDI OverlayObject overlay_make_detection(const int* xyxy, uint32_t colour, const OverlayObjStyle& s, int W, int H) {
+    OverlayObject o;
+    o.kind = OV_OBJ_DET;
+    o.x1 = xyxy[0]; o.y1 = xyxy[1]; o.x2 = xyxy[2]; o.y2 = xyxy[3];
+    const long long dy = (long long)o.y2 - o.y1, dx = (long long)o.x2 - o.x1;
+    const double p = (double)(dy < dx ? dy : dx) * 0.2;
+    const int l = (int)p;   // |p| < 2^30
+    o.l = l < 1 ? 1 : l;
+    o.colour = colour;
+    o.pad = 0;
+    const int rr = overlay_obj_radius(s, OV_SEG_RECT), ra = overlay_obj_radius(s, OV_SEG_ARM);
+    overlay_object_bounds(&o, (long long)o.l + (rr > ra ? rr : ra), W, H);
+    return o;
+}
+// plot_bbox's box of a track that is activated: tlwh.astype(int), clamped to the image; OV_OBJ_NONE when tlwh[2] * tlwh[3] > min_box_area fails
+ADAS_HDI OverlayObject overlay_make_track(const double* tlwh, int activated, double min_box_area, uint32_t colour, const OverlayObjStyle& s, int W,
+                                         int H) {
+    OverlayObject o;
+    o.kind = OV_OBJ_NONE;
+    o.x1 = o.y1 = o.x2 = o.y2 = o.l = o.pad = 0;
+    o.colour = colour;
+    o.bx0 = o.by0 = 1;
+    o.bx1 = o.by1 = 0;
+    if (!activated || !(tlwh[2] * tlwh[3] > min_box_area)) return o;
+    const long long tx = overlay_trunc_i32(tlwh[0]), ty = overlay_trunc_i32(tlwh[1]), tw = overlay_trunc_i32(tlwh[2]), th = overlay_trunc_i32(tlwh[3]);
+    const long long lo = -2147483647LL - 1;
+    long long x2 = tx + tw < W ? tx + tw : W, y2 = ty + th < H ? ty + th : H;
+    if (x2 < lo) x2 = lo;
+    if (y2 < lo) y2 = lo;
+    o.kind = OV_OBJ_TRACK;
+    o.x1 = (int)(tx > 0 ? tx : 0); o.y1 = (int)(ty > 0 ? ty : 0); o.x2 = (int)x2; o.y2 = (int)y2;
+    overlay_object_bounds(&o, overlay_obj_radius(s, OV_SEG_TRACK), W, H);
+    return o;
+}
+// segment k of a box: 0 .. 3 the outline's edges (D7), for a detection 4 .. 11 the corner arms in cornerRect's order.  Returns the segment's
+// radius and its half-widths in *hw.
+ADAS_HDI int overlay_object_segments(const OverlayObject& o) { return o.kind == OV_OBJ_DET ? 12 : (o.kind == OV_OBJ_TRACK ? 4 : 0); }
+ADAS_HDI int overlay_object_segment(const OverlayObject& o, int k, const OverlayObjStyle& s, long long* ax, long long* ay, long long* bx,
+                                    long long* by, const int** hw) {
+    const long long x1 = o.x1, y1 = o.y1, x2 = o.x2, y2 = o.y2, l = o.l;   // every field is read before any is chosen
+    int which = o.kind == OV_OBJ_DET ? OV_SEG_RECT : OV_SEG_TRACK;
+    if (k < 4) {
+        overlay_rect_edge(x1, y1, x2, y2, k, ax, ay, bx, by);
+    } else {
+        const int a = k - 4, corner = a >> 1;                        // corners: top left, top right, bottom left, bottom right
+        const long long cx = (corner & 1) ? x2 : x1, cy = (corner & 2) ? y2 : y1;
+        *ax = cx; *ay = cy; *bx = cx; *by = cy;
+        if (a & 1) *by = (corner & 2) ? cy - l : cy + l;            // the vertical arm, into the box
+        else *bx = (corner & 1) ? cx - l : cx + l;                  // the horizontal arm
+        which = OV_SEG_ARM;
+    }
+    *hw = s.hw + which * s.hw_stride;
+    return overlay_obj_radius(s, which);
+}
+// what box o does to pixel (x, y), in this order: bit 0 its colour is written, bit 1 the pixel is tinted with it
+ADAS_HDI int overlay_object_ops(const OverlayObject& o, int x, int y, const OverlayObjStyle& s) {
+    if (x < o.bx0 || x > o.bx1 || y < o.by0 || y > o.by1) return 0;
+    int ops = 0;
+    // every segment lies on one of the lines x = x1, x = x2, y = y1, y = y2 and reaches at most its radius across it (a cap is a disc on a
+    // point of its line): a pixel farther than the largest radius from all four lines is in no segment -- the box's interior, mostly
+    const long long g = o.kind == OV_OBJ_DET ? (overlay_obj_radius(s, OV_SEG_RECT) > overlay_obj_radius(s, OV_SEG_ARM) ? overlay_obj_radius(s, OV_SEG_RECT)
+                                                                                                                     : overlay_obj_radius(s, OV_SEG_ARM))
+                                             : overlay_obj_radius(s, OV_SEG_TRACK);
+    const long long dx1 = (long long)x - o.x1, dx2 = (long long)x - o.x2, dy1 = (long long)y - o.y1, dy2 = (long long)y - o.y2;
+    const bool near = (dx1 >= -g && dx1 <= g) || (dx2 >= -g && dx2 <= g) || (dy1 >= -g && dy1 <= g) || (dy2 >= -g && dy2 <= g);
+    const int n = near ? overlay_object_segments(o) : 0;
+    for (int k = 0; k < n && !ops; ++k) {
+        long long ax, ay, bx, by;
+        const int* hw;
+        const int R = overlay_object_segment(o, k, s, &ax, &ay, &bx, &by, &hw);
+        if (overlay_seg_hit(ax, ay, bx, by, R, hw, x, y)) ops = 1;
+    }
+    if (o.kind == OV_OBJ_TRACK && x >= o.x1 && x < o.x2 && y >= o.y1 && y < o.y2) ops |= 2;
+    return ops;
+}
+ADAS_HDI int overlay_object_channel(int v, int ops, uint32_t colour, int c) {
+    const int k = (int)((colour >> (8 * c)) & 0xffu);
+    if (ops & 1) v = k;
+    if (ops & 2) v = overlay_tint(v, k);
     return v;
 }
 

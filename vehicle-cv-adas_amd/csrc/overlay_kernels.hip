@@ -18,6 +18,14 @@
 //   overlay_clean_kernel   zeroes the words that were set (reads the ANY plane, writes only where it is not zero).
 // The bird view's discs are written in place: the same mark kernel on the bird planes, then overlay_apply_kernel, one thread per ANY word,
 // which writes the covered pixels and zeroes its words.
+// The object layer (ADAS_OVERLAY_DETECTIONS / ADAS_OVERLAY_TRACKS: cornerRect's outline and arms, plot_bbox's outline and tint, rules D6-D9)
+// carries a colour per box, which bit planes cannot: overlay_objects_kernel first turns the survivors and the live tracks into one 48-byte
+// record per box ([frames][det_cap + trk_cap] slots, order kept, a filtered track an empty record), the mark kernel ORs every record's runs
+// into the two spare detail planes ("some detection draws here", "some track draws or tints here"), and in the streaming pass a 16-byte
+// piece with such a pixel walks the frame's records once, in order (the first OV_OBJ_LDS staged in LDS, a longer list goes on from HBM --
+// nothing is truncated; a record whose box misses the piece's marked pixels is skipped) and evaluates the thick segments in closed form
+// for each marked pixel.  A piece without those bits takes the path it took before; with both stages off the pass is
+// overlay_stream_kernel, which holds no object code (with the layer: overlay_stream_objects_kernel), and the record kernel is not launched.
 // Memory-bound by design: the yardstick is a device-to-device copy of the same frames (tools/bench_overlay.py).
 #include "common.h"
 #include <stddef.h>
@@ -38,6 +46,12 @@ constexpr int OV_PLANES = 7;        // LDS planes of a band: lanes 0..3, area, d
 constexpr int OV_LIST = 2048;       // polygon edges listed per pass
 constexpr int OV_LDS_WORDS = 9216;  // LDS budget of the planes: 36 KB (+ 8 KB of edge list: under the 48 KB a launch may ask for)
 constexpr int OV_MAXPTS = ADAS_UFLD_MAX_POINTS;
+constexpr int OV_OBJ_STAGES = ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS;
+constexpr int OV_OBJ_PLANES = 9;    // with the object layer: + detections (plane 7), tracks (plane 8)
+constexpr int OV_OBJ_LDS = 384;     // records the streaming pass stages in LDS (18 KB); a longer list goes on from HBM
+constexpr int OV_OBJ_WAVES = 4;     // waves per SIMD the streaming pass with the object layer is compiled for
+constexpr int OV_HW = 68;           // ints of one half-width table in LDS (ADAS_OVERLAY_MAX_RADIUS + 1, rounded up to 16 bytes)
+static_assert(sizeof(OverlayObject) == 48, "OverlayObject is copied as three uint4");
 
 struct OvSources {                  // what one run reads, per frame q
     const int* lane_pts;            // [q][4][128][2]
@@ -61,6 +75,26 @@ struct OvSources {                  // what one run reads, per frame q
     int dist_cnt_stride;
 };
 
+struct OvObjects {                  // the boxes one run reads, per frame q (null / 0 with its stage off)
+    const int* det_xyxy;            // [q][det_cap][4]
+    const int* det_cls;             // [q][det_cap]
+    const int* det_cnt;             // det_cnt[q * det_cnt_stride]
+    int det_cap, det_cnt_stride;
+    const unsigned char* trk_tlwh;  // row k of frame q: 4 doubles at trk_tlwh + q * trk_frame_bytes + k * trk_row_bytes
+    const unsigned char* trk_cls;   // its class, an int at trk_cls + q * trk_cls_frame_bytes + k * trk_cls_row_bytes
+    const unsigned char* trk_act;   // its is_activated, an int at the strides of trk_tlwh, or null: every row is
+    const unsigned char* trk_cnt;   // rows of frame q: an int at trk_cnt + q * trk_cnt_bytes
+    size_t trk_frame_bytes, trk_row_bytes, trk_cls_frame_bytes, trk_cls_row_bytes, trk_cnt_bytes;
+    int trk_cap;
+    const uint32_t *det_colors, *trk_colors;   // packed class colours
+    int n_det_colors, n_trk_colors;
+    double min_box_area;
+    int radii;                      // overlay_obj_radii of the three thicknesses
+    OverlayObject* recs;            // [q][det_cap + trk_cap]: detections in their slots, tracks behind det_cap
+    int* rec_cnt;                   // [q][2]: detections, track rows
+    int lds_recs;                   // records of a frame the streaming pass stages in LDS
+};
+
 struct OvStyle {                    // colours packed as overlay_pack_bgr does
     uint32_t lane[4], offset, area, collision[4], dist;
     OverlayAlpha lane_w, area_w;
@@ -75,10 +109,14 @@ struct OvDev {
     uint32_t* any;                  // [frames][H][rw]
     uint32_t* detail;               // [frames][H][rw][8]
     int* flags;                     // [frames], null for the bird view
-    int stages;                     // ADAS_OVERLAY_LANES | AREA | DISTANCE of this launch
+    int stages;                     // ADAS_OVERLAY_LANES | AREA | DISTANCE | DETECTIONS | TRACKS of this launch
     int direct;                     // lanes are written, not blended (the bird view)
     const uint8_t* src;
     uint8_t* dst;
+};
+
+struct OvDevObj : OvDev {          // what the kernels of a run with the object layer take; the others take the OvDev they always took
+    OvObjects o;
 };
 
 __device__ __forceinline__ int ov_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -95,21 +133,68 @@ struct LdsRowOps {   // overlay_poly_edge_row on a band's LDS bitmaps
     __device__ void toggle(int t) { atomicXor(togw + (t >> 5), 1u << (t & 31)); }
 };
 
-// grid (ceil(H / band), frames); dynamic LDS: OV_PLANES * band * rw words + OV_LIST ints.  One workgroup owns rows [y0, y0 + band) of one
+__device__ __forceinline__ OverlayObjStyle ov_obj_style(const OvDevObj& d, const int* hw) {   // hw: [3][OV_HW]
+    OverlayObjStyle s;
+    s.radii = d.o.radii;
+    s.hw = hw;
+    s.hw_stride = OV_HW;
+    return s;
+}
+__device__ __forceinline__ void ov_obj_halfwidths(const OvDevObj& d, int which, int* hw) {
+    overlay_disc_halfwidths((d.o.radii >> (8 * which)) & 0xff, hw + which * OV_HW);
+}
+
+// grid (frames): one record per box of the frame.  Only the records' bounds need the radii, not the half-widths.
+__global__ __launch_bounds__(OV_THREADS) void overlay_objects_kernel(OvDevObj d) {
+    const size_t f = blockIdx.x;
+    const int slots = d.o.det_cap + d.o.trk_cap;
+    OverlayObject* recs = d.o.recs + f * slots;
+    const OverlayObjStyle s = ov_obj_style(d, nullptr);
+    int nd = 0, nt = 0;
+    if (d.stages & ADAS_OVERLAY_DETECTIONS) nd = ov_clampi(d.o.det_cnt[f * d.o.det_cnt_stride], 0, d.o.det_cap);
+    if (d.stages & ADAS_OVERLAY_TRACKS) nt = ov_clampi(*(const int*)(d.o.trk_cnt + f * d.o.trk_cnt_bytes), 0, d.o.trk_cap);
+    for (int i = threadIdx.x; i < nd; i += OV_THREADS) {
+        const size_t r = f * d.o.det_cap + i;
+        recs[i] = overlay_make_detection(d.o.det_xyxy + r * 4, overlay_class_colour(d.o.det_cls[r], d.o.det_colors, d.o.n_det_colors), s, d.W, d.H);
+    }
+    for (int k = threadIdx.x; k < nt; k += OV_THREADS) {
+        const size_t at = f * d.o.trk_frame_bytes + k * d.o.trk_row_bytes;
+        const int act = d.o.trk_act ? *(const int*)(d.o.trk_act + at) : 1;
+        const int cls = *(const int*)(d.o.trk_cls + f * d.o.trk_cls_frame_bytes + k * d.o.trk_cls_row_bytes);
+        recs[d.o.det_cap + k] = overlay_make_track((const double*)(d.o.trk_tlwh + at), act, d.o.min_box_area,
+                                                   overlay_class_colour(cls, d.o.trk_colors, d.o.n_trk_colors), s, d.W, d.H);
+    }
+    if (threadIdx.x == 0) {
+        d.o.rec_cnt[2 * f] = nd;
+        d.o.rec_cnt[2 * f + 1] = nt;
+    }
+}
+
+// grid (ceil(H / band), frames); dynamic LDS: nplanes * band * rw words + OV_LIST ints (+ 3 * OV_HW ints with the object layer).  One workgroup owns rows [y0, y0 + band) of one
 // frame: it builds their coverage in LDS and stores the words that are not zero (the planes are zero between runs).
-__global__ __launch_bounds__(OV_THREADS) void overlay_mark_kernel(OvDev d) {
+// OBJ: the kernel of a run with the object layer (two more planes, the boxes' runs).  Without it no object code is compiled in and the plane
+// count is the constant it was: a run with both stages off, and the bird view's, execute the code they executed before the layer existed.
+template <bool OBJ, class DEV>
+__device__ __forceinline__ void overlay_mark_body(const DEV& d) {
+    constexpr int NPLANES = OBJ ? OV_OBJ_PLANES : OV_PLANES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int hw[2][ADAS_OVERLAY_MAX_RADIUS + 1];
     __shared__ int bad, listed;
     const size_t f = blockIdx.y;
     const int tid = threadIdx.x;
     const int band = d.band, rw = d.rw, per = band * rw;
-    uint32_t* planes = (uint32_t*)smem;                 // [OV_PLANES][band][rw]: lanes 0..3, area (edges, then the whole fill), distance, toggles
-    int* list = (int*)(planes + OV_PLANES * per);       // [OV_LIST] edges that meet the band
+    constexpr bool objs = OBJ;
+    uint32_t* planes = (uint32_t*)smem;                 // [nplanes][band][rw]: lanes 0..3, area (edges, then the whole fill), distance, toggles,
+                                                        // and with the object layer detections, tracks
+    int* list = (int*)(planes + NPLANES * per);         // [OV_LIST] edges that meet the band
+    int* ohw = list + OV_LIST;                          // [3][OV_HW], with the object layer only: the static LDS stays what it was without it
     const int y0 = blockIdx.x * band;
     const int rows = d.H - y0 < band ? d.H - y0 : band;
-    for (int i = tid; i < OV_PLANES * per; i += OV_THREADS) planes[i] = 0u;
+    for (int i = tid; i < NPLANES * per; i += OV_THREADS) planes[i] = 0u;
     if (tid < 2) overlay_disc_halfwidths(tid == 0 ? d.st.r_lane : d.st.r_dist, hw[tid]);
+    else if constexpr (OBJ) {
+        if (tid < 5) ov_obj_halfwidths(d, tid - 2, ohw);
+    }
     if (tid == 0) bad = 0;
     __syncthreads();
     // ---- the polygon
@@ -173,6 +258,28 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_mark_kernel(OvDev d) {
             }
         }
     }
+    if constexpr (OBJ) {   // ---- boxes: every (record, row) pair ORs the runs of the record's segments on the row, and a track its tint region's
+        const OverlayObjStyle os = ov_obj_style(d, ohw);
+        const int nd = d.o.rec_cnt[2 * f], nt = d.o.rec_cnt[2 * f + 1];
+        const OverlayObject* recs = d.o.recs + f * (d.o.det_cap + d.o.trk_cap);
+        for (int t = tid; t < (nd + nt) * rows; t += OV_THREADS) {
+            const int i = t / rows, r = t - i * rows, y = y0 + r;
+            const OverlayObject o = recs[i < nd ? i : d.o.det_cap + (i - nd)];
+            if (y < o.by0 || y > o.by1) continue;   // an empty box (nothing inside the image, or a filtered track) fails this
+            uint32_t* roww = planes + (o.kind == OV_OBJ_DET ? 7 : 8) * per + r * rw;
+            const int ns = overlay_object_segments(o);
+            for (int k = 0; k < ns; ++k) {
+                long long ax, ay, bx, by, xl, xr;
+                const int* shw;
+                const int R = overlay_object_segment(o, k, os, &ax, &ay, &bx, &by, &shw);
+                if (!overlay_seg_row(ax, ay, bx, by, R, shw, y, &xl, &xr)) continue;
+                if (xl < 0) xl = 0;
+                if (xr > d.W - 1) xr = d.W - 1;
+                if (xl <= xr) ov_lds_span(roww, (int)xl, (int)xr);
+            }
+            if (o.kind == OV_OBJ_TRACK && y >= o.y1 && y < o.y2 && o.x1 < o.x2) ov_lds_span(roww, o.x1, o.x2 - 1);   // 0 <= x1, x2 <= W: clamped
+        }
+    }
     __syncthreads();
     if (n > 0 && tid < rows) {   // the prefix XOR of a row is sequential in its words: one lane per row turns the toggles into the interior
         uint32_t carry = 0u;
@@ -188,15 +295,19 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_mark_kernel(OvDev d) {
     for (int i = tid; i < rows * rw; i += OV_THREADS) {
         const uint4 lo = make_uint4(planes[i], planes[per + i], planes[2 * per + i], planes[3 * per + i]);
         const uint32_t ar = planes[4 * per + i], di = planes[5 * per + i];
-        const uint32_t any = lo.x | lo.y | lo.z | lo.w | ar | di;
+        const uint32_t de = objs ? planes[7 * per + i] : 0u, tr = objs ? planes[8 * per + i] : 0u;
+        const uint32_t any = lo.x | lo.y | lo.z | lo.w | ar | di | de | tr;
         if (!any) continue;
         const size_t w = (f * d.H + y0) * (size_t)rw + i;
         uint4* q = reinterpret_cast<uint4*>(d.detail + w * 8);
         q[0] = lo;
-        q[1] = make_uint4(ar, di, 0u, 0u);
+        q[1] = make_uint4(ar, di, de, tr);
         d.any[w] = any;
     }
 }
+
+__global__ __launch_bounds__(OV_THREADS) void overlay_mark_kernel(OvDev d) { overlay_mark_body<false>(d); }
+__global__ __launch_bounds__(OV_THREADS) void overlay_mark_objects_kernel(OvDevObj d) { overlay_mark_body<true>(d); }
 
 // frame f's colours after the offset rule and the collision table
 __device__ __forceinline__ OverlayStyle ov_frame_style(const OvDev& d, size_t f) {
@@ -227,8 +338,11 @@ struct OvWord {
     size_t at;        // index of the cached word, ~0: none
     uint32_t any;
     uint4 lanes;
-    uint2 rest;       // area, distance
+    uint4 rest;       // area, distance, detections, tracks
 };
+// OBJ: the kernel of a run with the object layer.  Without it (OBJ = false) the two spare detail words are not read and no object code
+// is compiled in: a run with both stages off executes the code it executed before the layer existed.
+template <bool OBJ>
 __device__ __forceinline__ uint32_t ov_bits(const OvDev& d, OvWord& c, size_t f, int y, int x) {
     const size_t w = (f * d.H + y) * (size_t)d.rw + (x >> 5);
     if (w != c.at) {
@@ -236,13 +350,19 @@ __device__ __forceinline__ uint32_t ov_bits(const OvDev& d, OvWord& c, size_t f,
         c.any = d.any[w];
         if (c.any) {
             c.lanes = *reinterpret_cast<const uint4*>(d.detail + w * 8);
-            c.rest = *reinterpret_cast<const uint2*>(d.detail + w * 8 + 4);
+            if (OBJ) {
+                c.rest = *reinterpret_cast<const uint4*>(d.detail + w * 8 + 4);
+            } else {
+                const uint2 r = *reinterpret_cast<const uint2*>(d.detail + w * 8 + 4);
+                c.rest = make_uint4(r.x, r.y, 0u, 0u);
+            }
         }
     }
     const uint32_t b = 1u << (x & 31);
     if (!(c.any & b)) return 0u;
     return ((c.lanes.x & b) ? 1u : 0u) | ((c.lanes.y & b) ? 2u : 0u) | ((c.lanes.z & b) ? 4u : 0u) | ((c.lanes.w & b) ? 8u : 0u) |
-           ((c.rest.x & b) ? OV_BIT_AREA : 0u) | ((c.rest.y & b) ? OV_BIT_DIST : 0u);
+           ((c.rest.x & b) ? OV_BIT_AREA : 0u) | ((c.rest.y & b) ? OV_BIT_DIST : 0u) |
+           (OBJ ? (((c.rest.z & b) ? OV_BIT_DET : 0u) | ((c.rest.w & b) ? OV_BIT_TRK : 0u)) : 0u);
 }
 
 struct __attribute__((packed, aligned(1))) OvPiece1 {   // a 16-byte piece at any address
@@ -272,17 +392,79 @@ __device__ __forceinline__ void ov_locate(const OvDev& d, size_t f, uint32_t b0,
     }
 }
 // second step of the fetch: the first word's detail, when something is drawn there (issued for every piece of a thread before any is drawn)
+template <bool OBJ>
 __device__ __forceinline__ void ov_fetch_detail(const OvDev& d, OvSpan& s) {
     if (s.x1 >= 0 && s.w.any) {
         s.w.lanes = *reinterpret_cast<const uint4*>(d.detail + s.w.at * 8);
-        s.w.rest = *reinterpret_cast<const uint2*>(d.detail + s.w.at * 8 + 4);
+        if (OBJ) {
+            s.w.rest = *reinterpret_cast<const uint4*>(d.detail + s.w.at * 8 + 4);
+        } else {
+            const uint2 r = *reinterpret_cast<const uint2*>(d.detail + s.w.at * 8 + 4);
+            s.w.rest = make_uint4(r.x, r.y, 0u, 0u);
+        }
     }
 }
+
+// the frame's records as the streaming pass sees them: the first `nlds` of the list in LDS, the rest in their slots in HBM
+struct OvObjCtx {
+    int nd, n;                      // detections, detections + track rows
+    int nlds, det_cap;
+    const OverlayObject* lds;
+    const OverlayObject* slots;     // the frame's [det_cap + trk_cap]
+    OverlayObjStyle s;
+};
+// byte k (0 .. 15) of a piece held as two 64-bit halves, k not known at compile time: shifts, not an indexed register array
+__device__ __forceinline__ int ov_get_byte(unsigned long long lo, unsigned long long hi, int k) {
+    return (int)(((k < 8 ? lo : hi) >> (8 * (k & 7))) & 0xffull);
+}
+__device__ __forceinline__ void ov_put_byte(unsigned long long& lo, unsigned long long& hi, int k, int b) {
+    const unsigned long long m = 0xffull << (8 * (k & 7)), q = (unsigned long long)(unsigned)b << (8 * (k & 7));
+    if (k < 8) lo = (lo & ~m) | q;
+    else hi = (hi & ~m) | q;
+}
+// D9 on the pixels of a piece that carry an object bit (bit p of `om`: pixel p of the piece; pixel 0 is (s.x, s.y), whose channel s.c is
+// byte 0).  The frame's records are walked once, in order: a record whose box misses the box of the piece's marked pixels is skipped, the
+// others ask each marked pixel for its membership (once per pixel) and rewrite that pixel's bytes of the piece -- every pixel still
+// sees the records in order.  One copy of the rules per piece: the loops are not unrolled.
+__device__ __forceinline__ void ov_fold_piece(const OvDev& d, const OvObjCtx& oc, int n, const OvSpan& s, uint32_t om, uint32_t v[4]) {
+    unsigned long long lo = (unsigned long long)v[0] | ((unsigned long long)v[1] << 32), hi = (unsigned long long)v[2] | ((unsigned long long)v[3] << 32);
+    int xa = d.W, xb = -1, ya = d.H, yb = -1;
+    {
+        int x = s.x, y = s.y;
+        for (uint32_t m = om; m; m >>= 1) {
+            if (m & 1u) {
+                xa = x < xa ? x : xa; xb = x > xb ? x : xb;
+                ya = y < ya ? y : ya; yb = y > yb ? y : yb;
+            }
+            if (++x == d.W) { x = 0; ++y; }
+        }
+    }
+    for (int i = 0; i < oc.n; ++i) {
+        const OverlayObject* o = i < oc.nlds ? oc.lds + i : oc.slots + (i < oc.nd ? i : oc.det_cap + (i - oc.nd));
+        if (o->bx0 > xb || o->bx1 < xa || o->by0 > yb || o->by1 < ya) continue;
+        int x = s.x, y = s.y, k0 = -s.c;   // k0: where the pixel's channel 0 lies in the piece (outside it for a pixel cut by the piece's ends)
+        for (uint32_t m = om; m; m >>= 1, k0 += 3) {
+            if (m & 1u) {
+                const int ops = overlay_object_ops(*o, x, y, oc.s);
+                if (ops) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        if (k0 + c >= 0 && k0 + c < n) ov_put_byte(lo, hi, k0 + c, overlay_object_channel(ov_get_byte(lo, hi, k0 + c), ops, o->colour, c));
+                }
+            }
+            if (++x == d.W) { x = 0; ++y; }
+        }
+    }
+    v[0] = (uint32_t)lo; v[1] = (uint32_t)(lo >> 32); v[2] = (uint32_t)hi; v[3] = (uint32_t)(hi >> 32);
+}
 // draws on the bytes held in v (byte k in bits 8 (k & 3) of v[k >> 2])
-__device__ __forceinline__ void ov_draw_piece(const OvDev& d, size_t f, const OverlayStyle& st, int n, OvSpan& s, uint32_t v[4]) {
+template <bool OBJ>
+__device__ __forceinline__ void ov_draw_piece(const OvDev& d, size_t f, const OverlayStyle& st, const OvObjCtx& oc, int n, OvSpan& s, uint32_t v[4]) {
     if (s.quiet) return;
     int c = s.c, y = s.y, x = s.x;
-    uint32_t bits = ov_bits(d, s.w, f, y, x);
+    uint32_t bits = ov_bits<OBJ>(d, s.w, f, y, x);
+    uint32_t om = 0u, pbit = 1u;   // the piece's pixels that carry an object bit and no distance disc (DISTANCE overrides everything)
+    if (OBJ && (bits & (OV_BIT_DET | OV_BIT_TRK)) && !(bits & OV_BIT_DIST)) om = 1u;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         if (k < n) {
@@ -294,17 +476,46 @@ __device__ __forceinline__ void ov_draw_piece(const OvDev& d, size_t f, const Ov
             if (++c == 3) {
                 c = 0;
                 if (++x == d.W) { x = 0; ++y; }
-                if (k + 1 < n) bits = ov_bits(d, s.w, f, y, x);
+                if (k + 1 < n) {
+                    bits = ov_bits<OBJ>(d, s.w, f, y, x);
+                    if (OBJ) {
+                        pbit <<= 1;
+                        if ((bits & (OV_BIT_DET | OV_BIT_TRK)) && !(bits & OV_BIT_DIST)) om |= pbit;
+                    }
+                }
             }
         }
     }
+    if (OBJ && om) ov_fold_piece(d, oc, n, s, om, v);   // no pixel of the piece has an object bit: the path ends here, as before the layer
 }
 
 constexpr int OV_UNROLL = 4;   // pieces a thread has in flight: the pass is a chain of dependent loads (frame bytes, ANY word, detail words)
 
 // grid (blocks, frames); a frame's 3HW bytes = a head of < 16 bytes up to the destination's first 16-byte boundary, aligned pieces, a tail
-__global__ __launch_bounds__(OV_THREADS) void overlay_stream_kernel(OvDev d) {
+// dynamic LDS, only with the object layer (OBJ): three half-width tables, then the frame's first lds_recs records
+template <bool OBJ, class DEV>
+__device__ __forceinline__ void overlay_stream_body(const DEV& d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char ov_smem[];
     const size_t f = blockIdx.y;
+    OvObjCtx oc;
+    oc.nd = oc.n = oc.nlds = 0;
+    if constexpr (OBJ) {
+        int* ohw = (int*)ov_smem;
+        uint4* lrec = (uint4*)(ov_smem + 3 * OV_HW * 4);
+        if (threadIdx.x < 3) ov_obj_halfwidths(d, threadIdx.x, ohw);
+        oc.nd = d.o.rec_cnt[2 * f];
+        oc.n = oc.nd + d.o.rec_cnt[2 * f + 1];
+        oc.nlds = oc.n < d.o.lds_recs ? oc.n : d.o.lds_recs;
+        oc.det_cap = d.o.det_cap;
+        oc.slots = d.o.recs + f * (d.o.det_cap + d.o.trk_cap);
+        oc.lds = (const OverlayObject*)lrec;
+        oc.s = ov_obj_style(d, ohw);
+        for (int t = threadIdx.x; t < oc.nlds * 3; t += OV_THREADS) {
+            const int i = t / 3, q = t - i * 3;
+            lrec[t] = reinterpret_cast<const uint4*>(oc.slots + (i < oc.nd ? i : oc.det_cap + (i - oc.nd)))[q];
+        }
+        __syncthreads();
+    }
     const uint32_t FB = (uint32_t)d.H * d.W * 3u;   // < 2^28: the image limits
     const uint8_t* src = d.src + f * FB;   // may be dst: no restrict
     uint8_t* dst = d.dst + f * FB;
@@ -334,12 +545,12 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_stream_kernel(OvDev d) {
         }
 #pragma unroll
         for (int u = 0; u < OV_UNROLL; ++u)
-            if (i0 + u * stride < pieces) ov_fetch_detail(d, sp[u]);
+            if (i0 + u * stride < pieces) ov_fetch_detail<OBJ>(d, sp[u]);
 #pragma unroll
         for (int u = 0; u < OV_UNROLL; ++u) {
             const uint32_t i = i0 + u * stride;
             if (i < pieces) {
-                ov_draw_piece(d, f, st, 16, sp[u], v[u]);
+                ov_draw_piece<OBJ>(d, f, st, oc, 16, sp[u], v[u]);
                 *reinterpret_cast<uint4*>(dst + head + i * 16u) = make_uint4(v[u][0], v[u][1], v[u][2], v[u][3]);
             }
         }
@@ -349,15 +560,31 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_stream_kernel(OvDev d) {
         const int n = (int)(threadIdx.x == 0 ? head : tail);
         if (n > 0) {
             uint32_t v[4] = {0u, 0u, 0u, 0u};
-            for (int k = 0; k < n; ++k) v[k >> 2] |= (uint32_t)src[b0 + k] << (8 * (k & 3));
+            if (OBJ) {   // the larger kernel keeps an indexed v[] in scratch: go through 64-bit shifts instead
+                unsigned long long lo = 0ull, hi = 0ull;
+                for (int k = 0; k < n; ++k) ov_put_byte(lo, hi, k, src[b0 + k]);
+                v[0] = (uint32_t)lo; v[1] = (uint32_t)(lo >> 32); v[2] = (uint32_t)hi; v[3] = (uint32_t)(hi >> 32);
+            } else {
+                for (int k = 0; k < n; ++k) v[k >> 2] |= (uint32_t)src[b0 + k] << (8 * (k & 3));
+            }
             OvSpan sp;
             ov_locate(d, f, b0, n, sp);
-            ov_fetch_detail(d, sp);
-            ov_draw_piece(d, f, st, n, sp, v);
-            for (int k = 0; k < n; ++k) dst[b0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+            ov_fetch_detail<OBJ>(d, sp);
+            ov_draw_piece<OBJ>(d, f, st, oc, n, sp, v);
+            if (OBJ) {
+                const unsigned long long lo = (unsigned long long)v[0] | ((unsigned long long)v[1] << 32), hi = (unsigned long long)v[2] | ((unsigned long long)v[3] << 32);
+                for (int k = 0; k < n; ++k) dst[b0 + k] = (uint8_t)ov_get_byte(lo, hi, k);
+            } else {
+                for (int k = 0; k < n; ++k) dst[b0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+            }
         }
     }
 }
+
+// Two kernels, so that each has its own launch bounds: the pass without the object layer keeps the bounds (and the code) it had before the
+// layer existed; the pass with it is held to the 4 waves per SIMD of the other one.
+__global__ __launch_bounds__(OV_THREADS) void overlay_stream_kernel(OvDev d) { overlay_stream_body<false>(d); }
+__global__ __launch_bounds__(OV_THREADS, OV_OBJ_WAVES) void overlay_stream_objects_kernel(OvDevObj d) { overlay_stream_body<true>(d); }
 
 // zeroes the words the mark kernel set: one thread per ANY word of frames [0, frames)
 __global__ __launch_bounds__(OV_THREADS) void overlay_clean_kernel(OvDev d, size_t words) {
@@ -409,6 +636,13 @@ struct adas_overlay {
     int dst_frames = 0;                                     // frames [0, dst_frames) of d_dst have been written by some run
     int run_frames = 0;
     hipStream_t last = 0;
+    // the object layer
+    adas_overlay_object_style os;
+    uint32_t* colors[2] = {nullptr, nullptr};               // packed class colours: [0] detections, [1] tracks
+    int n_colors[2] = {0, 0};
+    OverlayObject* recs = nullptr;                          // [max_batch][rec_slots]
+    int rec_slots = 0;
+    int* rec_cnt = nullptr;                                 // [max_batch][2]
     size_t frame_bytes() const { return (size_t)p.src_h * p.src_w * 3; }
 };
 
@@ -447,8 +681,8 @@ static void overlay_style(const adas_overlay_params& p, int bird, OvStyle* s) {
     s->r_dist = p.distance_radius;
 }
 
-static int overlay_band(int rw) {   // rows whose OV_PLANES planes fit the LDS budget: 8 up to 5248 columns, 2 at 16384
-    const int b = OV_LDS_WORDS / (OV_PLANES * rw);
+static int overlay_band(int rw, int nplanes) {   // rows whose planes fit the LDS budget: 8 up to 5248 columns, 2 at 16384 (OV_PLANES planes)
+    const int b = OV_LDS_WORDS / (nplanes * rw);
     return b < 1 ? 1 : (b > OV_BAND ? OV_BAND : b);
 }
 
@@ -457,16 +691,42 @@ static unsigned overlay_grid(size_t items) {
     return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-// the launches of one run; `s` holds the sources, bird_pts / bird_cnt (stride bird_cnt_stride) the bird view's
+// room for `slots` records per frame.  Allocates: not inside a stream capture (adas_pipeline_set_overlay_stages reserves ahead of the step)
+static int overlay_reserve_records(adas_overlay* h, int slots) {
+    if (slots <= h->rec_slots) return ADAS_OK;
+    ADAS_HIP_TRY(hipDeviceSynchronize());   // a run in flight may still read the old table
+    if (h->recs) (void)hipFree(h->recs);
+    h->recs = nullptr;
+    h->rec_slots = 0;
+    ADAS_HIP_TRY(hipMalloc((void**)&h->recs, (size_t)h->max_batch * slots * sizeof(OverlayObject)));
+    h->rec_slots = slots;
+    adas::bump_config_generation();   // a captured step holds the old table's address in its kernel arguments
+    return ADAS_OK;
+}
+
+namespace adas {
+int overlay_reserve_objects(::adas_overlay* h, int det_cap, int trk_cap) { return h ? overlay_reserve_records(h, det_cap + trk_cap) : ADAS_OK; }
+}  // namespace adas
+
+static int overlay_check_object_style(const adas_overlay_object_style* p, const char* who) {
+    ADAS_REQUIRE(p->det_rect_thickness >= 1 && p->det_rect_thickness <= ADAS_OVERLAY_MAX_THICKNESS && p->det_arm_thickness >= 1 &&
+                     p->det_arm_thickness <= ADAS_OVERLAY_MAX_THICKNESS && p->track_thickness >= 1 && p->track_thickness <= ADAS_OVERLAY_MAX_THICKNESS,
+                 ADAS_ERR_INVALID, "%s: thicknesses must be in [1, %d] (got %d, %d, %d)", who, ADAS_OVERLAY_MAX_THICKNESS, p->det_rect_thickness,
+                 p->det_arm_thickness, p->track_thickness);
+    ADAS_REQUIRE(p->min_box_area == p->min_box_area, ADAS_ERR_INVALID, "%s: min_box_area is not a number", who);
+    return ADAS_OK;
+}
+
+// the launches of one run; `s` holds the sources, bird_pts / bird_cnt (stride bird_cnt_stride) the bird view's, `obj` the boxes (stages 16 / 32)
 static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvSources s, const int* bird_pts, const int* bird_cnt, int bird_cnt_stride,
-                          uint8_t* d_bird, int stages, int frames, hipStream_t st) {
-    const int frame_stages = stages & (ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | ADAS_OVERLAY_DISTANCE);
+                          uint8_t* d_bird, int stages, int frames, hipStream_t st, const OvObjects* obj = nullptr) {
+    const int frame_stages = stages & (ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | ADAS_OVERLAY_DISTANCE | OV_OBJ_STAGES);
     if (frame_stages) {
         if (!dst) {
             int rc = overlay_own_buffer(h);
             if (rc) return rc;
         }
-        OvDev d;
+        OvDevObj d;
         memset(&d, 0, sizeof(d));
         d.s = s;
         overlay_style(h->p, 0, &d.st);
@@ -475,18 +735,43 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
         d.stages = frame_stages;
         d.src = src;
         d.dst = dst ? dst : h->d_dst;
-        d.band = overlay_band(d.rw);
-        hipLaunchKernelGGL(overlay_mark_kernel, dim3((unsigned)((d.H + d.band - 1) / d.band), (unsigned)frames), dim3(OV_THREADS),
-                           ((size_t)OV_PLANES * d.band * d.rw + OV_LIST) * 4, st, d);
+        int nplanes = OV_PLANES;
+        size_t stream_lds = 0;
+        if (frame_stages & OV_OBJ_STAGES) {   // one more launch, ahead of the coverage: the boxes' records
+            d.o = *obj;
+            if (!(frame_stages & ADAS_OVERLAY_DETECTIONS)) d.o.det_cap = 0;
+            if (!(frame_stages & ADAS_OVERLAY_TRACKS)) d.o.trk_cap = 0;
+            int rc = overlay_reserve_records(h, d.o.det_cap + d.o.trk_cap);
+            if (rc) return rc;
+            d.o.det_colors = h->colors[0]; d.o.n_det_colors = h->n_colors[0];
+            d.o.trk_colors = h->colors[1]; d.o.n_trk_colors = h->n_colors[1];
+            d.o.min_box_area = h->os.min_box_area;
+            d.o.radii = overlay_obj_radii(h->os.det_rect_thickness, h->os.det_arm_thickness, h->os.track_thickness);
+            d.o.recs = h->recs; d.o.rec_cnt = h->rec_cnt;
+            d.o.lds_recs = d.o.det_cap + d.o.trk_cap < OV_OBJ_LDS ? d.o.det_cap + d.o.trk_cap : OV_OBJ_LDS;
+            nplanes = OV_OBJ_PLANES;
+            stream_lds = (size_t)3 * OV_HW * 4 + (size_t)d.o.lds_recs * sizeof(OverlayObject);
+            hipLaunchKernelGGL(overlay_objects_kernel, dim3((unsigned)frames), dim3(OV_THREADS), 0, st, d);
+            ADAS_HIP_TRY(hipGetLastError());
+        }
+        d.band = overlay_band(d.rw, nplanes);
+        const OvDev plain = d;   // the kernels without the object layer take the arguments they always took
+        if (frame_stages & OV_OBJ_STAGES)
+            hipLaunchKernelGGL(overlay_mark_objects_kernel, dim3((unsigned)((d.H + d.band - 1) / d.band), (unsigned)frames), dim3(OV_THREADS),
+                               ((size_t)OV_OBJ_PLANES * d.band * d.rw + OV_LIST + 3 * OV_HW) * 4, st, d);
+        else
+            hipLaunchKernelGGL(overlay_mark_kernel, dim3((unsigned)((d.H + d.band - 1) / d.band), (unsigned)frames), dim3(OV_THREADS),
+                               ((size_t)OV_PLANES * d.band * d.rw + OV_LIST) * 4, st, plain);
         ADAS_HIP_TRY(hipGetLastError());
         const size_t pieces = h->frame_bytes() / 16 + 2;
         unsigned gx = overlay_grid(pieces);
         const unsigned per = (unsigned)((2048 + frames - 1) / frames);   // about 2048 workgroups in all, grid-stride the rest
         if (gx > per) gx = per;
-        hipLaunchKernelGGL(overlay_stream_kernel, dim3(gx, (unsigned)frames), dim3(OV_THREADS), 0, st, d);
+        if (frame_stages & OV_OBJ_STAGES) hipLaunchKernelGGL(overlay_stream_objects_kernel, dim3(gx, (unsigned)frames), dim3(OV_THREADS), stream_lds, st, d);
+        else hipLaunchKernelGGL(overlay_stream_kernel, dim3(gx, (unsigned)frames), dim3(OV_THREADS), 0, st, plain);
         ADAS_HIP_TRY(hipGetLastError());
         const size_t words = (size_t)frames * d.H * d.rw;
-        hipLaunchKernelGGL(overlay_clean_kernel, dim3(overlay_grid(words)), dim3(OV_THREADS), 0, st, d, words);
+        hipLaunchKernelGGL(overlay_clean_kernel, dim3(overlay_grid(words)), dim3(OV_THREADS), 0, st, plain, words);
         ADAS_HIP_TRY(hipGetLastError());
         if (!dst && frames > h->dst_frames) h->dst_frames = frames;
         h->run_frames = frames;
@@ -505,7 +790,7 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
         d.stages = ADAS_OVERLAY_LANES;
         d.direct = 1;
         d.dst = d_bird;
-        d.band = overlay_band(d.rw);
+        d.band = overlay_band(d.rw, OV_PLANES);
         hipLaunchKernelGGL(overlay_mark_kernel, dim3((unsigned)((d.H + d.band - 1) / d.band), (unsigned)frames), dim3(OV_THREADS),
                            ((size_t)OV_PLANES * d.band * d.rw + OV_LIST) * 4, st, d);
         ADAS_HIP_TRY(hipGetLastError());
@@ -517,103 +802,60 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
     return ADAS_OK;
 }
 
-#define OV_RUN_REQUIRE(name, frames)                                                                                                          \
-    ADAS_REQUIRE(h && (frames) > 0 && (frames) <= h->max_batch, ADAS_ERR_INVALID, name ": bad argument (%d frames, the handle holds %d)", (int)(frames), \
-                 h ? h->max_batch : 0);                                                                                                       \
-    ADAS_REQUIRE(!(stages & ~15), ADAS_ERR_INVALID, name ": unknown stage bits 0x%x", stages);                                                \
-    ADAS_REQUIRE(!(stages & 7) || d_src_bgr, ADAS_ERR_INVALID, name ": the frame stages need source frames");                                 \
+// who: the entry point's name; mask: the stage bits it accepts
+#define OV_RUN_REQUIRE(who, frames, mask)                                                                                                     \
+    ADAS_REQUIRE(h && (frames) > 0 && (frames) <= h->max_batch, ADAS_ERR_INVALID, "%s: bad argument (%d frames, the handle holds %d)", who,   \
+                 (int)(frames), h ? h->max_batch : 0);                                                                                        \
+    ADAS_REQUIRE(!(stages & ~(mask)), ADAS_ERR_INVALID, "%s: unknown stage bits 0x%x", who, stages);                                          \
+    ADAS_REQUIRE(!(stages & (mask) & ~ADAS_OVERLAY_BIRD) || d_src_bgr, ADAS_ERR_INVALID, "%s: the frame stages need source frames", who);     \
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (h->p.bird_h > 0 && d_bird_bgr), ADAS_ERR_INVALID,                                          \
-                 name ": the bird stage needs a handle created with a bird-view size and a bird-view image")
+                 "%s: the bird stage needs a handle created with a bird-view size and a bird-view image", who)
 
-extern "C" {
-
-int adas_overlay_default_params(adas_overlay_params* p) {
-    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_overlay_default_params: null argument");
-    memset(p, 0, sizeof(*p));
-    p->lane_radius = 3; p->distance_radius = 4; p->bird_radius = 10;
-    p->lane_alpha = 0.3; p->area_alpha = 0.85;
-    const uint8_t lanes[4][3] = {{255, 0, 0}, {46, 139, 87}, {50, 205, 50}, {0, 255, 255}};
-    const uint8_t coll[4][3] = {{0, 255, 255}, {0, 255, 0}, {0, 102, 255}, {0, 0, 255}};
-    memcpy(p->lane_colors, lanes, 12);
-    memcpy(p->collision_colors, coll, 12);
-    p->offset_color[0] = 0; p->offset_color[1] = 0; p->offset_color[2] = 255;
-    p->area_color[0] = 255; p->area_color[1] = 191; p->area_color[2] = 0;
-    p->distance_color[0] = p->distance_color[1] = p->distance_color[2] = 255;
-    return ADAS_OK;
-}
-
-int adas_overlay_create(const adas_overlay_params* p, int max_batch, adas_overlay** out) {
-    ADAS_REQUIRE(p && out && max_batch > 0 && max_batch <= 65535, ADAS_ERR_INVALID, "adas_overlay_create: bad argument");
-    ADAS_REQUIRE(p->src_h > 0 && p->src_h <= 4320 && p->src_w > 0 && p->src_w <= 16384, ADAS_ERR_INVALID,
-                 "adas_overlay_create: frames must be 1..4320 rows by 1..16384 columns (got %dx%d)", p->src_h, p->src_w);
-    ADAS_REQUIRE((p->bird_h == 0 && p->bird_w == 0) || (p->bird_h > 0 && p->bird_h <= 4320 && p->bird_w > 0 && p->bird_w <= 16384), ADAS_ERR_INVALID,
-                 "adas_overlay_create: the bird view must be 0x0 (none) or 1..4320 rows by 1..16384 columns (got %dx%d)", p->bird_h, p->bird_w);
-    int rc = overlay_check_style(p, "adas_overlay_create");
-    if (rc) return rc;
-    ADAS_REQUIRE(adas_device_count() > 0, ADAS_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    adas_overlay* h = new (std::nothrow) adas_overlay();
-    ADAS_REQUIRE(h, ADAS_ERR_INVALID, "out of host memory");
-    h->p = *p;
-    h->max_batch = max_batch;
-    h->rw = (p->src_w + 31) / 32;
-    h->bird_rw = (p->bird_w + 31) / 32;
-    const size_t B = max_batch, words = B * p->src_h * h->rw, bwords = B * p->bird_h * h->bird_rw;
-    hipError_t e = hipMalloc((void**)&h->detail, words * 32);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->any, words * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->flags, B * 4);
-    if (e == hipSuccess && bwords) e = hipMalloc((void**)&h->bird_detail, bwords * 32);
-    if (e == hipSuccess && bwords) e = hipMalloc((void**)&h->bird_any, bwords * 4);
-    if (e == hipSuccess) e = hipMemset(h->detail, 0, words * 32);   // the planes are zero between runs
-    if (e == hipSuccess) e = hipMemset(h->any, 0, words * 4);
-    if (e == hipSuccess) e = hipMemset(h->flags, 0, B * 4);
-    if (e == hipSuccess && bwords) e = hipMemset(h->bird_detail, 0, bwords * 32);
-    if (e == hipSuccess && bwords) e = hipMemset(h->bird_any, 0, bwords * 4);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        adas_overlay_destroy(h);
-        return hip_fail(e, "hipMalloc(overlay planes)", __FILE__, __LINE__);
-    }
-    *out = h;
-    return ADAS_OK;
-}
-
-int adas_overlay_destroy(adas_overlay* h) {
-    if (!h) return ADAS_OK;
-    for (void* q : {(void*)h->any, (void*)h->detail, (void*)h->bird_any, (void*)h->bird_detail, (void*)h->flags, (void*)h->d_dst})
-        if (q) (void)hipFree(q);
-    delete h;
-    return ADAS_OK;
-}
-
-int adas_overlay_set_style(adas_overlay* h, const adas_overlay_params* p) {
-    ADAS_REQUIRE(h && p, ADAS_ERR_INVALID, "adas_overlay_set_style: bad argument");
-    int rc = overlay_check_style(p, "adas_overlay_set_style");
-    if (rc) return rc;
-    adas_overlay_params n = *p;
-    n.src_h = h->p.src_h; n.src_w = h->p.src_w; n.bird_h = h->p.bird_h; n.bird_w = h->p.bird_w;
-    h->p = n;
-    adas::bump_config_generation();   // a captured step holds the old style in its kernel arguments
-    return ADAS_OK;
-}
-
-int adas_overlay_run(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
-                     adas_analysis* analysis, uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream) {
-    ADAS_REQUIRE(n_streams > 0 && n_frames > 0, ADAS_ERR_INVALID, "adas_overlay_run: bad argument (%d streams x %d frames)", n_streams, n_frames);
+// adas_overlay_run (mask 15, no post / tracker) and adas_overlay_run_objects (mask 63)
+static int overlay_run_handles(const char* who, int mask, adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
+                               adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker,
+                               uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream) {
+    ADAS_REQUIRE(n_streams > 0 && n_frames > 0, ADAS_ERR_INVALID, "%s: bad argument (%d streams x %d frames)", who, n_streams, n_frames);
     const long long frames = (long long)n_streams * n_frames;
-    OV_RUN_REQUIRE("adas_overlay_run", frames);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || decode, ADAS_ERR_INVALID, "adas_overlay_run: the lane stage needs a decode handle");
+    OV_RUN_REQUIRE(who, frames, mask);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || decode, ADAS_ERR_INVALID, "%s: the lane stage needs a decode handle", who);
     ADAS_REQUIRE(!decode || adas::decode_num_lanes(decode) == 4, ADAS_ERR_INVALID,
-                 "adas_overlay_run: the decoder has num_lanes = %d (CurveLanes); the overlay draws the reference's four lane colours, num_lanes must be 4",
+                 "%s: the decoder has num_lanes = %d (CurveLanes); the overlay draws the reference's four lane colours, num_lanes must be 4", who,
                  adas::decode_num_lanes(decode));
-    ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_AREA | ADAS_OVERLAY_BIRD)) || geometry, ADAS_ERR_INVALID,
-                 "adas_overlay_run: the area and bird stages need a geometry handle");
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || analysis, ADAS_ERR_INVALID, "adas_overlay_run: the distance stage needs an analysis handle");
+    ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_AREA | ADAS_OVERLAY_BIRD)) || geometry, ADAS_ERR_INVALID, "%s: the area and bird stages need a geometry handle",
+                 who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || analysis, ADAS_ERR_INVALID, "%s: the distance stage needs an analysis handle", who);
     ADAS_REQUIRE((!decode || frames <= adas::handle_max_batch(decode)) && (!geometry || frames <= adas::handle_max_batch(geometry)), ADAS_ERR_INVALID,
-                 "adas_overlay_run: %d frames, the decode handle holds %d, the geometry handle %d", (int)frames, adas::handle_max_batch(decode),
+                 "%s: %d frames, the decode handle holds %d, the geometry handle %d", who, (int)frames, adas::handle_max_batch(decode),
                  adas::handle_max_batch(geometry));
     int af = 0;
     ADAS_REQUIRE(!analysis || (adas::analysis_capacity(analysis, nullptr, &af) && frames <= af), ADAS_ERR_INVALID,
-                 "adas_overlay_run: %d frames, the analysis handle holds %d", (int)frames, af);
+                 "%s: %d frames, the analysis handle holds %d", who, (int)frames, af);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || post, ADAS_ERR_INVALID, "%s: the detections stage needs a yolo_post handle", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || tracker, ADAS_ERR_INVALID, "%s: the tracks stage needs a bytetrack handle", who);
+    OvObjects o;
+    memset(&o, 0, sizeof(o));
+    if (stages & ADAS_OVERLAY_DETECTIONS) {
+        ADAS_REQUIRE(frames <= adas::handle_max_batch(post), ADAS_ERR_INVALID, "%s: %d frames, the yolo_post handle holds %d", who, (int)frames,
+                     adas::handle_max_batch(post));
+        const int* cnt = nullptr;
+        adas::post_survivor_views(post, &o.det_xyxy, &o.det_cls, &cnt, &o.det_cap);
+        o.det_cnt = cnt + 2;   // counts[4]: n_found, n_candidates, n_keep, flags
+        o.det_cnt_stride = 4;
+    }
+    if (stages & ADAS_OVERLAY_TRACKS) {
+        ADAS_REQUIRE(n_frames == 1, ADAS_ERR_INVALID,
+                     "%s: the tracks stage draws the tracker's live table, which holds the last frame only: n_frames must be 1 (got %d)", who, n_frames);
+        int ts = 0;
+        adas::tracker_live_views(tracker, &o.trk_cnt, &o.trk_tlwh, &o.trk_frame_bytes, &ts, &o.trk_cap);
+        ADAS_REQUIRE(n_streams <= ts, ADAS_ERR_INVALID, "%s: %d streams, the bytetrack handle holds %d", who, n_streams, ts);
+        o.trk_cnt += offsetof(adas_track_header, n_tracked);
+        o.trk_cnt_bytes = o.trk_frame_bytes;
+        o.trk_row_bytes = sizeof(adas_track);
+        o.trk_cls = o.trk_tlwh + offsetof(adas_track, class_id);
+        o.trk_cls_frame_bytes = o.trk_frame_bytes; o.trk_cls_row_bytes = o.trk_row_bytes;
+        o.trk_act = o.trk_tlwh + offsetof(adas_track, is_activated);
+    }
     OvSources s;
     memset(&s, 0, sizeof(s));
     if (decode) {
@@ -644,23 +886,29 @@ int adas_overlay_run(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_b
         s.dist_pts = pts; s.dist_cap = maxp;
         s.dist_cnt = fr + offsetof(adas_analysis_frame, n_points) / 4; s.dist_cnt_stride = stride;
     }
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, bird_pts, bird_cnt, 8, d_bird_bgr, stages, (int)frames, (hipStream_t)stream);
+    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, bird_pts, bird_cnt, 8, d_bird_bgr, stages, (int)frames, (hipStream_t)stream, &o);
 }
 
-int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points, const int32_t* d_lane_counts,
-                            const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
-                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
-                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
-                            int n_frames, void* stream) {
-    OV_RUN_REQUIRE("adas_overlay_run_arrays", n_frames);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || (d_lane_points && d_lane_counts), ADAS_ERR_INVALID,
-                 "adas_overlay_run_arrays: the lane stage needs lane points and counts");
+// adas_overlay_run_arrays (mask 15, no box arrays) and adas_overlay_run_arrays_objects (mask 63)
+static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points,
+                           const int32_t* d_lane_counts, const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
+                           const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
+                           const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr,
+                           const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts, const double* d_trk_tlwh,
+                           int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages, int n_frames, void* stream) {
+    OV_RUN_REQUIRE(who, n_frames, mask);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || (d_lane_points && d_lane_counts), ADAS_ERR_INVALID, "%s: the lane stage needs lane points and counts",
+                 who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_AREA) || (d_poly && poly_cap > 0 && d_poly_counts && d_area_status), ADAS_ERR_INVALID,
-                 "adas_overlay_run_arrays: the area stage needs a polygon, its counts and the area flags");
+                 "%s: the area stage needs a polygon, its counts and the area flags", who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || (d_dist_points && dist_cap > 0 && d_dist_counts), ADAS_ERR_INVALID,
-                 "adas_overlay_run_arrays: the distance stage needs distance points and counts");
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (d_bird_points && d_bird_counts), ADAS_ERR_INVALID,
-                 "adas_overlay_run_arrays: the bird stage needs bird points and counts");
+                 "%s: the distance stage needs distance points and counts", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (d_bird_points && d_bird_counts), ADAS_ERR_INVALID, "%s: the bird stage needs bird points and counts", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (d_det_xyxy && det_cap > 0 && d_det_cls && d_det_counts), ADAS_ERR_INVALID,
+                 "%s: the detections stage needs boxes, classes and counts", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (d_trk_tlwh && trk_cap > 0 && d_trk_cls && d_trk_counts), ADAS_ERR_INVALID,
+                 "%s: the tracks stage needs boxes, classes and counts", who);
+    ADAS_REQUIRE(det_cap <= (1 << 24) && trk_cap <= (1 << 24), ADAS_ERR_INVALID, "%s: capacities above 2^24 boxes per frame (%d, %d)", who, det_cap, trk_cap);
     OvSources s;
     memset(&s, 0, sizeof(s));
     s.lane_pts = d_lane_points; s.lane_cnt = d_lane_counts; s.lane_cnt_stride = 4;
@@ -672,7 +920,169 @@ int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* 
     s.dist_pts = d_dist_points; s.dist_cap = dist_cap > 0 ? dist_cap : 0;
     s.dist_cnt = d_dist_counts; s.dist_cnt_stride = 1;
     if (!(stages & ADAS_OVERLAY_AREA)) s.poly = nullptr;
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, d_bird_points, d_bird_counts, 4, d_bird_bgr, stages, n_frames, (hipStream_t)stream);
+    OvObjects o;
+    memset(&o, 0, sizeof(o));
+    if (stages & ADAS_OVERLAY_DETECTIONS) {
+        o.det_xyxy = d_det_xyxy; o.det_cls = d_det_cls; o.det_cnt = d_det_counts; o.det_cap = det_cap; o.det_cnt_stride = 1;
+    }
+    if (stages & ADAS_OVERLAY_TRACKS) {
+        o.trk_tlwh = (const unsigned char*)d_trk_tlwh; o.trk_frame_bytes = (size_t)trk_cap * 32; o.trk_row_bytes = 32;
+        o.trk_cls = (const unsigned char*)d_trk_cls; o.trk_cls_frame_bytes = (size_t)trk_cap * 4; o.trk_cls_row_bytes = 4; o.trk_act = nullptr;
+        o.trk_cnt = (const unsigned char*)d_trk_counts; o.trk_cnt_bytes = 4; o.trk_cap = trk_cap;
+    }
+    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, d_bird_points, d_bird_counts, 4, d_bird_bgr, stages, n_frames, (hipStream_t)stream, &o);
+}
+
+extern "C" {
+
+int adas_overlay_default_params(adas_overlay_params* p) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_overlay_default_params: null argument");
+    memset(p, 0, sizeof(*p));
+    p->lane_radius = 3; p->distance_radius = 4; p->bird_radius = 10;
+    p->lane_alpha = 0.3; p->area_alpha = 0.85;
+    const uint8_t lanes[4][3] = {{255, 0, 0}, {46, 139, 87}, {50, 205, 50}, {0, 255, 255}};
+    const uint8_t coll[4][3] = {{0, 255, 255}, {0, 255, 0}, {0, 102, 255}, {0, 0, 255}};
+    memcpy(p->lane_colors, lanes, 12);
+    memcpy(p->collision_colors, coll, 12);
+    p->offset_color[0] = 0; p->offset_color[1] = 0; p->offset_color[2] = 255;
+    p->area_color[0] = 255; p->area_color[1] = 191; p->area_color[2] = 0;
+    p->distance_color[0] = p->distance_color[1] = p->distance_color[2] = 255;
+    return ADAS_OK;
+}
+
+int adas_overlay_create(const adas_overlay_params* p, int max_batch, adas_overlay** out) {
+    ADAS_REQUIRE(p && out && max_batch > 0 && max_batch <= 65535, ADAS_ERR_INVALID, "adas_overlay_create: bad argument");
+    ADAS_REQUIRE(p->src_h > 0 && p->src_h <= 4320 && p->src_w > 0 && p->src_w <= 16384, ADAS_ERR_INVALID,
+                 "adas_overlay_create: frames must be 1..4320 rows by 1..16384 columns (got %dx%d)", p->src_h, p->src_w);
+    ADAS_REQUIRE((p->bird_h == 0 && p->bird_w == 0) || (p->bird_h > 0 && p->bird_h <= 4320 && p->bird_w > 0 && p->bird_w <= 16384), ADAS_ERR_INVALID,
+                 "adas_overlay_create: the bird view must be 0x0 (none) or 1..4320 rows by 1..16384 columns (got %dx%d)", p->bird_h, p->bird_w);
+    int rc = overlay_check_style(p, "adas_overlay_create");
+    if (rc) return rc;
+    ADAS_REQUIRE(adas_device_count() > 0, ADAS_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    adas_overlay* h = new (std::nothrow) adas_overlay();
+    ADAS_REQUIRE(h, ADAS_ERR_INVALID, "out of host memory");
+    h->p = *p;
+    (void)adas_overlay_default_object_style(&h->os);
+    h->max_batch = max_batch;
+    h->rw = (p->src_w + 31) / 32;
+    h->bird_rw = (p->bird_w + 31) / 32;
+    const size_t B = max_batch, words = B * p->src_h * h->rw, bwords = B * p->bird_h * h->bird_rw;
+    hipError_t e = hipMalloc((void**)&h->detail, words * 32);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->any, words * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->flags, B * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->rec_cnt, B * 8);
+    if (e == hipSuccess) e = hipMemset(h->rec_cnt, 0, B * 8);
+    if (e == hipSuccess && bwords) e = hipMalloc((void**)&h->bird_detail, bwords * 32);
+    if (e == hipSuccess && bwords) e = hipMalloc((void**)&h->bird_any, bwords * 4);
+    if (e == hipSuccess) e = hipMemset(h->detail, 0, words * 32);   // the planes are zero between runs
+    if (e == hipSuccess) e = hipMemset(h->any, 0, words * 4);
+    if (e == hipSuccess) e = hipMemset(h->flags, 0, B * 4);
+    if (e == hipSuccess && bwords) e = hipMemset(h->bird_detail, 0, bwords * 32);
+    if (e == hipSuccess && bwords) e = hipMemset(h->bird_any, 0, bwords * 4);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        adas_overlay_destroy(h);
+        return hip_fail(e, "hipMalloc(overlay planes)", __FILE__, __LINE__);
+    }
+    *out = h;
+    return ADAS_OK;
+}
+
+int adas_overlay_destroy(adas_overlay* h) {
+    if (!h) return ADAS_OK;
+    for (void* q : {(void*)h->any, (void*)h->detail, (void*)h->bird_any, (void*)h->bird_detail, (void*)h->flags, (void*)h->d_dst,
+                    (void*)h->rec_cnt, (void*)h->recs, (void*)h->colors[0], (void*)h->colors[1]})
+        if (q) (void)hipFree(q);
+    delete h;
+    return ADAS_OK;
+}
+
+int adas_overlay_set_style(adas_overlay* h, const adas_overlay_params* p) {
+    ADAS_REQUIRE(h && p, ADAS_ERR_INVALID, "adas_overlay_set_style: bad argument");
+    int rc = overlay_check_style(p, "adas_overlay_set_style");
+    if (rc) return rc;
+    adas_overlay_params n = *p;
+    n.src_h = h->p.src_h; n.src_w = h->p.src_w; n.bird_h = h->p.bird_h; n.bird_w = h->p.bird_w;
+    h->p = n;
+    adas::bump_config_generation();   // a captured step holds the old style in its kernel arguments
+    return ADAS_OK;
+}
+
+int adas_overlay_run(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
+                     adas_analysis* analysis, uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream) {
+    return overlay_run_handles("adas_overlay_run", 15, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, nullptr, nullptr, d_bird_bgr, stages,
+                               n_streams, n_frames, stream);
+}
+
+int adas_overlay_run_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
+                             adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr, int stages, int n_streams,
+                             int n_frames, void* stream) {
+    return overlay_run_handles("adas_overlay_run_objects", 63, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, post, tracker, d_bird_bgr, stages,
+                               n_streams, n_frames, stream);
+}
+
+int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points, const int32_t* d_lane_counts,
+                            const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
+                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
+                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
+                            int n_frames, void* stream) {
+    return overlay_run_raw("adas_overlay_run_arrays", 15, h, d_src_bgr, d_dst_bgr, d_lane_points, d_lane_counts, d_poly, poly_cap, d_poly_counts,
+                           d_area_status, d_offset_type, d_area_bgr, d_dist_points, dist_cap, d_dist_counts, d_bird_points, d_bird_counts, d_bird_bgr,
+                           nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stages, n_frames, stream);
+}
+
+int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points,
+                                    const int32_t* d_lane_counts, const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts,
+                                    const int32_t* d_area_status, const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points,
+                                    int dist_cap, const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts,
+                                    uint8_t* d_bird_bgr, const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts,
+                                    const double* d_trk_tlwh, int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages,
+                                    int n_frames, void* stream) {
+    return overlay_run_raw("adas_overlay_run_arrays_objects", 63, h, d_src_bgr, d_dst_bgr, d_lane_points, d_lane_counts, d_poly, poly_cap, d_poly_counts,
+                           d_area_status, d_offset_type, d_area_bgr, d_dist_points, dist_cap, d_dist_counts, d_bird_points, d_bird_counts, d_bird_bgr,
+                           d_det_xyxy, det_cap, d_det_cls, d_det_counts, d_trk_tlwh, trk_cap, d_trk_cls, d_trk_counts, stages, n_frames, stream);
+}
+
+int adas_overlay_default_object_style(adas_overlay_object_style* p) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_overlay_default_object_style: null argument");
+    memset(p, 0, sizeof(*p));
+    p->min_box_area = 10.0;
+    p->det_rect_thickness = 1; p->det_arm_thickness = 5; p->track_thickness = 2;
+    return ADAS_OK;
+}
+
+int adas_overlay_set_object_style(adas_overlay* h, const adas_overlay_object_style* p) {
+    ADAS_REQUIRE(h && p, ADAS_ERR_INVALID, "adas_overlay_set_object_style: bad argument");
+    int rc = overlay_check_object_style(p, "adas_overlay_set_object_style");
+    if (rc) return rc;
+    h->os = *p;
+    adas::bump_config_generation();   // a captured step holds the old style in its kernel arguments
+    return ADAS_OK;
+}
+
+int adas_overlay_set_class_colors(adas_overlay* h, int which, const uint8_t (*bgr)[3], int n) {
+    ADAS_REQUIRE(h && (which == ADAS_OVERLAY_DETECTIONS || which == ADAS_OVERLAY_TRACKS) && n >= 0 && (bgr || n == 0), ADAS_ERR_INVALID,
+                 "adas_overlay_set_class_colors: bad argument (which must be ADAS_OVERLAY_DETECTIONS or ADAS_OVERLAY_TRACKS)");
+    const int t = which == ADAS_OVERLAY_TRACKS;
+    uint32_t* table = nullptr;
+    if (n > 0) {
+        uint32_t* packed = new (std::nothrow) uint32_t[n];
+        ADAS_REQUIRE(packed, ADAS_ERR_INVALID, "out of host memory");
+        for (int i = 0; i < n; ++i) packed[i] = overlay_pack_bgr(bgr[i]);
+        hipError_t e = hipMalloc((void**)&table, (size_t)n * 4);
+        if (e == hipSuccess) e = hipMemcpy(table, packed, (size_t)n * 4, hipMemcpyHostToDevice);
+        delete[] packed;
+        if (e != hipSuccess) {
+            if (table) (void)hipFree(table);
+            return hip_fail(e, "hipMalloc(overlay class colours)", __FILE__, __LINE__);
+        }
+    }
+    ADAS_HIP_TRY(hipDeviceSynchronize());   // a run in flight may still read the old table
+    if (h->colors[t]) (void)hipFree(h->colors[t]);
+    h->colors[t] = table;
+    h->n_colors[t] = n;
+    adas::bump_config_generation();   // a captured step holds the old table's address in its kernel arguments
+    return ADAS_OK;
 }
 
 int adas_overlay_fetch(adas_overlay* h, int frame, uint8_t* h_bgr) {

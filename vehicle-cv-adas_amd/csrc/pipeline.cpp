@@ -187,7 +187,18 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             rc = adas_warp_device_view(p->bird_warp, &bird_img);
             if (rc) return rc;
         }
-        rc = adas_overlay_run(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, const_cast<uint8_t*>(bird_img), stages, NS, B, st);
+        if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the object layer: this step's survivors, the tracker after this step's update
+            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
+                         "the overlay's detections stage needs a detector with its post handle");
+            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
+                         "the overlay's tracks stage needs a tracker (and the detector that feeds it)");
+            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || B <= 1, ADAS_ERR_INVALID,
+                         "the overlay's tracks stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step", B);
+            rc = adas_overlay_run_objects(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
+                                          const_cast<uint8_t*>(bird_img), stages, NS, B, st);
+        } else {
+            rc = adas_overlay_run(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, const_cast<uint8_t*>(bird_img), stages, NS, B, st);
+        }
         if (rc) return rc;
     }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
@@ -363,9 +374,19 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
 
 int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
     ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: no overlay handle attached");
-    ADAS_REQUIRE(stages >= 0 && !(stages & ~15), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: unknown stage bits 0x%x", stages);
+    ADAS_REQUIRE(stages >= 0 && !(stages & ~63), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: unknown stage bits 0x%x", stages);
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
+    if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the boxes' records are allocated now: a captured step cannot
+        int det_cap = 0, trk_cap = 0, ts = 0;
+        const int *a, *b, *c;
+        const unsigned char *hdr, *out;
+        size_t sb = 0;
+        if ((stages & ADAS_OVERLAY_DETECTIONS) && p->d.post) adas::post_survivor_views(p->d.post, &a, &b, &c, &det_cap);
+        if ((stages & ADAS_OVERLAY_TRACKS) && p->d.tracker) adas::tracker_live_views(p->d.tracker, &hdr, &out, &sb, &ts, &trk_cap);
+        int rc = adas::overlay_reserve_objects(p->overlay, det_cap, trk_cap);
+        if (rc) return rc;
+    }
     p->overlay_stages = stages;
     return ADAS_OK;
 }

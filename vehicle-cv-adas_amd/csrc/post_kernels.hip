@@ -514,6 +514,22 @@ int handle_max_batch(const ::adas_ufld_decode* h) { return h ? h->max_batch : 0;
 int handle_max_batch(const ::adas_lane_geometry* h) { return h ? h->max_batch : 0; }
 int decode_num_lanes(const ::adas_ufld_decode* h) { return !h ? 0 : (h->v1 ? 4 : h->p.num_lanes); }
 const int* geometry_bird_points(const ::adas_lane_geometry* h) { return h->dev.bird; }
+void post_survivor_views(const ::adas_yolo_post* h, const int** xyxy_int, const int** cls, const int** counts, int* cap) {
+    *xyxy_int = h->dev.det_xyxy_i;
+    *cls = h->dev.det_cls;
+    *counts = h->dev.counts;
+    *cap = h->p.max_candidates;
+}
+void tracker_live_views(const ::adas_bytetrack* h, const unsigned char** hdr, const unsigned char** out, size_t* stream_bytes, int* n_streams,
+                        int* max_tracks) {
+    static_assert(sizeof(BtOut) == sizeof(adas_track) && sizeof(BtHeader) == sizeof(adas_track_header), "the live table is the fetch layout");
+    const BtStream S = bt_view(h->dev.base, h->p.max_tracks, h->p.max_dets);
+    *hdr = (const unsigned char*)S.hdr;
+    *out = (const unsigned char*)S.out;
+    *stream_bytes = h->dev.stream_bytes;
+    *n_streams = h->n_streams;
+    *max_tracks = h->p.max_tracks;
+}
 void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int** det, const int** pts) {
     *cnt = h->dev.lane_cnt;
     *det = h->dev.lane_det;

@@ -11,8 +11,10 @@ Same public surface (`_defaults` / `set_defaults`, `DetectFrame(frame)`, `.objec
 frame is uploaded, letterbox/normalise (pre_kernels.hip), the network (MFMA conv engine), decode + NMS /
 lane decode (post_kernels.hip) all run in HBM, and only the survivors (<= 2 KB) come back.
 Of the reference's drawing, the lane detectors' `DrawDetectedOnFrame` / `DrawAreaOnFrame` run on the device (csrc/overlay_kernels.hip:
-filled discs, the ego-lane polygon and the alpha blends, restated from OpenCV 4.5 with parity unpinned); text, thick lines, arrows,
-trajectories, the UI panels and everything else cv2 stay out of scope.
+filled discs, the ego-lane polygon and the alpha blends, restated from OpenCV 4.5 with parity unpinned), and so do the BOXES of
+`YoloDetector.DrawDetectedOnFrame` / `EfficientdetDetector.DrawDetectedOnFrame` (cornerRect: outline and corner arms in the class colour)
+and of `BYTETracker.DrawTrackedOnFrame` (plot_bbox's rectangle and tint).  Text, the label's background rectangle, key points,
+trajectories, arrows, slanted thick lines, the UI panels and everything else cv2 stay out of scope.
 
 What stays on the host is what the reference keeps there and SURVEY 8a marks "host": RectInfo construction and
 LaneDetectBase.__update_lanes_status/__update_lanes_area (core.py:102-158: ego-lane polyfit, <1 ms).
@@ -98,6 +100,37 @@ def _engine_for(model_path, **kw):
     return TensorRTEngine(model_path, **kw) if model_path.endswith('.trt') else OnnxEngine(model_path, **kw)
 
 
+def _colors_dict(class_names):
+    """label -> colour, what yoloDetector.py:93-94 ends up with: one 24-bit random number per label, its three bytes from the top down."""
+    import random
+    out = {}
+    for label in class_names:
+        v = random.randint(0, 0xFFFFFF)
+        out[label] = ((v >> 16) & 0xFF, (v >> 8) & 0xFF, v & 0xFF)
+    return out
+
+
+class _DrawsBoxes:
+    """DrawDetectedOnFrame of the two object detectors (yoloDetector.py:170-191, the same in efficientdetDetector.py) on the device: the
+    cornerRect of every RectInfo, in _object_info order, in colors_dict[label] -- (0, 0, 0) for 'unknown'.  The label, its background
+    rectangle and the key points are NOT drawn (getTextSize / putText).  `frame_show` is an HxWx3 uint8 ndarray (uploaded, drawn, copied
+    back into frame_show[:]) or a StagedFrame (drawn where it sits).  OpenCV's thick line restated (csrc/overlay_core.h D6), parity unpinned."""
+
+    def DrawDetectedOnFrame(self, frame_show) -> None:
+        if len(self._object_info) == 0:
+            return
+        if getattr(self, "_painter", None) is None:
+            self._painter = OverlayPainter()
+        boxes = [info.tolist() for info in self._object_info]
+        colors = [self.colors_dict[info.label] if info.label != 'unknown' else (0, 0, 0) for info in self._object_info]
+        self._painter.detections(frame_show, boxes, list(range(len(boxes))), colors)
+
+    def _close_painter(self):
+        if getattr(self, "_painter", None) is not None:
+            self._painter.close()
+            self._painter = None
+
+
 class StagedFrame:
     """A BGR u8 frame that already sits in HBM: what `detector.staged_frame` hands out after a DetectFrame, so that the next task class
     of the same loop iteration (demo.py:269,280 pass the SAME frame to the object and the lane detector) does not upload its 2.7 MB
@@ -157,7 +190,7 @@ class _FrameStage:
 MAX_LDS_CANDIDATES = 2048      # candidate arenas up to this size live in LDS; larger ones (up to one per anchor) in HBM (post_kernels.hip)
 
 
-class YoloDetector(_Defaults):
+class YoloDetector(_Defaults, _DrawsBoxes):
     _defaults = {
         "model_path": './models/yolov5n-coco.onnx',
         "model_type": ObjectModelType.YOLOV5,
@@ -203,6 +236,7 @@ class YoloDetector(_Defaults):
         assert os.path.isfile(classes_path), Exception("%s is not exist." % classes_path)
         with open(classes_path) as f:
             self.class_names = [c.strip() for c in f.readlines()]
+        self.colors_dict = _colors_dict(self.class_names)
 
     @property
     def object_info(self):
@@ -267,6 +301,7 @@ class YoloDetector(_Defaults):
         self._object_info = out
 
     def close(self):
+        self._close_painter()
         if getattr(self, "_post", None) is not None:
             self._post.close()
             self._post = None
@@ -283,7 +318,7 @@ class YoloDetector(_Defaults):
 
 
 # =====================================================================================
-class EfficientdetDetector(_Defaults):
+class EfficientdetDetector(_Defaults, _DrawsBoxes):
     """efficientdetDetector.py:18-111.  The exported EfficientDet graph carries its own decode + NMS; around it the reference does
     letterbox + BGR mean/std normalisation (:57-65) and inverse letterbox + score filter + label lookup (:67-85).  Both run on the
     device here (adas_preprocess_effdet, adas_effdet_post_*).  The graph itself is coreEngine.EfficientdetEngine: an EfficientDet-D0 .. D3
@@ -315,6 +350,7 @@ class EfficientdetDetector(_Defaults):
         assert os.path.isfile(classes_path), Exception("%s is not exist." % classes_path)
         with open(classes_path) as f:
             self.class_names = [c.strip() for c in f.readlines()]
+        self.colors_dict = _colors_dict(self.class_names)
         # the in-graph tail's own parameters (what an exporter bakes into the graph): overridable like any other default
         self.engine = engine if engine is not None else EfficientdetEngine(
             os.path.expanduser(self.model_path), precision=getattr(self, "precision", None), score_thr=float(getattr(self, "graph_score_thr", 0.05)),
@@ -362,6 +398,7 @@ class EfficientdetDetector(_Defaults):
         self._object_info = info
 
     def close(self):
+        self._close_painter()
         if getattr(self, "_post", None) is not None:
             self._post.close()
             self._post = None
@@ -726,8 +763,20 @@ class BYTETracker:
     Each instance owns its id counter (the reference's BaseTrack._count is process-global, base_track.py:12)."""
 
     def __init__(self, track_thresh: float = 0.5, track_buffer: int = 30, match_thresh: float = 0.8, frame_rate: int = 30,
-                 min_box_area: int = 10, max_tracks: int = 256, max_dets: int = 512, **kwargs: Any):
+                 min_box_area: int = 10, max_tracks: int = 256, max_dets: int = 512, names=None, **kwargs: Any):
+        """names: the reference's ObjectTrackBase argument (ObjectTracker/core.py:83-93) -- a dict label -> colour (the class colours
+        themselves) or a list of labels (one random colour each); None: no colours, every box is drawn black."""
         self.track_thresh, self.match_thresh, self.min_box_area = track_thresh, match_thresh, min_box_area
+        # what ObjectTrackBase keeps (ObjectTracker/core.py:83-93): a dict is the colour table itself and every label names itself; a list
+        # of labels gets one random colour per entry, channels in 0 .. 254
+        if names is None:
+            self.names, self.class_colors = None, {}
+        elif isinstance(names, dict):
+            self.names, self.class_colors = {label: label for label in names}, names
+        else:
+            draw = np.random.default_rng()
+            self.names, self.class_colors = names, [[int(c) for c in draw.integers(0, 255, 3)] for _ in range(len(names))]
+        self._painter = None
         self.det_thresh = track_thresh + 0.1
         self.buffer_size = int(frame_rate / 30.0 * track_buffer)
         self.max_time_lost = self.buffer_size
@@ -809,6 +858,26 @@ class BYTETracker:
         return [b for b in self.trajectories().get(int(track_id), [])
                 if b[0] >= 0 + padw and b[1] >= 0 + padh and b[2] <= fw - padw and b[3] <= fh - padh]
 
+    def DrawTrackedOnFrame(self, frame, show_box: bool = True, show_traject: bool = True) -> None:
+        """byteTracker.py:202-215 on the device, the BOX part only: for every activated track of tracked_stracks, in list order, with
+        tlwh[2] * tlwh[3] > min_box_area, plot_bbox's thickness-2 rectangle and its 0.6 / 0.4 / + 1 tint in class_colors[class_id] (a class
+        without a colour is drawn black).  NOT drawn: plot_bbox's text, plot_trajectories' circles and plot_directions' arrows --
+        show_traject is accepted and ignored.  `frame` is an HxWx3 uint8 ndarray (drawn and copied back into frame[:]) or a StagedFrame."""
+        if not show_box:
+            return
+        online = [t for t in self._tracked if t["is_activated"]]
+        if not online:
+            return
+        colors = []
+        for t in online:
+            try:
+                colors.append(tuple(int(v) for v in self.class_colors[t["class_id"]]))
+            except (KeyError, IndexError, TypeError):
+                colors.append((0, 0, 0))
+        if self._painter is None:
+            self._painter = OverlayPainter()
+        self._painter.tracks(frame, [t["tlwh"] for t in online], list(range(len(online))), colors, min_box_area=self.min_box_area)
+
     @property
     def tracked_stracks(self):
         return self._tracked
@@ -825,6 +894,9 @@ class BYTETracker:
         self._dev.reset(0)
 
     def close(self):
+        if getattr(self, "_painter", None) is not None:
+            self._painter.close()
+            self._painter = None
         if getattr(self, "_dev", None) is not None:
             self._dev.close()
             self._dev = None

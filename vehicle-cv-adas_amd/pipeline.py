@@ -39,7 +39,11 @@ class AdasPipeline:
         overlay as the step's very last stage, drawn from step_frames' frames into a buffer of its own (overlay_image(frame) after sync()):
         lane-point discs and the ego-lane polygon alpha-blended, distance-point discs, and the discs on the bird-view image -- no text, thick
         lines, arrows, trajectories or panels.  Needs lane_model= and geometry=; the distance stage needs analysis=, the bird stage
-        birdview=dict(image=True).  stages=None: every stage the pipeline has the handles for."""
+        birdview=dict(image=True).  stages=None: every one of those four stages the pipeline has the handles for.  Only by name: "detections"
+        (cornerRect boxes of the step's survivors; needs det_model=) and "tracks" (the tracked tracks' rectangles and tints after this step's
+        update; needs track=True and micro_batch 1), drawn between the area and the distance discs in the class colours of
+        overlay["detection_colors"] / overlay["track_colors"] (BGR by class id; none: black).  Boxes only: no labels, key points,
+        trajectories or arrows."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
@@ -56,6 +60,12 @@ class AdasPipeline:
                 raise ValueError("the overlay's distance stage needs analysis= (the distance points it draws)")
             if ov_mask is not None and ov_mask & L.OVERLAY_BIRD and not (birdview is not None and dict(birdview).get("image", False)):
                 raise ValueError("the overlay's bird stage needs birdview=dict(image=True) (the bird-view image it draws on)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_DETECTIONS and not det_model:
+                raise ValueError("the overlay's detections stage needs det_model= (the survivors it draws)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_TRACKS and not (det_model and track):
+                raise ValueError("the overlay's tracks stage needs det_model= and track=True (the tracked tracks it draws)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_TRACKS and self.B > 1:
+                raise ValueError("the overlay's tracks stage needs micro_batch=1: the tracker's live table holds only the last frame of a step")
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:
@@ -108,8 +118,11 @@ class AdasPipeline:
             self.analysis = Analysis(n_streams=n_tracks, max_frames=n_streams, **kw)
             L.check(L.lib().adas_pipeline_attach_analysis(self.h, self.analysis.h))
         if overlay is not None:
-            style = {k: v for k, v in dict(overlay).items() if k != "stages"}
+            style = {k: v for k, v in dict(overlay).items() if k not in ("stages", "detection_colors", "track_colors")}
             self.overlay = LaneOverlay(src_hw, self.warp.dst_hw if self.warp else None, n_streams, **style)
+            for key, which in (("detection_colors", "detections"), ("track_colors", "tracks")):
+                if dict(overlay).get(key) is not None:
+                    self.overlay.set_class_colors(which, overlay[key])
             L.check(L.lib().adas_pipeline_attach_overlay(self.h, self.overlay.h))
             if ov_mask is not None:
                 L.check(L.lib().adas_pipeline_set_overlay_stages(self.h, ov_mask))

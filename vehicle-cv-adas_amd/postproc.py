@@ -540,10 +540,15 @@ class LaneOverlay:
     """The pixel part of the reference's Draw* block on frames resident in HBM (adas_overlay_*): discs of radius 3 on every lane point
     blended at alpha 0.3 (UltrafastLaneDetectorV2.DrawDetectedOnFrame), the ego-lane polygon blended at 0.85 (DrawAreaOnFrame), white
     discs of radius 4 on the distance points (SingleCamDistanceMeasure.DrawDetectedOnFrame) and discs of radius 10 on the bird-view
-    image (PerspectiveTransformation.DrawDetectedOnBirdView).  Text, thick lines, arrows, trajectories and the UI panels are not drawn.
+    image (PerspectiveTransformation.DrawDetectedOnBirdView).  The object layer ("detections", "tracks"; off unless asked for) adds the
+    boxes between the area blend and the distance discs: ObjectDetectBase.cornerRect per survivor (outline and eight corner arms in the
+    class colour) and the box part of BYTETracker.DrawTrackedOnFrame (a thickness-2 rectangle, then the region tinted 0.6 / 0.4 / + 1) per
+    activated tracked track over min_box_area.  Not drawn: text, the label's background rectangle, key points, plot_trajectories' thick
+    circles, plot_directions' arrows, DrawTransformFrontalViewArea's slanted thick lines and the UI panels.
     The pixel rules are csrc/overlay_core.h (modelled on OpenCV 4.5; parity with a real cv2 build is unpinned, lines are not clipped
     before they are walked)."""
     STAGES = L.OVERLAY_STAGES
+    OBJECT_STYLE = ("min_box_area", "det_rect_thickness", "det_arm_thickness", "track_thickness")
 
     def __init__(self, src_hw, bird_hw=None, max_batch=1, **style):
         """style: lane_radius, distance_radius, bird_radius, lane_alpha, area_alpha, lane_colors (4 BGR tuples), offset_color,
@@ -553,11 +558,31 @@ class LaneOverlay:
         self.p.src_h, self.p.src_w = int(src_hw[0]), int(src_hw[1])
         if bird_hw is not None:
             self.p.bird_h, self.p.bird_w = int(bird_hw[0]), int(bird_hw[1])
+        self.os = L.OverlayObjectStyle()
+        L.check(L.lib().adas_overlay_default_object_style(C.byref(self.os)))
+        obj = {k: style.pop(k) for k in self.OBJECT_STYLE if k in style}
         self._apply(style)
         self.src_hw, self.bird_hw, self.max_batch = (self.p.src_h, self.p.src_w), (self.p.bird_h, self.p.bird_w), int(max_batch)
         h = C.c_void_p()
         L.check(L.lib().adas_overlay_create(C.byref(self.p), self.max_batch, C.byref(h)))
         self.h = h.value
+        if obj:
+            self.set_object_style(**obj)
+
+    def set_object_style(self, **style):
+        """min_box_area (10), det_rect_thickness (1), det_arm_thickness (5), track_thickness (2), from the next run on."""
+        for k, v in style.items():
+            if k not in self.OBJECT_STYLE:
+                raise TypeError("unknown overlay object style %r" % k)
+            setattr(self.os, k, v)
+        L.check(L.lib().adas_overlay_set_object_style(self.h, C.byref(self.os)))
+
+    def set_class_colors(self, which, colors):
+        """The class colours of "detections" (colors_dict by class id) or "tracks" (class_colors): BGR triples, written as given.  A class id
+        outside the table is 'unknown', black; so is every object while no table is set.  From the next run on."""
+        which = self.stage_mask(which)
+        tab = np.ascontiguousarray(np.asarray(list(colors), np.int64).reshape(-1, 3).astype(np.uint8))
+        L.check(L.lib().adas_overlay_set_class_colors(self.h, which, L.ptr(tab) if len(tab) else None, len(tab)))
 
     def _apply(self, style):
         for k, v in style.items():
@@ -575,7 +600,7 @@ class LaneOverlay:
 
     @classmethod
     def stage_mask(cls, stages):
-        """An int, or names out of "lanes", "area", "distance", "bird"."""
+        """An int, or names out of "lanes", "area", "distance", "bird", "detections", "tracks"."""
         if isinstance(stages, int):
             return stages
         names = [stages] if isinstance(stages, str) else list(stages)
@@ -592,25 +617,44 @@ class LaneOverlay:
         self._apply(style)
         L.check(L.lib().adas_overlay_set_style(self.h, C.byref(self.p)))
 
-    def run(self, src_ptr, decode=None, geometry=None, analysis=None, bird_ptr=None, stages=None, n_streams=1, n_frames=1, dst_ptr=None, stream=None):
+    def run(self, src_ptr, decode=None, geometry=None, analysis=None, bird_ptr=None, stages=None, n_streams=1, n_frames=1, dst_ptr=None, stream=None,
+            post=None, tracker=None):
         """Frames [0, n_streams * n_frames) of the device pointer src_ptr -> dst_ptr (None: the handle's own buffer; src_ptr: in place), drawn
-        from the handles' device arrays (UfldDecode / Ufld1Decode, LaneGeometry, Analysis).  stages=None: every stage whose handle is given."""
+        from the handles' device arrays (UfldDecode / Ufld1Decode, LaneGeometry, Analysis; post=: a YoloPost, its survivors' boxes; tracker=: a
+        DeviceTracker, its live tracked tracks -- n_frames must then be 1).  stages=None: every stage whose handle is given."""
         if stages is None:
             stages = ((L.OVERLAY_LANES if decode else 0) | (L.OVERLAY_AREA if geometry else 0) | (L.OVERLAY_DISTANCE if analysis else 0) |
-                      (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0))
-        L.check(L.lib().adas_overlay_run(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
-                                         analysis.h if analysis else None, bird_ptr, self.stage_mask(stages), int(n_streams), int(n_frames), stream))
+                      (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if post else 0) | (L.OVERLAY_TRACKS if tracker else 0))
+        mask = self.stage_mask(stages)
+        if post is None and tracker is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
+            L.check(L.lib().adas_overlay_run(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
+                                             analysis.h if analysis else None, bird_ptr, mask, int(n_streams), int(n_frames), stream))
+            return
+        L.check(L.lib().adas_overlay_run_objects(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
+                                                 analysis.h if analysis else None, post.h if post else None, tracker.h if tracker else None, bird_ptr,
+                                                 mask, int(n_streams), int(n_frames), stream))
 
     def run_arrays(self, src_ptr, n_frames=1, lane_points=None, lane_counts=None, poly=None, poly_cap=0, poly_counts=None, area_status=None,
                    offset_type=None, area_bgr=None, dist_points=None, dist_cap=0, dist_counts=None, bird_points=None, bird_counts=None,
-                   bird_ptr=None, stages=None, dst_ptr=None, stream=None):
-        """The same kernels on raw device pointers (adas_overlay_run_arrays).  stages=None: every stage whose arrays are given."""
+                   bird_ptr=None, stages=None, dst_ptr=None, stream=None, det_xyxy=None, det_cap=0, det_cls=None, det_counts=None, trk_tlwh=None,
+                   trk_cap=0, trk_cls=None, trk_counts=None):
+        """The same kernels on raw device pointers (adas_overlay_run_arrays; with boxes adas_overlay_run_arrays_objects: det_xyxy
+        [frames][det_cap][4] int32 + det_cls + det_counts, trk_tlwh [frames][trk_cap][4] fp64 + trk_cls + trk_counts, rows of activated
+        tracked tracks).  stages=None: every stage whose arrays are given."""
         if stages is None:
             stages = ((L.OVERLAY_LANES if lane_points else 0) | (L.OVERLAY_AREA if poly else 0) | (L.OVERLAY_DISTANCE if dist_points else 0) |
-                      (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0))
-        L.check(L.lib().adas_overlay_run_arrays(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
-                                                offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts, bird_ptr,
-                                                self.stage_mask(stages), int(n_frames), stream))
+                      (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if det_xyxy else 0) |
+                      (L.OVERLAY_TRACKS if trk_tlwh else 0))
+        mask = self.stage_mask(stages)
+        if det_xyxy is None and trk_tlwh is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
+            L.check(L.lib().adas_overlay_run_arrays(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
+                                                    offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts, bird_ptr,
+                                                    mask, int(n_frames), stream))
+            return
+        L.check(L.lib().adas_overlay_run_arrays_objects(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
+                                                        offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts,
+                                                        bird_ptr, det_xyxy, int(det_cap), det_cls, det_counts, trk_tlwh, int(trk_cap), trk_cls,
+                                                        trk_counts, mask, int(n_frames), stream))
 
     def fetch(self, frame=0):
         out = np.empty((self.src_hw[0], self.src_hw[1], 3), np.uint8)
@@ -646,6 +690,7 @@ class OverlayPainter:
         self.ov = None
         self.key = None
         self.buf = None
+        self._set = {}
 
     def _target(self, image):
         staged = hasattr(image, "ptr") and not isinstance(image, np.ndarray)
@@ -660,6 +705,7 @@ class OverlayPainter:
                 self.ov.close()
             self.ov = LaneOverlay(hw, hw, 1)
             self.key = hw
+            self._set = {}                  # what the handle was last given: the colour table of each stage, the object style
         if staged:
             return image.ptr, None
         n = hw[0] * hw[1] * 3
@@ -719,6 +765,44 @@ class OverlayPainter:
         finally:
             d_poly.free()
             d_meta.free()
+
+    def _boxes(self, image, stage, table, boxes, classes, dtype, **style):
+        ptr, host = self._target(image)
+        b = np.ascontiguousarray(np.asarray(boxes, dtype).reshape(-1, 4))
+        if len(b) == 0:
+            return
+        c = np.ascontiguousarray(np.asarray(classes, np.int64).reshape(-1).astype(np.int32))
+        if len(c) != len(b):
+            raise Exception("%d boxes, %d classes" % (len(b), len(c)))
+        d_b, d_c, d_n = L.DeviceBuffer.from_array(b), L.DeviceBuffer.from_array(c), L.DeviceBuffer.from_array(np.array([len(b)], np.int32))
+        try:
+            # both setters wait for the device and make a captured step of this process re-capture: only when something changed
+            tab = tuple(tuple(int(v) for v in c) for c in table)
+            if self._set.get(stage) != tab:
+                self.ov.set_class_colors(stage, tab)
+                self._set[stage] = tab
+            new = {k: v for k, v in style.items() if getattr(self.ov.os, k) != v}
+            if new:
+                self.ov.set_object_style(**new)
+            if stage == L.OVERLAY_DETECTIONS:
+                self.ov.run_arrays(ptr, 1, det_xyxy=d_b.ptr, det_cap=len(b), det_cls=d_c.ptr, det_counts=d_n.ptr, stages=stage, dst_ptr=ptr)
+            else:
+                self.ov.run_arrays(ptr, 1, trk_tlwh=d_b.ptr, trk_cap=len(b), trk_cls=d_c.ptr, trk_counts=d_n.ptr, stages=stage, dst_ptr=ptr)
+            self._finish(ptr, host)
+        finally:
+            for x in (d_b, d_c, d_n):
+                x.free()
+
+    def detections(self, image, boxes, classes, colors=(), arm_thickness=5, rect_thickness=1):
+        """DrawDetectedOnFrame's boxes: cornerRect on every (xmin, ymin, xmax, ymax) in order, in colors[class] (outside the table: black).
+        No label, no label background, no key points."""
+        self._boxes(image, L.OVERLAY_DETECTIONS, colors, boxes, classes, np.int32, det_arm_thickness=int(arm_thickness),
+                    det_rect_thickness=int(rect_thickness))
+
+    def tracks(self, image, tlwhs, classes, colors=(), min_box_area=10, thickness=2):
+        """DrawTrackedOnFrame's boxes: plot_bbox's rectangle and tint on every tlwh (rows of activated tracked tracks, in list order) whose
+        area passes the gate, in colors[class].  No text, trajectories or arrows."""
+        self._boxes(image, L.OVERLAY_TRACKS, colors, tlwhs, classes, np.float64, min_box_area=float(min_box_area), track_thickness=int(thickness))
 
     def close(self):
         if self.ov is not None:
