@@ -643,8 +643,8 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * in HBM -- UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame (ultrafastLaneDetectorV2.py:196-218, the same in v1), the
  * discs of SingleCamDistanceMeasure.DrawDetectedOnFrame (distanceMeasure.py:98) and PerspectiveTransformation.DrawDetectedOnBirdView
  * (perspectiveTransformation.py:217-226): two whole-frame cv2.addWeighted passes, a cv2.fillPoly and filled cv2.circles.
- * NOT drawn: text (putText / getTextSize), arrows and trajectories (arrowedLine, thick circles) and the UI panels; the boxes of the
- * detector and the tracker are the object layer below.
+ * NOT drawn: text (putText / getTextSize) and the UI panels; the boxes of the detector and the tracker are the object layer below, the
+ * tracker's trajectories and direction marks (thick circles, arrowedLine) the trajectories stage below that.
  * The pixel rules are modelled on OpenCV 4.5's drawing.cpp / arithm and defined in csrc/overlay_core.h (restated in NumPy,
  * tests/overlay_ref.py); parity with a real cv2 build is UNPINNED, and lines are not clipped before they are walked (OpenCV clips the
  * segment first and restarts the error term).  Per frame f, S0 = the source frame:
@@ -658,7 +658,8 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * With an analysis handle the offset type and the area colour (collision_colors[collision_msg]) are the frame's row after its three
  * updates; without one the offset type is UNKNOWN and the colour is area_color.  The frame goes to a buffer of its own
  * (frame_show = frame.copy()); every output byte depends on the same input byte and geometry only, so dst == src is legal.
- * Three launches for the frame (coverage, one streaming pass with 16-byte accesses, coverage clean-up), two for the bird view; all plain:
+ * Three launches for the frame (coverage, one streaming pass with 16-byte accesses, coverage clean-up; four with the object layer, two
+ * more with the trajectories stage), two for the bird view; all plain:
  * capturable.  Nothing is capped: lanes hold at most ADAS_UFLD_MAX_POINTS points, polygons and distance points as many as their sources.
  *
  * The object layer: two more stages, off unless asked for, drawn between AREA and DISTANCE in the reference's order (demo.py:299-305).
@@ -673,9 +674,27 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * A class id outside the colour table is the reference's 'unknown': black.  Where boxes overlap the result is the sequential fold of the
  * reference's calls; the distance discs still lie over everything.  The pixel rules are D6-D9 of csrc/overlay_core.h (a thick axis-aligned
  * segment is a body plus two end discs; modelled on OpenCV 4.5's ThickLine, parity UNPINNED).  NOT drawn: text, the label's background
- * rectangle, key points, plot_trajectories' thick circles, plot_directions' arrows, DrawTransformFrontalViewArea's slanted thick lines, the
- * UI panels.  One more launch (the boxes' records) when one of the two stages is on, none when both are off; nothing is capped below the
- * sources' capacities (max_candidates per frame, max_tracks per stream).
+ * rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines, the UI panels.  One more launch (the boxes' records) when one
+ * of the two stages is on, none when both are off; nothing is capped below the sources' capacities (max_candidates per frame, max_tracks
+ * per stream).
+ *
+ * The trajectories stage: what the reference's demo actually draws for a track -- DrawTrackedOnFrame(frame_show, False) (demo.py:304:
+ * show_box = False, show_traject = True).  Off unless asked for; bit 128 (64 stays an unknown stage bit).
+ *  128 TRAJECTORIES  per track of tracked_stracks, in list order, that is activated and has tlwh[2] * tlwh[3] > min_box_area (the gate and the
+ *               min_box_area of TRACKS): plot_trajectories' circles (ObjectTracker/core.py:188-197) -- with more than one box in the
+ *               trajectory, box i (oldest first) a circle at (int((x1 + x2) / 2), int(y2)) of radius int(sqrt(i + 1) * 0.5) and thickness
+ *               int(sqrt(i + 1) * 1.2) in the class colour -- then plot_directions' indicator (core.py:132-171) from the boxes at least 10
+ *               pixels inside the frame (strack.py:145-149): with n < 5 direction vectors the lock-on rectangle (thickness 2, class colour
+ *               minus 10 per channel, saturated), else the shadowed arrow along the median direction (three arrowedLine calls:
+ *               (100,100,100) t 5 tip 0.3 shifted by (-2, +2), white t 2 tip 0.3 - 0.1 ending one pixel short, white t 3 tip 0.3).
+ * In the fold a track's circles and indicator come behind its own TRACKS outline and tint and ahead of the next track's; every primitive
+ * writes its colour; the distance discs still lie over everything.  The arithmetic and the pixel rules D10-D12 (thick circle, thick segment
+ * of any slope, arrow; modelled on OpenCV 4.5's EllipseEx / ThickLine / arrowedLine, the arrow's tips without trigonometry, parity
+ * UNPINNED) are csrc/overlay_track_core.h.  A segment endpoint beyond +-32767 skips that primitive and sets ADAS_OVERLAY_TRACK_RANGE.
+ * Colours are the TRACKS class colours.  NOT drawn: the 'ID: n' text and the label.  Two more launches when the stage is on (the tracks'
+ * primitives; behind the streaming pass one pass per band of rows that lists the primitives meeting the band, builds their coverage in
+ * LDS and writes the covered pixels), none when it is off: the other kernels are then the ones they were.  At most 30 circles + 9 segments per track, max_tracks tracks per stream: nothing is capped, nothing allocates at run time once
+ * the first run (or adas_pipeline_set_overlay_stages) has sized the tables.
  * ----------------------------------------------------------------------------------- */
 typedef struct adas_overlay adas_overlay;
 typedef struct {
@@ -697,7 +716,9 @@ typedef struct {
 #define ADAS_OVERLAY_BIRD 8
 #define ADAS_OVERLAY_DETECTIONS 16 /* adas_overlay_run_objects / _run_arrays_objects / adas_pipeline_set_overlay_stages only */
 #define ADAS_OVERLAY_TRACKS 32
+#define ADAS_OVERLAY_TRAJECTORIES 128 /* adas_overlay_run_trajectories / _run_arrays_trajectories / adas_pipeline_set_overlay_stages only; 64 is no stage */
 #define ADAS_OVERLAY_POLY_RANGE 1 /* frame flags: a polygon vertex outside +-32767, the frame's fill was skipped */
+#define ADAS_OVERLAY_TRACK_RANGE 2 /* a segment of a track's indicator had an endpoint outside +-32767 and was skipped */
 /* The reference's radii, alphas and colours; the four sizes are 0. */
 int adas_overlay_default_params(adas_overlay_params* p);
 /* max_batch frames per run.  Allocates the coverage planes (src_h x src_w / 8 bytes per frame, plus a detail plane of src_h x src_w
@@ -753,6 +774,48 @@ int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, u
                                     uint8_t* d_bird_bgr, const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts,
                                     const double* d_trk_tlwh, int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages,
                                     int n_frames, void* stream);
+/* adas_overlay_run_objects plus the trajectories stage, which reads `tracker`'s live state: the message rows for the order, tlwh, class and
+ * is_activated, and each row's trajectory ring through the table slot the row names.  Like TRACKS it needs n_frames == 1 and a tracker
+ * handle (ADAS_ERR_INVALID otherwise, by name). */
+int adas_overlay_run_trajectories(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
+                                  adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, struct adas_bytetrack* tracker,
+                                  uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream);
+/* The arguments of adas_overlay_run_arrays_objects as one struct, plus the trajectories of the rows of d_trk_tlwh: d_traj_tlbr
+ * [frames][trk_cap][ADAS_TRAJECTORY_LEN][4] fp64 (x1, y1, x2, y2), oldest first, and d_traj_len [frames][trk_cap], 0 .. 30. */
+typedef struct {
+    const uint8_t* d_src_bgr;
+    uint8_t* d_dst_bgr;
+    const int32_t *d_lane_points, *d_lane_counts;
+    const int32_t *d_poly, *d_poly_counts, *d_area_status, *d_offset_type;
+    const uint8_t* d_area_bgr;
+    const int32_t *d_dist_points, *d_dist_counts;
+    const int32_t *d_bird_points, *d_bird_counts;
+    uint8_t* d_bird_bgr;
+    const int32_t *d_det_xyxy, *d_det_cls, *d_det_counts;
+    const double* d_trk_tlwh;
+    const int32_t *d_trk_cls, *d_trk_counts;
+    const double* d_traj_tlbr;
+    const int32_t* d_traj_len;
+    void* stream;
+    int32_t poly_cap, dist_cap, det_cap, trk_cap;
+    int32_t stages, n_frames;
+} adas_overlay_arrays;
+/* adas_overlay_run_arrays_objects plus the trajectories stage (TRAJECTORIES needs the four track arrays and the two trajectory arrays). */
+int adas_overlay_run_arrays_trajectories(adas_overlay* h, const adas_overlay_arrays* a);
+/* The primitives the device built for frame `frame` of the last run with the trajectories stage, in drawing order: per track row its
+ * circles, then its rectangle or its three arrows.  Up to max_marks are stored, *n_marks is their total.  Synchronises. */
+#define ADAS_TRACK_MARK_CIRCLE 1 /* centre (x1, y1), radius, thickness */
+#define ADAS_TRACK_MARK_RECT 2   /* cv2.rectangle((x1, y1), (x2, y2), thickness) */
+#define ADAS_TRACK_MARK_ARROW 3  /* cv2.arrowedLine((x1, y1), (x2, y2), thickness); tip: the two tip points (x, y), (x, y) */
+typedef struct {
+    int32_t kind, track;         /* ADAS_TRACK_MARK_*; the track's row */
+    int32_t x1, y1, x2, y2;
+    int32_t radius, thickness;
+    int32_t tip[4];
+    uint8_t color[3];            /* channels 0, 1, 2 */
+    uint8_t skipped;             /* bit j: segment j of the mark was out of range and not drawn */
+} adas_overlay_track_mark;
+int adas_overlay_fetch_track_marks(adas_overlay* h, int frame, adas_overlay_track_mark* marks, int max_marks, int32_t* n_marks);
 /* Frame `frame` of the handle's own buffer -> h_bgr [src_h][src_w][3], after the last run's stream has drained.  A frame that no run
  * has written is ADAS_ERR_INVALID. */
 int adas_overlay_fetch(adas_overlay* h, int frame, uint8_t* h_bgr);
@@ -883,9 +946,10 @@ int adas_pipeline_attach_analysis(adas_pipeline* p, adas_analysis* analysis);
  * its launch count are unchanged.  The handle stays the caller's. */
 int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay);
 /* The stages (ADAS_OVERLAY_*) the attached overlay draws; one that lacks its handle (DISTANCE without an analysis handle, BIRD without a
- * warp, DETECTIONS without a detector, TRACKS without a tracker) is ADAS_ERR_INVALID at the step.  The default set holds neither
- * DETECTIONS nor TRACKS.  DETECTIONS draws the step's survivors, TRACKS the tracker's table after this step's update; TRACKS with
- * micro_batch > 1 is ADAS_ERR_INVALID at the step (the live table holds the last frame only).  Cached graphs are dropped. */
+ * warp, DETECTIONS without a detector, TRACKS or TRAJECTORIES without a tracker) is ADAS_ERR_INVALID at the step.  The default set holds
+ * none of DETECTIONS, TRACKS, TRAJECTORIES.  DETECTIONS draws the step's survivors, TRACKS and TRAJECTORIES the tracker's table after this
+ * step's update; either with micro_batch > 1 is ADAS_ERR_INVALID at the step (the live table holds the last frame only).  Accepts
+ * 63 | ADAS_OVERLAY_TRAJECTORIES; bit 64 is refused.  Cached graphs are dropped. */
 int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);

@@ -7,9 +7,12 @@ drawing on the host:
     hipMemcpyAsync device-to-device of the same frames between the same events, in alternation.  The copy is the yardstick: the
     streaming pass moves the same bytes plus the coverage words.  The frame stages alone (no bird view) and an empty scene (the pass as a
     pure copy plus the preparation and clean-up launches) are timed the same way to show where the time goes.  So is the object layer:
-    the frame stages plus --detections cornerRect boxes per frame, plus --tracks tracked boxes (rectangle and tint), and all six stages.
+    the frame stages plus --detections cornerRect boxes per frame, plus --tracks tracked boxes (rectangle and tint), and all six stages;
+    and the trajectories stage: the frame stages plus the --tracks tracks' circles over full 30-box rings and their direction marks (every
+    other track an arrow, the others a lock-on rectangle), and all seven stages.
 (b) fused step: two pipelines of the same two networks, bird-view image and analysis in ONE process, stepped from the same camera frames
-    in alternation: `off` as it was, `on` with overlay= (all four stages), `obj` with the detections and tracks stages as well.  A window is
+    in alternation: `off` as it was, `on` with overlay= (all four stages), `obj` with the detections and tracks stages as well, `trj` with
+    the four stages and the trajectories stage.  A window is
     --steps steps between two host clock readings with
     the pipeline drained at both ends; median window of --rounds, with the fastest and the slowest.
 (c) the host loop the stage replaces, on the `off` pipeline: sync, fetch every frame's lanes, polygon, analysis row, distance points and
@@ -40,7 +43,7 @@ ap.add_argument("--precision", default=None)
 ap.add_argument("--box-score", type=float, default=0.1)
 ap.add_argument("--detections", type=int, default=24, help="boxes per frame of the detections stage in (a)")
 ap.add_argument("--tracks", type=int, default=16, help="boxes per frame of the tracks stage in (a)")
-ap.add_argument("--no-objects", action="store_true", help="leave the object layer's variants out of (a)'s alternation and (b)")
+ap.add_argument("--no-objects", action="store_true", help="leave the object layer's and the trajectories stage's variants out of (a)'s alternation and (b)")
 ap.add_argument("--standalone-only", action="store_true", help="(a) alone, e.g. under a kernel trace")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "overlay_ab.txt"))
 a = ap.parse_args()
@@ -86,8 +89,21 @@ bw, bh = rng.integers(60, 300, (S, ND + NT)), rng.integers(50, 220, (S, ND + NT)
 obj = dict(det_xyxy=np.stack([bx, by, bx + bw, by + bh], 2)[:, :ND].astype(np.int32), det_cls=rng.integers(0, 80, (S, ND)).astype(np.int32),
            det_counts=np.full(S, ND, np.int32), trk_tlwh=np.stack([bx, by, bw, bh], 2)[:, ND:].astype(np.float64) + 0.5,
            trk_cls=rng.integers(0, 80, (S, NT)).astype(np.int32), trk_counts=np.full(S, NT, np.int32))
+# the tracks' trajectories: full rings that end on the track's box, a step of a few pixels a frame; every other track's first 26 boxes hang
+# over the bottom border (filter_trajectories drops them): 4 boxes left, a lock-on rectangle -- the others get the shadowed arrow
+tl = obj["trk_tlwh"]
+vel = np.stack([rng.uniform(-5, 5, (S, NT)), rng.uniform(-2, 2, (S, NT))], 2)
+age = np.arange(29, -1, -1, dtype=np.float64)[None, None, :, None]
+xy = np.clip(tl[:, :, None, :2] - vel[:, :, None, :] * age, 12.0, None)
+ring = np.concatenate([xy, xy + np.minimum(tl[:, :, None, 2:], 200.0)], 3)
+ring[:, :, :, 2] = np.minimum(ring[:, :, :, 2], W - 12.0)
+ring[:, :, :, 3] = np.minimum(ring[:, :, :, 3], H - 12.0)
+ring[:, 1::2, :26, 3] = H - 4.0
+obj["traj"] = np.ascontiguousarray(ring)
+obj["traj_len"] = np.full((S, NT), 30, np.int32)
 obufs = {k: L.DeviceBuffer.from_array(np.ascontiguousarray(v)) for k, v in obj.items()}
-okw = dict(kw, det_cap=ND, trk_cap=NT, **{k: b.ptr for k, b in obufs.items()})
+okw = dict(kw, det_cap=ND, trk_cap=NT, **{k: b.ptr for k, b in obufs.items() if k not in ("traj", "traj_len")})
+tkw = dict(okw, trajectories=(obufs["traj"].ptr, obufs["traj_len"].ptr))
 CLASS_COLORS = rng.integers(0, 256, (80, 3)).tolist()
 ov = PP.LaneOverlay((H, W), (H, W), S)
 ov.set_class_colors("detections", CLASS_COLORS)
@@ -110,8 +126,10 @@ variants = [("copy", lambda: hip.hipMemcpyAsync(dst, cam[0].ptr, nbytes, D2D, No
             ("overlay, empty scene", lambda: ov.run_arrays(cam[0].ptr, S, stages=7, **kw_empty)),
             ("frame stages + detections", lambda: ov.run_arrays(cam[0].ptr, S, stages=7 | 16, **okw)),
             ("frame stages + tracks", lambda: ov.run_arrays(cam[0].ptr, S, stages=7 | 32, **okw)),
-            ("all six stages", lambda: ov.run_arrays(cam[0].ptr, S, bird_ptr=bird.ptr, stages=63, **okw))]
-OBJECT_LINES = ("frame stages + detections", "frame stages + tracks", "all six stages")
+            ("all six stages", lambda: ov.run_arrays(cam[0].ptr, S, bird_ptr=bird.ptr, stages=63, **okw)),
+            ("frame stages + trajectories", lambda: ov.run_arrays(cam[0].ptr, S, stages=7 | 128, **tkw)),
+            ("all seven stages", lambda: ov.run_arrays(cam[0].ptr, S, bird_ptr=bird.ptr, stages=63 | 128, **tkw))]
+OBJECT_LINES = ("frame stages + detections", "frame stages + tracks", "all six stages", "frame stages + trajectories", "all seven stages")
 if a.no_objects:
     variants = [v for v in variants if v[0] not in OBJECT_LINES]
     OBJECT_LINES = ()
@@ -129,9 +147,11 @@ lines = ["tools/bench_overlay.py on one MI355X (gfx950).", "",
          % (S, nbytes / 1e6, nbytes / 1e6, a.rounds, a.iters),
          "    alternated in one process; us per call, median round (fastest, slowest); %.1f %% of a frame's pixels are drawn on." % (100 * drawn), ""]
 share = {}
-for name, st in (("detections", 16), ("tracks", 32)):
-    ov.run_arrays(cam[0].ptr, S, stages=st, **okw)
+for name, st in (("detections", 16), ("tracks", 32), ("trajectories", 128)):
+    ov.run_arrays(cam[0].ptr, S, stages=st, **tkw)
     share[name] = float((ov.fetch(0) != cams[0][0]).any(axis=2).mean())
+marks = ov.track_marks(0)
+n_marks = {k: int((marks["kind"] == k).sum()) for k in (1, 2, 3)}
 cm = median(us["copy"])[0]
 for n, _ in variants:
     if n in OBJECT_LINES:
@@ -145,7 +165,10 @@ lines += ["", "    ratio to the copy: %.2f (expected within 1.5).  The empty sce
 if OBJECT_LINES:
     lines += ["", "    the object layer: %d detections per frame (cornerRect: outline and eight arms, %.1f %% of a frame's pixels) and %d tracked boxes per frame"
               % (ND, 100 * share["detections"], NT), "    (thickness-2 rectangle and the tinted region, %.1f %% of a frame's pixels), one record-building launch more:"
-              % (100 * share["tracks"]), ""]
+              % (100 * share["tracks"]),
+              "    the trajectories stage: per frame the same %d tracks' full rings -- %d circles, %d lock-on rectangles, %d arrows (three to a track) in frame 0,"
+              % (NT, n_marks[1], n_marks[2], n_marks[3]), "    %.2f %% of a frame's pixels; two launches more (the primitives, one pass per band of rows that draws them):"
+              % (100 * share["trajectories"]), ""]
 for n in OBJECT_LINES:
     m, lo, hi = median(us[n])
     lines.append("    %-26s %9.1f us  (%.1f, %.1f)  %5.2f x the copy  %+8.1f us on this run's frame stages" % (n, m, lo, hi, m / cm, m - frm))
@@ -189,7 +212,10 @@ pkw = dict(n_streams=S, precision=a.precision, src_hw=(H, W), use_graph=True, tr
 pipes = [("off", PL.AdasPipeline(det_path, lane_path, **pkw)), ("on", PL.AdasPipeline(det_path, lane_path, overlay=dict(), **pkw)),
          ("obj", PL.AdasPipeline(det_path, lane_path, overlay=dict(stages=("lanes", "area", "distance", "bird", "detections", "tracks"),
                                                                     detection_colors=CLASS_COLORS, track_colors=CLASS_COLORS), **pkw))]
+pipes.append(("trj", PL.AdasPipeline(det_path, lane_path, overlay=dict(stages=("lanes", "area", "distance", "bird", "trajectories"),
+                                                                        track_colors=CLASS_COLORS), **pkw)))
 if a.no_objects:
+    pipes.pop()[1].close()
     pipes.pop()[1].close()
 count = {n: 0 for n, _ in pipes}
 OFF = {"UNKNOWN": 0, "RIGHT": 1, "LEFT": 2, "CENTER": 3}
@@ -252,7 +278,9 @@ hm, hlo, hhi = median(host)
 lines += ["", "    on - off = %+8.1f us per step (five plain launches behind the analysis stage, inside the capture); the stand-alone run takes %.1f us"
           % ((med["on"] - med["off"]) * 1e3, allm),
           ] + (["    obj - on  = %+8.1f us per step (the detections and tracks stages: the step's survivors and its tracked tracks, one launch more)"
-                % ((med["obj"] - med["on"]) * 1e3)] if "obj" in med else []) + [
+                % ((med["obj"] - med["on"]) * 1e3)] if "obj" in med else []) + (
+          ["    trj - on  = %+8.1f us per step (the trajectories stage: the tracker's live rows and rings after this step's update, two launches more)"
+           % ((med["trj"] - med["on"]) * 1e3)] if "trj" in med else []) + [
           "", "(c) the host loop the stage replaces, on the `off` pipeline after a sync: per stream 5 fetches (lanes, geometry, analysis row, distance",
           "    points, bird view) and the NumPy restatement's drawing of both images: %.1f ms per step of %d streams (fastest %.1f, slowest %.1f; %d steps),"
           % (hm, S, hlo, hhi, a.host_steps),

@@ -127,9 +127,24 @@ class OverlayObjectStyle(C.Structure):
 
 OVERLAY_LANES, OVERLAY_AREA, OVERLAY_DISTANCE, OVERLAY_BIRD = 1, 2, 4, 8     # adas_overlay_run's stages
 OVERLAY_DETECTIONS, OVERLAY_TRACKS = 16, 32                                  # the object layer: adas_overlay_run_objects / _run_arrays_objects
+OVERLAY_TRAJECTORIES = 128                                                   # adas_overlay_run_trajectories / _run_arrays_trajectories (64 is no stage)
 OVERLAY_STAGES = {"lanes": OVERLAY_LANES, "area": OVERLAY_AREA, "distance": OVERLAY_DISTANCE, "bird": OVERLAY_BIRD,
-                  "detections": OVERLAY_DETECTIONS, "tracks": OVERLAY_TRACKS}
-OVERLAY_POLY_RANGE = 1                                                       # adas_overlay_fetch_flags
+                  "detections": OVERLAY_DETECTIONS, "tracks": OVERLAY_TRACKS, "trajectories": OVERLAY_TRAJECTORIES}
+OVERLAY_POLY_RANGE, OVERLAY_TRACK_RANGE = 1, 2                               # adas_overlay_fetch_flags
+TRAJECTORY_LEN = 30
+TRACK_MARK_CIRCLE, TRACK_MARK_RECT, TRACK_MARK_ARROW = 1, 2, 3
+
+
+class OverlayArrays(C.Structure):                                            # adas_overlay_arrays
+    _fields_ = [(n, C.c_void_p) for n in ("d_src_bgr", "d_dst_bgr", "d_lane_points", "d_lane_counts", "d_poly", "d_poly_counts", "d_area_status",
+                                          "d_offset_type", "d_area_bgr", "d_dist_points", "d_dist_counts", "d_bird_points", "d_bird_counts",
+                                          "d_bird_bgr", "d_det_xyxy", "d_det_cls", "d_det_counts", "d_trk_tlwh", "d_trk_cls", "d_trk_counts",
+                                          "d_traj_tlbr", "d_traj_len", "stream")] + \
+               [(n, C.c_int32) for n in ("poly_cap", "dist_cap", "det_cap", "trk_cap", "stages", "n_frames")]
+
+
+TRACK_MARK_DTYPE = np.dtype([("kind", "i4"), ("track", "i4"), ("x1", "i4"), ("y1", "i4"), ("x2", "i4"), ("y2", "i4"), ("radius", "i4"),
+                             ("thickness", "i4"), ("tip", "i4", (4,)), ("color", "u1", (3,)), ("skipped", "u1")])   # adas_overlay_track_mark
 
 
 class BytetrackParams(C.Structure):
@@ -293,6 +308,9 @@ _SIGS = {
     "adas_overlay_run_objects": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "adas_overlay_run_arrays_objects": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P,
                                                   _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_trajectories": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_arrays_trajectories": (C.c_int, [_P, C.POINTER(OverlayArrays)]),
+    "adas_overlay_fetch_track_marks": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32)]),
     "adas_overlay_default_object_style": (C.c_int, [C.POINTER(OverlayObjectStyle)]),
     "adas_overlay_set_object_style": (C.c_int, [_P, C.POINTER(OverlayObjectStyle)]),
     "adas_overlay_set_class_colors": (C.c_int, [_P, C.c_int, _P, C.c_int]),

@@ -58,8 +58,15 @@ int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_
 void post_survivor_views(const ::adas_yolo_post* h, const int** xyxy_int, const int** cls, const int** counts, int* cap);
 void tracker_live_views(const ::adas_bytetrack* h, const unsigned char** hdr, const unsigned char** out, size_t* stream_bytes, int* n_streams,
                         int* max_tracks);
+// the trajectory rings behind the live table (post_kernels.hip), stream s at + s * stream_bytes: the tracked list's slot ids [max_tracks] int,
+// the first slot's count of boxes ever appended (the next slot's slot_bytes further on), and the rings [max_tracks][30][4] fp64 by slot,
+// entry i of a track's list at i % 30
+void tracker_ring_views(const ::adas_bytetrack* h, const unsigned char** tracked_slots, const unsigned char** appended, size_t* slot_bytes,
+                        const unsigned char** rings);
 // room for the records of det_cap + trk_cap boxes per frame, ahead of a captured step (overlay_kernels.hip)
 int overlay_reserve_objects(::adas_overlay* h, int det_cap, int trk_cap);
+// the same for the trajectories stage: the primitives of trk_cap tracks per frame and the stage's plane
+int overlay_reserve_trajectories(::adas_overlay* h, int trk_cap);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

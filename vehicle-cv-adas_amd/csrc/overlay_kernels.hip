@@ -33,6 +33,7 @@
 #include <initializer_list>
 #include <new>
 #include "overlay_core.h"
+#include "overlay_track_core.h"
 
 using namespace adas;
 
@@ -623,6 +624,194 @@ __global__ __launch_bounds__(OV_THREADS) void overlay_apply_kernel(OvDev d, size
     }
 }
 
+// ---- the trajectories stage (ADAS_OVERLAY_TRAJECTORIES: plot_trajectories' circles, plot_directions' rectangle or arrows; rules D10-D12 of
+// overlay_track_core.h).  A sparse pass of its own beside the streaming pass, which it does not touch:
+//   overlay_track_prims_kernel   one lane per track row: the trajectory ring -> at most ADAS_OVERLAY_TRACK_PRIMS 64-byte primitives in the
+//                                track's slots, and a 32-byte head (their number, the box around them)
+//   overlay_tracks_draw_kernel   behind the streaming pass and ahead of the clean-up, one workgroup per band of rows: the primitives that meet
+//                                the band are listed in LDS, every (listed primitive, row) pair ORs its runs into one more plane -- which
+//                                lives in LDS only --, and every marked pixel without a distance disc takes the colour of the last
+//                                primitive that hits it, folded through the later tracks' outline and tint when TRACKS is on (the fold of
+//                                overlay_track_core.h: no earlier pixel value is needed, so the pass is legal in place).
+constexpr int OV_TRK_LANES = 64;    // tracks of a workgroup of the primitive kernel
+constexpr int OV_TRK_WORK = 2 * (ADAS_OVERLAY_TRACK_RING - 1);   // doubles of one track's direction list
+constexpr int OV_TRK_LIST = OV_THREADS;   // slots of a frame's primitive list a band takes at a time, one per thread (their records: 16 KB of LDS)
+static_assert(sizeof(OverlayPrim) == 64 && sizeof(OverlayTrackHead) == 32, "the primitive records' layout");
+
+struct OvTracks {                   // the tracks one run reads, per frame q
+    const unsigned char* tlwh;      // row k: 4 doubles at tlwh + q * frame_bytes + k * row_bytes
+    const unsigned char* cls;       // an int at cls + q * cls_frame_bytes + k * cls_row_bytes
+    const unsigned char* act;       // is_activated, an int at the strides of tlwh, or null: every row is
+    const unsigned char* cnt;       // rows of frame q: an int at cnt + q * cnt_bytes
+    size_t frame_bytes, row_bytes, cls_frame_bytes, cls_row_bytes, cnt_bytes;
+    int trk_cap;
+    // row k's trajectory: ring `slot` of frame q, 30 x 4 doubles at ring + q * ring_frame_bytes + slot * 960
+    const unsigned char* ring;
+    size_t ring_frame_bytes;
+    const unsigned char* slot_ids;  // null: slot = k, the ring is stored oldest first; else the slot is the int at slot_ids + q * slot_frame_bytes + k * 4
+    size_t slot_frame_bytes;
+    const unsigned char* len;       // slot_ids null: len(trajectory), an int at len + q * len_frame_bytes + k * 4; else the boxes ever appended,
+    size_t len_frame_bytes, len_row_bytes;   // an int at len + q * len_frame_bytes + slot * len_row_bytes (entry i of the list lives at i % 30)
+};
+
+struct OvTrkDev {
+    OvTracks t;
+    int H, W, rw, band;
+    const uint32_t* colors;         // packed class colours of the tracks
+    int n_colors;
+    double min_box_area;
+    int tab[2 * ADAS_OVERLAY_TRACK_RING];   // overlay_mark_table: radii, then thicknesses
+    OverlayPrim* prims;             // [q][trk_cap][ADAS_OVERLAY_TRACK_PRIMS]
+    OverlayTrackHead* heads;        // [q][trk_cap]
+    int* cnt;                       // [q]: track rows
+    const uint32_t* detail;         // the frame's detail planes: word 5 of a group is the distance discs'
+    int* flags;
+    const OverlayObject* objs;      // TRACKS on: frame q's track records at objs + q * obj_stride, row k at [k]; else null
+    size_t obj_stride;
+    int radii;                      // overlay_obj_radii of the object style
+    uint8_t* dst;
+};
+
+__global__ __launch_bounds__(OV_TRK_LANES) void overlay_track_prims_kernel(OvTrkDev d) {
+    __shared__ double work[OV_TRK_WORK * OV_TRK_LANES];   // element j of lane l at work[j * OV_TRK_LANES + l]
+    __shared__ int tab[2 * ADAS_OVERLAY_TRACK_RING];
+    const size_t f = blockIdx.y;
+    const int tid = threadIdx.x, k = blockIdx.x * OV_TRK_LANES + tid;
+    if (tid < 2 * ADAS_OVERLAY_TRACK_RING) tab[tid] = d.tab[tid];
+    __syncthreads();
+    const int nt = ov_clampi(*(const int*)(d.t.cnt + f * d.t.cnt_bytes), 0, d.t.trk_cap);
+    if (blockIdx.x == 0 && tid == 0) d.cnt[f] = nt;
+    if (k >= nt) return;
+    const size_t at = f * d.t.frame_bytes + k * d.t.row_bytes;
+    const int act = d.t.act ? *(const int*)(d.t.act + at) : 1;
+    const int cls = *(const int*)(d.t.cls + f * d.t.cls_frame_bytes + k * d.t.cls_row_bytes);
+    int slot = k, len = 0, start = 0;
+    if (d.t.slot_ids) {   // the tracker's rings: through the slot the message row names
+        slot = *(const int*)(d.t.slot_ids + f * d.t.slot_frame_bytes + (size_t)k * 4);
+        if (slot >= 0 && slot < d.t.trk_cap) {
+            const int n = *(const int*)(d.t.len + f * d.t.len_frame_bytes + slot * d.t.len_row_bytes);
+            len = ov_clampi(n, 0, ADAS_OVERLAY_TRACK_RING);
+            start = n > len ? (n - len) % ADAS_OVERLAY_TRACK_RING : 0;
+        } else {
+            slot = 0;   // not a slot of the table: no trajectory
+        }
+    } else {
+        len = ov_clampi(*(const int*)(d.t.len + f * d.t.len_frame_bytes + (size_t)k * 4), 0, ADAS_OVERLAY_TRACK_RING);
+    }
+    const double* ring = (const double*)(d.t.ring + f * d.t.ring_frame_bytes + (size_t)slot * (ADAS_OVERLAY_TRACK_RING * 32));
+    OverlayPrim* out = d.prims + (f * d.t.trk_cap + k) * ADAS_OVERLAY_TRACK_PRIMS;
+    int range = 0;
+    const int n = overlay_track_prims((const double*)(d.t.tlwh + at), act, d.min_box_area, overlay_class_colour(cls, d.colors, d.n_colors), ring, start,
+                                      len, tab, tab + ADAS_OVERLAY_TRACK_RING, d.W, d.H, work + tid, OV_TRK_LANES, out, &range);
+    d.heads[f * d.t.trk_cap + k] = overlay_track_head(out, n, range);
+}
+
+struct LdsFillOps {   // overlay_prim_row on a band's LDS bitmap
+    uint32_t* roww;
+    __device__ void fill(int xl, int xr) { ov_lds_span(roww, xl, xr); }
+};
+
+// grid (ceil(H / band), frames); dynamic LDS: 2 * band * rw words.  One workgroup owns rows [y0, y0 + band) of one frame.  The frame's slots
+// (track k, primitive i: slot k * ADAS_OVERLAY_TRACK_PRIMS + i, the drawing order) are taken OV_TRK_LIST at a time, one per thread, from the
+// LAST to the first: the primitives of the chunk that meet the band are copied to LDS in slot order (a ballot and a prefix count: the list
+// stays sorted), every (listed primitive, row) pair ORs its runs into the band's plane, and every marked pixel that no later chunk has
+// drawn walks the list from its end: the first hit is the last primitive drawn there, and the pixel takes the fold of
+// overlay_track_core.h from it unless a distance disc covers it.  Nothing is truncated: a longer list is more chunks.
+__global__ __launch_bounds__(OV_THREADS) void overlay_tracks_draw_kernel(OvTrkDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int hw[(ADAS_OVERLAY_TRACK_MAX_R + 1) * ADAS_OVERLAY_TRACK_HW];
+    __shared__ int ohw[3 * OV_HW];
+    __shared__ __attribute__((aligned(16))) OverlayPrim list[OV_TRK_LIST];
+    __shared__ int lslot[OV_TRK_LIST];
+    __shared__ int wcount[OV_THREADS / 64];
+    const size_t f = blockIdx.y;
+    const int tid = threadIdx.x, rw = d.rw, per = d.band * rw;
+    uint32_t* plane = (uint32_t*)smem;   // [band][rw]: this chunk's coverage
+    uint32_t* done = plane + per;        // [band][rw]: drawn by a later chunk
+    const int y0 = blockIdx.x * d.band;
+    const int rows = d.H - y0 < d.band ? d.H - y0 : d.band;
+    for (int i = tid; i < per; i += OV_THREADS) done[i] = 0u;
+    if (tid <= ADAS_OVERLAY_TRACK_MAX_R) overlay_track_halfwidths(tid, hw);
+    else if (tid < ADAS_OVERLAY_TRACK_MAX_R + 4) {
+        const int which = tid - ADAS_OVERLAY_TRACK_MAX_R - 1;
+        overlay_disc_halfwidths((d.radii >> (8 * which)) & 0xff, ohw + which * OV_HW);
+    }
+    const int nt = d.cnt[f];
+    const OverlayTrackHead* heads = d.heads + f * d.t.trk_cap;
+    const OverlayPrim* prims = d.prims + f * d.t.trk_cap * ADAS_OVERLAY_TRACK_PRIMS;
+    const OverlayObject* objs = d.objs ? d.objs + f * d.obj_stride : nullptr;
+    if (blockIdx.x == 0 && tid == 0 && d.flags) {   // behind the coverage kernel, which stores the frame's other flags
+        int range = 0;
+        for (int k = 0; k < nt; ++k) range |= heads[k].range;
+        if (range) d.flags[f] |= ADAS_OVERLAY_TRACK_RANGE;
+    }
+    const OverlayTrackStyle s{hw};
+    OverlayObjStyle os;
+    os.radii = d.radii; os.hw = ohw; os.hw_stride = OV_HW;
+    for (int c1 = nt * ADAS_OVERLAY_TRACK_PRIMS; c1 > 0; c1 -= OV_TRK_LIST) {
+        const int c0 = c1 > OV_TRK_LIST ? c1 - OV_TRK_LIST : 0;
+        for (int i = tid; i < per; i += OV_THREADS) plane[i] = 0u;
+        const int q = c0 + tid;   // this thread's slot
+        bool meets = false;
+        if (q < c1) {
+            const int k = q / ADAS_OVERLAY_TRACK_PRIMS, i = q - k * ADAS_OVERLAY_TRACK_PRIMS;
+            const OverlayTrackHead h = heads[k];
+            if (i < h.n && h.y1 >= y0 && h.y0 < y0 + rows) {
+                const OverlayPrim* p = prims + q;
+                const int px0 = p->x0, py0 = p->y0, px1 = p->x1, py1 = p->y1;
+                meets = px0 <= px1 && py1 >= y0 && py0 < y0 + rows;
+            }
+        }
+        const unsigned long long bal = __ballot(meets);
+        const int lane = tid & 63, wv = tid >> 6;
+        if (lane == 0) wcount[wv] = __popcll(bal);
+        __syncthreads();   // also: the tables, `done`, the plane, and the previous chunk's pixels
+        int at = __popcll(bal & ((1ull << lane) - 1ull)), m = 0;
+        for (int w = 0; w < OV_THREADS / 64; ++w) {
+            if (w < wv) at += wcount[w];
+            m += wcount[w];
+        }
+        if (meets) {
+            const uint4* src = reinterpret_cast<const uint4*>(prims + q);
+            uint4* dst = reinterpret_cast<uint4*>(list + at);
+            dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+            lslot[at] = q;
+        }
+        __syncthreads();
+        if (m > 0) {   // uniform
+            for (int t = tid; t < m * rows; t += OV_THREADS) {
+                const int e = t / rows, r = t - e * rows;
+                LdsFillOps ops{plane + r * rw};
+                overlay_prim_row(list[e], s, y0 + r, d.W, ops);
+            }
+            __syncthreads();
+            for (int t = tid; t < rows * rw * 32; t += OV_THREADS) {   // one lane per pixel of the band
+                const int wi = t >> 5, b = t & 31;
+                if (!(((plane[wi] & ~done[wi]) >> b) & 1u)) continue;
+                const int r = wi / rw, x = (wi - r * rw) * 32 + b, y = y0 + r;
+                int e = m - 1;
+                while (e >= 0 && !overlay_prim_hit(list[e], s, x, y)) --e;   // the list is in drawing order: the first hit from its end
+                if (e < 0) continue;   // (the runs and the test agree: not expected)
+                const int best = lslot[e];
+                atomicOr(done + wi, 1u << b);
+                const size_t gw = (f * d.H + y) * (size_t)rw + (wi - r * rw);
+                if ((d.detail[gw * 8 + 5] >> b) & 1u) continue;   // DISTANCE overrides everything
+                const uint32_t c = list[e].colour;
+                int bgr[3] = {(int)(c & 0xffu), (int)((c >> 8) & 0xffu), (int)((c >> 16) & 0xffu)};
+                if (objs)
+                    for (int j = best / ADAS_OVERLAY_TRACK_PRIMS + 1; j < nt; ++j) {
+                        const int ops = overlay_object_ops(objs[j], x, y, os);
+                        if (!ops) continue;
+                        for (int ch = 0; ch < 3; ++ch) bgr[ch] = overlay_object_channel(bgr[ch], ops, objs[j].colour, ch);
+                    }
+                uint8_t* px = d.dst + ((f * d.H + y) * (size_t)d.W + x) * 3;
+                px[0] = (uint8_t)bgr[0]; px[1] = (uint8_t)bgr[1]; px[2] = (uint8_t)bgr[2];
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 struct adas_overlay {
@@ -643,6 +832,12 @@ struct adas_overlay {
     OverlayObject* recs = nullptr;                          // [max_batch][rec_slots]
     int rec_slots = 0;
     int* rec_cnt = nullptr;                                 // [max_batch][2]
+    // the trajectories stage: allocated when first asked for (overlay_reserve_tracks)
+    OverlayPrim* trj_prims = nullptr;                       // [max_batch][trj_cap][ADAS_OVERLAY_TRACK_PRIMS]
+    OverlayTrackHead* trj_heads = nullptr;                  // [max_batch][trj_cap]
+    int* trj_cnt = nullptr;                                 // [max_batch]
+    int trj_cap = 0;
+    int trj_run_cap = 0, trj_run_frames = 0;                // the last run with the stage: its trk_cap and frames (0: none yet)
     size_t frame_bytes() const { return (size_t)p.src_h * p.src_w * 3; }
 };
 
@@ -704,8 +899,38 @@ static int overlay_reserve_records(adas_overlay* h, int slots) {
     return ADAS_OK;
 }
 
+// room for the primitives of trk_cap tracks per frame.  Allocates: not inside a stream capture
+static int overlay_reserve_tracks(adas_overlay* h, int trk_cap) {
+    if (!h->trj_cnt) {
+        int* cnt = nullptr;
+        hipError_t e = hipMalloc((void**)&cnt, (size_t)h->max_batch * 4);
+        if (e == hipSuccess) e = hipMemset(cnt, 0, (size_t)h->max_batch * 4);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            if (cnt) (void)hipFree(cnt);
+            return hip_fail(e, "hipMalloc(overlay track counts)", __FILE__, __LINE__);
+        }
+        h->trj_cnt = cnt;
+        adas::bump_config_generation();
+    }
+    if (trk_cap <= h->trj_cap) return ADAS_OK;
+    ADAS_HIP_TRY(hipDeviceSynchronize());   // a run in flight may still read the old tables
+    if (h->trj_prims) (void)hipFree(h->trj_prims);
+    if (h->trj_heads) (void)hipFree(h->trj_heads);
+    h->trj_prims = nullptr;
+    h->trj_heads = nullptr;
+    h->trj_cap = 0;
+    h->trj_run_cap = h->trj_run_frames = 0;
+    ADAS_HIP_TRY(hipMalloc((void**)&h->trj_prims, (size_t)h->max_batch * trk_cap * ADAS_OVERLAY_TRACK_PRIMS * sizeof(OverlayPrim)));
+    ADAS_HIP_TRY(hipMalloc((void**)&h->trj_heads, (size_t)h->max_batch * trk_cap * sizeof(OverlayTrackHead)));
+    h->trj_cap = trk_cap;
+    adas::bump_config_generation();   // a captured step holds the old tables' addresses in its kernel arguments
+    return ADAS_OK;
+}
+
 namespace adas {
 int overlay_reserve_objects(::adas_overlay* h, int det_cap, int trk_cap) { return h ? overlay_reserve_records(h, det_cap + trk_cap) : ADAS_OK; }
+int overlay_reserve_trajectories(::adas_overlay* h, int trk_cap) { return h ? overlay_reserve_tracks(h, trk_cap) : ADAS_OK; }
 }  // namespace adas
 
 static int overlay_check_object_style(const adas_overlay_object_style* p, const char* who) {
@@ -719,9 +944,10 @@ static int overlay_check_object_style(const adas_overlay_object_style* p, const 
 
 // the launches of one run; `s` holds the sources, bird_pts / bird_cnt (stride bird_cnt_stride) the bird view's, `obj` the boxes (stages 16 / 32)
 static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvSources s, const int* bird_pts, const int* bird_cnt, int bird_cnt_stride,
-                          uint8_t* d_bird, int stages, int frames, hipStream_t st, const OvObjects* obj = nullptr) {
+                          uint8_t* d_bird, int stages, int frames, hipStream_t st, const OvObjects* obj = nullptr, const OvTracks* trk = nullptr) {
     const int frame_stages = stages & (ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | ADAS_OVERLAY_DISTANCE | OV_OBJ_STAGES);
-    if (frame_stages) {
+    const bool traj = (stages & ADAS_OVERLAY_TRAJECTORIES) != 0;   // two launches of its own; without it neither, and nothing else changes
+    if (frame_stages || traj) {
         if (!dst) {
             int rc = overlay_own_buffer(h);
             if (rc) return rc;
@@ -754,6 +980,31 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
             hipLaunchKernelGGL(overlay_objects_kernel, dim3((unsigned)frames), dim3(OV_THREADS), 0, st, d);
             ADAS_HIP_TRY(hipGetLastError());
         }
+        OvTrkDev td;
+        if (traj) {   // the tracks' primitives, beside the boxes' records
+            int rc = overlay_reserve_tracks(h, trk->trk_cap);
+            if (rc) return rc;
+            memset(&td, 0, sizeof(td));
+            td.t = *trk;
+            td.H = d.H; td.W = d.W; td.rw = d.rw;
+            td.band = overlay_band(d.rw, 2);
+            td.colors = h->colors[1]; td.n_colors = h->n_colors[1];
+            td.min_box_area = h->os.min_box_area;
+            overlay_mark_table(td.tab, td.tab + ADAS_OVERLAY_TRACK_RING);
+            td.prims = h->trj_prims; td.heads = h->trj_heads; td.cnt = h->trj_cnt;
+            td.detail = h->detail; td.flags = h->flags;
+            if (frame_stages & ADAS_OVERLAY_TRACKS) {   // the later tracks' outline and tint fold over a primitive's colour
+                td.objs = h->recs + d.o.det_cap;
+                td.obj_stride = (size_t)d.o.det_cap + d.o.trk_cap;
+            }
+            td.radii = overlay_obj_radii(h->os.det_rect_thickness, h->os.det_arm_thickness, h->os.track_thickness);
+            td.dst = d.dst;
+            hipLaunchKernelGGL(overlay_track_prims_kernel, dim3((unsigned)((trk->trk_cap + OV_TRK_LANES - 1) / OV_TRK_LANES), (unsigned)frames),
+                               dim3(OV_TRK_LANES), 0, st, td);
+            ADAS_HIP_TRY(hipGetLastError());
+            h->trj_run_cap = trk->trk_cap;
+            h->trj_run_frames = frames;
+        }
         d.band = overlay_band(d.rw, nplanes);
         const OvDev plain = d;   // the kernels without the object layer take the arguments they always took
         if (frame_stages & OV_OBJ_STAGES)
@@ -771,6 +1022,11 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
         else hipLaunchKernelGGL(overlay_stream_kernel, dim3(gx, (unsigned)frames), dim3(OV_THREADS), 0, st, plain);
         ADAS_HIP_TRY(hipGetLastError());
         const size_t words = (size_t)frames * d.H * d.rw;
+        if (traj) {   // behind the streaming pass, whose bytes it overwrites, and ahead of the clean-up: it reads the distance discs' plane
+            hipLaunchKernelGGL(overlay_tracks_draw_kernel, dim3((unsigned)((td.H + td.band - 1) / td.band), (unsigned)frames), dim3(OV_THREADS),
+                               (size_t)2 * td.band * td.rw * 4, st, td);
+            ADAS_HIP_TRY(hipGetLastError());
+        }
         hipLaunchKernelGGL(overlay_clean_kernel, dim3(overlay_grid(words)), dim3(OV_THREADS), 0, st, plain, words);
         ADAS_HIP_TRY(hipGetLastError());
         if (!dst && frames > h->dst_frames) h->dst_frames = frames;
@@ -833,6 +1089,7 @@ static int overlay_run_handles(const char* who, int mask, adas_overlay* h, const
                  "%s: %d frames, the analysis handle holds %d", who, (int)frames, af);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || post, ADAS_ERR_INVALID, "%s: the detections stage needs a yolo_post handle", who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || tracker, ADAS_ERR_INVALID, "%s: the tracks stage needs a bytetrack handle", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || tracker, ADAS_ERR_INVALID, "%s: the trajectories stage needs a bytetrack handle", who);
     OvObjects o;
     memset(&o, 0, sizeof(o));
     if (stages & ADAS_OVERLAY_DETECTIONS) {
@@ -855,6 +1112,24 @@ static int overlay_run_handles(const char* who, int mask, adas_overlay* h, const
         o.trk_cls = o.trk_tlwh + offsetof(adas_track, class_id);
         o.trk_cls_frame_bytes = o.trk_frame_bytes; o.trk_cls_row_bytes = o.trk_row_bytes;
         o.trk_act = o.trk_tlwh + offsetof(adas_track, is_activated);
+    }
+    OvTracks t;
+    memset(&t, 0, sizeof(t));
+    if (stages & ADAS_OVERLAY_TRAJECTORIES) {
+        ADAS_REQUIRE(n_frames == 1, ADAS_ERR_INVALID,
+                     "%s: the trajectories stage draws the tracker's live table, which holds the last frame only: n_frames must be 1 (got %d)", who,
+                     n_frames);
+        int ts = 0;
+        adas::tracker_live_views(tracker, &t.cnt, &t.tlwh, &t.frame_bytes, &ts, &t.trk_cap);
+        ADAS_REQUIRE(n_streams <= ts, ADAS_ERR_INVALID, "%s: %d streams, the bytetrack handle holds %d", who, n_streams, ts);
+        t.cnt += offsetof(adas_track_header, n_tracked);
+        t.cnt_bytes = t.frame_bytes;
+        t.row_bytes = sizeof(adas_track);
+        t.cls = t.tlwh + offsetof(adas_track, class_id);
+        t.cls_frame_bytes = t.frame_bytes; t.cls_row_bytes = t.row_bytes;
+        t.act = t.tlwh + offsetof(adas_track, is_activated);
+        adas::tracker_ring_views(tracker, &t.slot_ids, &t.len, &t.len_row_bytes, &t.ring);   // the rings, through the slot each row names
+        t.slot_frame_bytes = t.len_frame_bytes = t.ring_frame_bytes = t.frame_bytes;
     }
     OvSources s;
     memset(&s, 0, sizeof(s));
@@ -886,7 +1161,7 @@ static int overlay_run_handles(const char* who, int mask, adas_overlay* h, const
         s.dist_pts = pts; s.dist_cap = maxp;
         s.dist_cnt = fr + offsetof(adas_analysis_frame, n_points) / 4; s.dist_cnt_stride = stride;
     }
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, bird_pts, bird_cnt, 8, d_bird_bgr, stages, (int)frames, (hipStream_t)stream, &o);
+    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, bird_pts, bird_cnt, 8, d_bird_bgr, stages, (int)frames, (hipStream_t)stream, &o, &t);
 }
 
 // adas_overlay_run_arrays (mask 15, no box arrays) and adas_overlay_run_arrays_objects (mask 63)
@@ -895,8 +1170,11 @@ static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const uin
                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr,
                            const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts, const double* d_trk_tlwh,
-                           int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages, int n_frames, void* stream) {
+                           int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages, int n_frames, void* stream,
+                           const double* d_traj_tlbr = nullptr, const int32_t* d_traj_len = nullptr) {
     OV_RUN_REQUIRE(who, n_frames, mask);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || (d_trk_tlwh && trk_cap > 0 && d_trk_cls && d_trk_counts && d_traj_tlbr && d_traj_len),
+                 ADAS_ERR_INVALID, "%s: the trajectories stage needs the tracks' boxes, classes and counts, and their trajectories and lengths", who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || (d_lane_points && d_lane_counts), ADAS_ERR_INVALID, "%s: the lane stage needs lane points and counts",
                  who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_AREA) || (d_poly && poly_cap > 0 && d_poly_counts && d_area_status), ADAS_ERR_INVALID,
@@ -930,7 +1208,16 @@ static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const uin
         o.trk_cls = (const unsigned char*)d_trk_cls; o.trk_cls_frame_bytes = (size_t)trk_cap * 4; o.trk_cls_row_bytes = 4; o.trk_act = nullptr;
         o.trk_cnt = (const unsigned char*)d_trk_counts; o.trk_cnt_bytes = 4; o.trk_cap = trk_cap;
     }
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, d_bird_points, d_bird_counts, 4, d_bird_bgr, stages, n_frames, (hipStream_t)stream, &o);
+    OvTracks t;
+    memset(&t, 0, sizeof(t));
+    if (stages & ADAS_OVERLAY_TRAJECTORIES) {
+        t.tlwh = (const unsigned char*)d_trk_tlwh; t.frame_bytes = (size_t)trk_cap * 32; t.row_bytes = 32;
+        t.cls = (const unsigned char*)d_trk_cls; t.cls_frame_bytes = (size_t)trk_cap * 4; t.cls_row_bytes = 4; t.act = nullptr;
+        t.cnt = (const unsigned char*)d_trk_counts; t.cnt_bytes = 4; t.trk_cap = trk_cap;
+        t.ring = (const unsigned char*)d_traj_tlbr; t.ring_frame_bytes = (size_t)trk_cap * ADAS_OVERLAY_TRACK_RING * 32;
+        t.len = (const unsigned char*)d_traj_len; t.len_frame_bytes = (size_t)trk_cap * 4; t.len_row_bytes = 4;
+    }
+    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, d_bird_points, d_bird_counts, 4, d_bird_bgr, stages, n_frames, (hipStream_t)stream, &o, &t);
 }
 
 extern "C" {
@@ -991,7 +1278,8 @@ int adas_overlay_create(const adas_overlay_params* p, int max_batch, adas_overla
 int adas_overlay_destroy(adas_overlay* h) {
     if (!h) return ADAS_OK;
     for (void* q : {(void*)h->any, (void*)h->detail, (void*)h->bird_any, (void*)h->bird_detail, (void*)h->flags, (void*)h->d_dst,
-                    (void*)h->rec_cnt, (void*)h->recs, (void*)h->colors[0], (void*)h->colors[1]})
+                    (void*)h->rec_cnt, (void*)h->recs, (void*)h->colors[0], (void*)h->colors[1], (void*)h->trj_prims, (void*)h->trj_heads,
+                    (void*)h->trj_cnt})
         if (q) (void)hipFree(q);
     delete h;
     return ADAS_OK;
@@ -1041,6 +1329,58 @@ int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, u
     return overlay_run_raw("adas_overlay_run_arrays_objects", 63, h, d_src_bgr, d_dst_bgr, d_lane_points, d_lane_counts, d_poly, poly_cap, d_poly_counts,
                            d_area_status, d_offset_type, d_area_bgr, d_dist_points, dist_cap, d_dist_counts, d_bird_points, d_bird_counts, d_bird_bgr,
                            d_det_xyxy, det_cap, d_det_cls, d_det_counts, d_trk_tlwh, trk_cap, d_trk_cls, d_trk_counts, stages, n_frames, stream);
+}
+
+int adas_overlay_run_trajectories(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
+                                  adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr,
+                                  int stages, int n_streams, int n_frames, void* stream) {
+    return overlay_run_handles("adas_overlay_run_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, post,
+                               tracker, d_bird_bgr, stages, n_streams, n_frames, stream);
+}
+
+int adas_overlay_run_arrays_trajectories(adas_overlay* h, const adas_overlay_arrays* a) {
+    ADAS_REQUIRE(a, ADAS_ERR_INVALID, "adas_overlay_run_arrays_trajectories: null argument");
+    return overlay_run_raw("adas_overlay_run_arrays_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, a->d_src_bgr, a->d_dst_bgr, a->d_lane_points,
+                           a->d_lane_counts, a->d_poly, a->poly_cap, a->d_poly_counts, a->d_area_status, a->d_offset_type, a->d_area_bgr, a->d_dist_points,
+                           a->dist_cap, a->d_dist_counts, a->d_bird_points, a->d_bird_counts, a->d_bird_bgr, a->d_det_xyxy, a->det_cap, a->d_det_cls,
+                           a->d_det_counts, a->d_trk_tlwh, a->trk_cap, a->d_trk_cls, a->d_trk_counts, a->stages, a->n_frames, a->stream, a->d_traj_tlbr,
+                           a->d_traj_len);
+}
+
+int adas_overlay_fetch_track_marks(adas_overlay* h, int frame, adas_overlay_track_mark* marks, int max_marks, int32_t* n_marks) {
+    ADAS_REQUIRE(h && n_marks && max_marks >= 0 && (marks || max_marks == 0) && frame >= 0 && frame < h->max_batch, ADAS_ERR_INVALID,
+                 "adas_overlay_fetch_track_marks: bad argument");
+    ADAS_REQUIRE(frame < h->trj_run_frames, ADAS_ERR_INVALID,
+                 "adas_overlay_fetch_track_marks: frame %d was not part of a run with the trajectories stage (the last one had %d frames)", frame,
+                 h->trj_run_frames);
+    ADAS_HIP_TRY(hipStreamSynchronize(h->last));
+    const int cap = h->trj_run_cap;
+    int nt = 0;
+    ADAS_HIP_TRY(hipMemcpy(&nt, h->trj_cnt + frame, 4, hipMemcpyDeviceToHost));
+    nt = nt < 0 ? 0 : (nt > cap ? cap : nt);
+    OverlayTrackHead* heads = new (std::nothrow) OverlayTrackHead[nt > 0 ? nt : 1];
+    OverlayPrim* prims = new (std::nothrow) OverlayPrim[(size_t)(nt > 0 ? nt : 1) * ADAS_OVERLAY_TRACK_PRIMS];
+    hipError_t e = hipSuccess;
+    if (heads && prims && nt > 0) {
+        e = hipMemcpy(heads, h->trj_heads + (size_t)frame * cap, (size_t)nt * sizeof(OverlayTrackHead), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(prims, h->trj_prims + (size_t)frame * cap * ADAS_OVERLAY_TRACK_PRIMS, (size_t)nt * ADAS_OVERLAY_TRACK_PRIMS * sizeof(OverlayPrim),
+                          hipMemcpyDeviceToHost);
+    }
+    int n = 0;
+    if (heads && prims && e == hipSuccess) {
+        for (int k = 0; k < nt; ++k) {
+            const OverlayPrim* p = prims + (size_t)k * ADAS_OVERLAY_TRACK_PRIMS;
+            n = overlay_track_marks(p, heads[k].n, k, marks, max_marks, n);
+        }
+    }
+    const bool oom = !heads || !prims;
+    delete[] heads;
+    delete[] prims;
+    ADAS_REQUIRE(!oom, ADAS_ERR_INVALID, "out of host memory");
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(overlay track marks)", __FILE__, __LINE__);
+    *n_marks = n;
+    return ADAS_OK;
 }
 
 int adas_overlay_default_object_style(adas_overlay_object_style* p) {

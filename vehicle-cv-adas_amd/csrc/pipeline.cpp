@@ -187,7 +187,18 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             rc = adas_warp_device_view(p->bird_warp, &bird_img);
             if (rc) return rc;
         }
-        if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the object layer: this step's survivors, the tracker after this step's update
+        if (stages & ADAS_OVERLAY_TRAJECTORIES) {   // the tracks' trajectories and direction marks, under the conditions of the tracks stage
+            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
+                         "the overlay's detections stage needs a detector with its post handle");
+            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
+                         "the overlay's tracks stage needs a tracker (and the detector that feeds it)");
+            ADAS_REQUIRE(p->d.tracker && p->d.detector, ADAS_ERR_INVALID, "the overlay's trajectories stage needs a tracker (and the detector that feeds it)");
+            ADAS_REQUIRE(B <= 1, ADAS_ERR_INVALID,
+                         "the overlay's %s stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step",
+                         (stages & ADAS_OVERLAY_TRACKS) ? "tracks" : "trajectories", B);
+            rc = adas_overlay_run_trajectories(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
+                                               const_cast<uint8_t*>(bird_img), stages, NS, B, st);
+        } else if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the object layer: this step's survivors, the tracker after this step's update
             ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
                          "the overlay's detections stage needs a detector with its post handle");
             ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
@@ -374,7 +385,8 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
 
 int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
     ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: no overlay handle attached");
-    ADAS_REQUIRE(stages >= 0 && !(stages & ~63), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: unknown stage bits 0x%x", stages);
+    ADAS_REQUIRE(stages >= 0 && !(stages & ~(63 | ADAS_OVERLAY_TRAJECTORIES)), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_stages: unknown stage bits 0x%x",
+                 stages);
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
     if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the boxes' records are allocated now: a captured step cannot
@@ -385,6 +397,14 @@ int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
         if ((stages & ADAS_OVERLAY_DETECTIONS) && p->d.post) adas::post_survivor_views(p->d.post, &a, &b, &c, &det_cap);
         if ((stages & ADAS_OVERLAY_TRACKS) && p->d.tracker) adas::tracker_live_views(p->d.tracker, &hdr, &out, &sb, &ts, &trk_cap);
         int rc = adas::overlay_reserve_objects(p->overlay, det_cap, trk_cap);
+        if (rc) return rc;
+    }
+    if ((stages & ADAS_OVERLAY_TRAJECTORIES) && p->d.tracker) {   // so are the tracks' primitives and their plane
+        int trk_cap = 0, ts = 0;
+        const unsigned char *hdr, *out;
+        size_t sb = 0;
+        adas::tracker_live_views(p->d.tracker, &hdr, &out, &sb, &ts, &trk_cap);
+        int rc = adas::overlay_reserve_trajectories(p->overlay, trk_cap);
         if (rc) return rc;
     }
     p->overlay_stages = stages;

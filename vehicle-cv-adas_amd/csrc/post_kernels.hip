@@ -530,6 +530,15 @@ void tracker_live_views(const ::adas_bytetrack* h, const unsigned char** hdr, co
     *n_streams = h->n_streams;
     *max_tracks = h->p.max_tracks;
 }
+void tracker_ring_views(const ::adas_bytetrack* h, const unsigned char** tracked_slots, const unsigned char** appended, size_t* slot_bytes,
+                        const unsigned char** rings) {
+    static_assert(ADAS_BT_TRAJ == ADAS_TRAJECTORY_LEN, "trajectory depth");
+    const BtStream S = bt_view(h->dev.base, h->p.max_tracks, h->p.max_dets);
+    *tracked_slots = (const unsigned char*)S.tracked;
+    *appended = (const unsigned char*)&S.slots[0].traj_n;
+    *slot_bytes = sizeof(BtTrack);
+    *rings = (const unsigned char*)S.traj;
+}
 void decode_lane_views(const ::adas_ufld_decode* h, const int** cnt, const int** det, const int** pts) {
     *cnt = h->dev.lane_cnt;
     *det = h->dev.lane_det;

@@ -13,8 +13,9 @@ lane decode (post_kernels.hip) all run in HBM, and only the survivors (<= 2 KB) 
 Of the reference's drawing, the lane detectors' `DrawDetectedOnFrame` / `DrawAreaOnFrame` run on the device (csrc/overlay_kernels.hip:
 filled discs, the ego-lane polygon and the alpha blends, restated from OpenCV 4.5 with parity unpinned), and so do the BOXES of
 `YoloDetector.DrawDetectedOnFrame` / `EfficientdetDetector.DrawDetectedOnFrame` (cornerRect: outline and corner arms in the class colour)
-and of `BYTETracker.DrawTrackedOnFrame` (plot_bbox's rectangle and tint).  Text, the label's background rectangle, key points,
-trajectories, arrows, slanted thick lines, the UI panels and everything else cv2 stay out of scope.
+and of `BYTETracker.DrawTrackedOnFrame` (plot_bbox's rectangle and tint) and, with `BYTETracker(draw_trajectories=True)`, its trajectories
+and direction marks (plot_trajectories' circles, plot_directions' lock-on rectangle or shadowed arrow).  Text, the label's background
+rectangle, key points, DrawTransformFrontalViewArea's lines, the UI panels and everything else cv2 stay out of scope.
 
 What stays on the host is what the reference keeps there and SURVEY 8a marks "host": RectInfo construction and
 LaneDetectBase.__update_lanes_status/__update_lanes_area (core.py:102-158: ego-lane polyfit, <1 ms).
@@ -763,10 +764,13 @@ class BYTETracker:
     Each instance owns its id counter (the reference's BaseTrack._count is process-global, base_track.py:12)."""
 
     def __init__(self, track_thresh: float = 0.5, track_buffer: int = 30, match_thresh: float = 0.8, frame_rate: int = 30,
-                 min_box_area: int = 10, max_tracks: int = 256, max_dets: int = 512, names=None, **kwargs: Any):
+                 min_box_area: int = 10, max_tracks: int = 256, max_dets: int = 512, names=None, draw_trajectories: bool = False, **kwargs: Any):
         """names: the reference's ObjectTrackBase argument (ObjectTracker/core.py:83-93) -- a dict label -> colour (the class colours
-        themselves) or a list of labels (one random colour each); None: no colours, every box is drawn black."""
+        themselves) or a list of labels (one random colour each); None: no colours, every box is drawn black.
+        draw_trajectories (also a plain attribute): False -- DrawTrackedOnFrame draws the boxes only, whatever show_traject says; True --
+        show_box and show_traject select the boxes and the trajectories with their direction marks, as in the reference."""
         self.track_thresh, self.match_thresh, self.min_box_area = track_thresh, match_thresh, min_box_area
+        self.draw_trajectories = bool(draw_trajectories)
         # what ObjectTrackBase keeps (ObjectTracker/core.py:83-93): a dict is the colour table itself and every label names itself; a list
         # of labels gets one random colour per entry, channels in 0 .. 254
         if names is None:
@@ -859,10 +863,20 @@ class BYTETracker:
                 if b[0] >= 0 + padw and b[1] >= 0 + padh and b[2] <= fw - padw and b[3] <= fh - padh]
 
     def DrawTrackedOnFrame(self, frame, show_box: bool = True, show_traject: bool = True) -> None:
-        """byteTracker.py:202-215 on the device, the BOX part only: for every activated track of tracked_stracks, in list order, with
-        tlwh[2] * tlwh[3] > min_box_area, plot_bbox's thickness-2 rectangle and its 0.6 / 0.4 / + 1 tint in class_colors[class_id] (a class
-        without a colour is drawn black).  NOT drawn: plot_bbox's text, plot_trajectories' circles and plot_directions' arrows --
-        show_traject is accepted and ignored.  `frame` is an HxWx3 uint8 ndarray (drawn and copied back into frame[:]) or a StagedFrame."""
+        """byteTracker.py:202-215 on the device: for every activated track of tracked_stracks, in list order, with tlwh[2] * tlwh[3] >
+        min_box_area, plot_bbox's thickness-2 rectangle and its 0.6 / 0.4 / + 1 tint in class_colors[class_id] (a class without a colour is
+        drawn black).  With draw_trajectories False (the default) that is all: show_traject is accepted and ignored.  With draw_trajectories
+        True show_traject adds plot_trajectories' circles and plot_directions' lock-on rectangle or shadowed arrow behind each track's box
+        -- DrawTrackedOnFrame(frame, False) is then the demo's call (demo.py:304) -- drawn from the device tracker's live state: rows, boxes
+        and trajectory rings are read where they lie in HBM, nothing is fetched.  NOT drawn: the text.  `frame` is an HxWx3 uint8 ndarray
+        (drawn and copied back into frame[:]) or a StagedFrame."""
+        if self.draw_trajectories:
+            if (show_box or show_traject) and self._tracked:
+                if self._painter is None:
+                    self._painter = OverlayPainter()
+                self._painter.live_tracks(frame, self._dev, self._live_colors(), min_box_area=self.min_box_area, boxes=bool(show_box),
+                                          trajectories=bool(show_traject))
+            return
         if not show_box:
             return
         online = [t for t in self._tracked if t["is_activated"]]
@@ -877,6 +891,24 @@ class BYTETracker:
         if self._painter is None:
             self._painter = OverlayPainter()
         self._painter.tracks(frame, [t["tlwh"] for t in online], list(range(len(online))), colors, min_box_area=self.min_box_area)
+
+    def _live_colors(self):
+        """class_colors as the table the device indexes with ITS class ids: an int id is itself, label k is 1_000_000 + k (_cls_index).
+        With labels the table is that long (4 MB in HBM, rebuilt only when a label is added); ids without a colour are black."""
+        cc = self.class_colors
+        ints = {k: v for k, v in (cc.items() if isinstance(cc, dict) else enumerate(cc)) if isinstance(k, (int, np.integer)) and 0 <= k < 1_000_000}
+        labelled = [cc.get(lab) if isinstance(cc, dict) else None for lab in self._labels]
+        key = (tuple(sorted((int(k), tuple(int(c) for c in v)) for k, v in ints.items())), tuple(None if v is None else tuple(int(c) for c in v) for v in labelled))
+        if getattr(self, "_live_key", None) != key:
+            n = (1_000_000 + len(labelled)) if any(v is not None for v in labelled) else (max(ints) + 1 if ints else 0)
+            tab = np.zeros((n, 3), np.uint8)
+            for k, v in ints.items():
+                tab[int(k)] = [int(c) for c in v]
+            for i, v in enumerate(labelled):
+                if v is not None:
+                    tab[1_000_000 + i] = [int(c) for c in v]
+            self._live_key, self._live_tab = key, tab
+        return self._live_tab
 
     @property
     def tracked_stracks(self):

@@ -37,13 +37,15 @@ class AdasPipeline:
         re-anchoring requests (request_transform raises) and micro_batch must be 1.
         overlay: None, or dict(stages=("lanes", "area", "distance", "bird") or a subset / mask, plus LaneOverlay's style keys): the lane
         overlay as the step's very last stage, drawn from step_frames' frames into a buffer of its own (overlay_image(frame) after sync()):
-        lane-point discs and the ego-lane polygon alpha-blended, distance-point discs, and the discs on the bird-view image -- no text, thick
-        lines, arrows, trajectories or panels.  Needs lane_model= and geometry=; the distance stage needs analysis=, the bird stage
+        lane-point discs and the ego-lane polygon alpha-blended, distance-point discs, and the discs on the bird-view image -- no text or
+        panels.  Needs lane_model= and geometry=; the distance stage needs analysis=, the bird stage
         birdview=dict(image=True).  stages=None: every one of those four stages the pipeline has the handles for.  Only by name: "detections"
         (cornerRect boxes of the step's survivors; needs det_model=) and "tracks" (the tracked tracks' rectangles and tints after this step's
         update; needs track=True and micro_batch 1), drawn between the area and the distance discs in the class colours of
-        overlay["detection_colors"] / overlay["track_colors"] (BGR by class id; none: black).  Boxes only: no labels, key points,
-        trajectories or arrows."""
+        overlay["detection_colors"] / overlay["track_colors"] (BGR by class id; none: black).  Also only by name: "trajectories" -- what
+        the demo's DrawTrackedOnFrame(frame_show, False) draws per tracked track, behind its box: plot_trajectories' circles over its last 30
+        boxes and plot_directions' lock-on rectangle or shadowed arrow, in overlay["track_colors"]; read from the tracker's live state on the
+        device (needs det_model=, track=True and micro_batch 1 like "tracks").  No labels, key points or other text."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
@@ -66,6 +68,12 @@ class AdasPipeline:
                 raise ValueError("the overlay's tracks stage needs det_model= and track=True (the tracked tracks it draws)")
             if ov_mask is not None and ov_mask & L.OVERLAY_TRACKS and self.B > 1:
                 raise ValueError("the overlay's tracks stage needs micro_batch=1: the tracker's live table holds only the last frame of a step")
+            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and not det_model:
+                raise ValueError("the overlay's trajectories stage needs det_model= (the detector that feeds the tracker it draws from)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and not track:
+                raise ValueError("the overlay's trajectories stage needs det_model= and track=True (the tracked tracks it draws)")
+            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and self.B > 1:
+                raise ValueError("the overlay's trajectories stage needs micro_batch=1: the tracker's live table holds only the last frame of a step")
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:

@@ -543,8 +543,10 @@ class LaneOverlay:
     image (PerspectiveTransformation.DrawDetectedOnBirdView).  The object layer ("detections", "tracks"; off unless asked for) adds the
     boxes between the area blend and the distance discs: ObjectDetectBase.cornerRect per survivor (outline and eight corner arms in the
     class colour) and the box part of BYTETracker.DrawTrackedOnFrame (a thickness-2 rectangle, then the region tinted 0.6 / 0.4 / + 1) per
-    activated tracked track over min_box_area.  Not drawn: text, the label's background rectangle, key points, plot_trajectories' thick
-    circles, plot_directions' arrows, DrawTransformFrontalViewArea's slanted thick lines and the UI panels.
+    activated tracked track over min_box_area.  The trajectories stage ("trajectories", bit 128; off unless asked for) adds what the demo's
+    DrawTrackedOnFrame(frame_show, False) draws per such track, behind its box: plot_trajectories' growing circles over the track's last 30
+    boxes and plot_directions' lock-on rectangle or shadowed arrow (csrc/overlay_track_core.h).  Not drawn: text, the label's background
+    rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines and the UI panels.
     The pixel rules are csrc/overlay_core.h (modelled on OpenCV 4.5; parity with a real cv2 build is unpinned, lines are not clipped
     before they are walked)."""
     STAGES = L.OVERLAY_STAGES
@@ -600,7 +602,7 @@ class LaneOverlay:
 
     @classmethod
     def stage_mask(cls, stages):
-        """An int, or names out of "lanes", "area", "distance", "bird", "detections", "tracks"."""
+        """An int, or names out of "lanes", "area", "distance", "bird", "detections", "tracks", "trajectories"."""
         if isinstance(stages, int):
             return stages
         names = [stages] if isinstance(stages, str) else list(stages)
@@ -621,11 +623,17 @@ class LaneOverlay:
             post=None, tracker=None):
         """Frames [0, n_streams * n_frames) of the device pointer src_ptr -> dst_ptr (None: the handle's own buffer; src_ptr: in place), drawn
         from the handles' device arrays (UfldDecode / Ufld1Decode, LaneGeometry, Analysis; post=: a YoloPost, its survivors' boxes; tracker=: a
-        DeviceTracker, its live tracked tracks -- n_frames must then be 1).  stages=None: every stage whose handle is given."""
+        DeviceTracker, its live tracked tracks -- n_frames must then be 1).  stages=None: every stage whose handle is given, except
+        "trajectories", which is drawn only when named (it reads tracker='s live state: the rows and their trajectory rings)."""
         if stages is None:
             stages = ((L.OVERLAY_LANES if decode else 0) | (L.OVERLAY_AREA if geometry else 0) | (L.OVERLAY_DISTANCE if analysis else 0) |
                       (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if post else 0) | (L.OVERLAY_TRACKS if tracker else 0))
         mask = self.stage_mask(stages)
+        if mask & L.OVERLAY_TRAJECTORIES:
+            L.check(L.lib().adas_overlay_run_trajectories(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
+                                                          analysis.h if analysis else None, post.h if post else None, tracker.h if tracker else None,
+                                                          bird_ptr, mask, int(n_streams), int(n_frames), stream))
+            return
         if post is None and tracker is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
             L.check(L.lib().adas_overlay_run(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
                                              analysis.h if analysis else None, bird_ptr, mask, int(n_streams), int(n_frames), stream))
@@ -637,15 +645,29 @@ class LaneOverlay:
     def run_arrays(self, src_ptr, n_frames=1, lane_points=None, lane_counts=None, poly=None, poly_cap=0, poly_counts=None, area_status=None,
                    offset_type=None, area_bgr=None, dist_points=None, dist_cap=0, dist_counts=None, bird_points=None, bird_counts=None,
                    bird_ptr=None, stages=None, dst_ptr=None, stream=None, det_xyxy=None, det_cap=0, det_cls=None, det_counts=None, trk_tlwh=None,
-                   trk_cap=0, trk_cls=None, trk_counts=None):
+                   trk_cap=0, trk_cls=None, trk_counts=None, trajectories=None):
         """The same kernels on raw device pointers (adas_overlay_run_arrays; with boxes adas_overlay_run_arrays_objects: det_xyxy
         [frames][det_cap][4] int32 + det_cls + det_counts, trk_tlwh [frames][trk_cap][4] fp64 + trk_cls + trk_counts, rows of activated
-        tracked tracks).  stages=None: every stage whose arrays are given."""
+        tracked tracks).  trajectories=(traj_tlbr, traj_len): device pointers to the rows' trajectories [frames][trk_cap][30][4] fp64, oldest
+        first, and their lengths [frames][trk_cap] -- the "trajectories" stage (adas_overlay_run_arrays_trajectories), which also needs the
+        four trk_ arrays.  stages=None: every stage whose arrays are given ("tracks" not by the trk_ arrays alone when trajectories= is)."""
         if stages is None:
             stages = ((L.OVERLAY_LANES if lane_points else 0) | (L.OVERLAY_AREA if poly else 0) | (L.OVERLAY_DISTANCE if dist_points else 0) |
                       (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if det_xyxy else 0) |
-                      (L.OVERLAY_TRACKS if trk_tlwh else 0))
+                      (L.OVERLAY_TRACKS if (trk_tlwh and trajectories is None) else 0) | (L.OVERLAY_TRAJECTORIES if trajectories is not None else 0))
         mask = self.stage_mask(stages)
+        if trajectories is not None or mask & L.OVERLAY_TRAJECTORIES:
+            a = L.OverlayArrays()
+            tr = trajectories if trajectories is not None else (None, None)
+            for k, v in dict(d_src_bgr=src_ptr, d_dst_bgr=dst_ptr, d_lane_points=lane_points, d_lane_counts=lane_counts, d_poly=poly,
+                             d_poly_counts=poly_counts, d_area_status=area_status, d_offset_type=offset_type, d_area_bgr=area_bgr,
+                             d_dist_points=dist_points, d_dist_counts=dist_counts, d_bird_points=bird_points, d_bird_counts=bird_counts,
+                             d_bird_bgr=bird_ptr, d_det_xyxy=det_xyxy, d_det_cls=det_cls, d_det_counts=det_counts, d_trk_tlwh=trk_tlwh,
+                             d_trk_cls=trk_cls, d_trk_counts=trk_counts, d_traj_tlbr=tr[0], d_traj_len=tr[1], stream=stream).items():
+                setattr(a, k, v)
+            a.poly_cap, a.dist_cap, a.det_cap, a.trk_cap, a.stages, a.n_frames = int(poly_cap), int(dist_cap), int(det_cap), int(trk_cap), mask, int(n_frames)
+            L.check(L.lib().adas_overlay_run_arrays_trajectories(self.h, C.byref(a)))
+            return
         if det_xyxy is None and trk_tlwh is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
             L.check(L.lib().adas_overlay_run_arrays(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
                                                     offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts, bird_ptr,
@@ -671,6 +693,16 @@ class LaneOverlay:
         f = C.c_int32()
         L.check(L.lib().adas_overlay_fetch_flags(self.h, int(frame), C.byref(f)))
         return int(f.value)
+
+    def track_marks(self, frame=0):
+        """The primitives the device built for the frame in the last run with the "trajectories" stage, in drawing order: a structured
+        array (L.TRACK_MARK_DTYPE: kind L.TRACK_MARK_CIRCLE / _RECT / _ARROW, track row, x1, y1, x2, y2, radius, thickness, tip, color,
+        skipped).  Synchronises."""
+        n = C.c_int32()
+        L.check(L.lib().adas_overlay_fetch_track_marks(self.h, int(frame), None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), L.TRACK_MARK_DTYPE)
+        L.check(L.lib().adas_overlay_fetch_track_marks(self.h, int(frame), L.ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
 
     def close(self):
         if getattr(self, "h", None):
@@ -803,6 +835,61 @@ class OverlayPainter:
         """DrawTrackedOnFrame's boxes: plot_bbox's rectangle and tint on every tlwh (rows of activated tracked tracks, in list order) whose
         area passes the gate, in colors[class].  No text, trajectories or arrows."""
         self._boxes(image, L.OVERLAY_TRACKS, colors, tlwhs, classes, np.float64, min_box_area=float(min_box_area), track_thickness=int(thickness))
+
+    def _track_style(self, table, min_box_area, thickness):
+        # both setters wait for the device and make a captured step of this process re-capture: only when something changed
+        if self._set.get(L.OVERLAY_TRACKS) != table:
+            self.ov.set_class_colors(L.OVERLAY_TRACKS, table)
+            self._set[L.OVERLAY_TRACKS] = table
+        new = {k: v for k, v in dict(min_box_area=float(min_box_area), track_thickness=int(thickness)).items() if getattr(self.ov.os, k) != v}
+        if new:
+            self.ov.set_object_style(**new)
+
+    def trajectories(self, image, tlwhs, trajectories, classes, colors=(), min_box_area=10, boxes=False, thickness=2):
+        """DrawTrackedOnFrame(frame, show_box=boxes, show_traject=True) without its text, from host arrays: per tlwh (rows of activated
+        tracked tracks, in list order) whose area passes the gate, plot_bbox's rectangle and tint when boxes=True, then plot_trajectories'
+        circles over trajectories[row] (tlbr boxes, oldest first; the last 30 count) and plot_directions' lock-on rectangle or shadowed
+        arrow, in colors[class] (outside the table: black)."""
+        ptr, host = self._target(image)
+        b = np.ascontiguousarray(np.asarray(tlwhs, np.float64).reshape(-1, 4))
+        if len(b) == 0:
+            return
+        c = np.ascontiguousarray(np.asarray(classes, np.int64).reshape(-1).astype(np.int32))
+        if len(c) != len(b) or len(trajectories) != len(b):
+            raise Exception("%d boxes, %d classes, %d trajectories" % (len(b), len(c), len(trajectories)))
+        tr, ln = np.zeros((len(b), L.TRAJECTORY_LEN, 4), np.float64), np.zeros(len(b), np.int32)
+        for k, t in enumerate(trajectories):
+            t = np.asarray(t, np.float64).reshape(-1, 4)[-L.TRAJECTORY_LEN:]
+            tr[k, :len(t)], ln[k] = t, len(t)
+        bufs = [L.DeviceBuffer.from_array(a) for a in (b, c, np.array([len(b)], np.int32), tr, ln)]
+        try:
+            self._track_style(tuple(tuple(int(v) for v in col) for col in colors), min_box_area, thickness)
+            self.ov.run_arrays(ptr, 1, trk_tlwh=bufs[0].ptr, trk_cap=len(b), trk_cls=bufs[1].ptr, trk_counts=bufs[2].ptr,
+                               trajectories=(bufs[3].ptr, bufs[4].ptr), stages=L.OVERLAY_TRAJECTORIES | (L.OVERLAY_TRACKS if boxes else 0), dst_ptr=ptr)
+            self._finish(ptr, host)
+        finally:
+            for x in bufs:
+                x.free()
+
+    def live_tracks(self, image, tracker, colors=(), min_box_area=10, boxes=True, trajectories=True, thickness=2):
+        """The same from a DeviceTracker's live state (stream 0), with no host copy of it: the rows, their class, tlwh and is_activated and
+        each row's trajectory ring are read where they lie in HBM (adas_overlay_run_trajectories).  colors: BGR by the tracker's class id,
+        a sequence (a tuple is compared with the last one given, an ndarray [n][3] u8 goes to the device as it is)."""
+        stages = (L.OVERLAY_TRACKS if boxes else 0) | (L.OVERLAY_TRAJECTORIES if trajectories else 0)
+        if not stages:
+            return
+        ptr, host = self._target(image)
+        if isinstance(colors, np.ndarray):                  # a large table (class ids that are not small): straight to the setter
+            key = ("array", colors.shape[0], hash(colors.tobytes()))
+            if self._set.get(L.OVERLAY_TRACKS) != key:
+                tab = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+                L.check(L.lib().adas_overlay_set_class_colors(self.ov.h, L.OVERLAY_TRACKS, L.ptr(tab) if len(tab) else None, len(tab)))
+                self._set[L.OVERLAY_TRACKS] = key
+            self._track_style(key, min_box_area, thickness)
+        else:
+            self._track_style(tuple(tuple(int(v) for v in col) for col in colors), min_box_area, thickness)
+        self.ov.run(ptr, tracker=tracker, stages=stages, dst_ptr=ptr)
+        self._finish(ptr, host)
 
     def close(self):
         if self.ov is not None:
