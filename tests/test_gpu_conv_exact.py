@@ -12,9 +12,10 @@ with an odd period: every copy must equal its original bit for bit, and the refe
 (adas_engine_layer_kernel) is asserted: a case that lands on another kernel fails.  Slice cases read channels [8, 8 + cin) of a wider
 buffer and write [16, 16 + cout) of a concat buffer between guard channels set to 7.0 in front of the conv (test_gpu_ops_exact.py).
 
-Out of scope: the fused launches (conv_c2f16*, conv_pair_kernel, stem + second conv, +pool, +shortcut, the fused Detect kernels) --
-their intermediate never reaches memory, so it cannot be fetched.  conv_ml_kernel and conv_halo_group_kernel are asserted bit-identical
-to the per-layer launches by tests/test_gpu_ml.py and inherit this coverage.
+The fused launches (conv_c2f16*, conv_pair_kernel, stem + second conv, +pool, +shortcut), whose intermediate never reaches memory, are
+checked per element by tests/test_gpu_fused_exact.py: the intermediate is computed in float64 from the fetched input and rounded as the
+kernel stores it (tests/fused_ref.py); that file also says where the fused Detect kernels are tested.  conv_ml_kernel and
+conv_halo_group_kernel are asserted bit-identical to the per-layer launches by tests/test_gpu_ml.py and inherit this coverage.
 
 Where the activation is a template parameter of the kernel ({A}) the cases of a label run SiLU, ReLU, leaky and none between them; fc_kernel,
 conv_pw*, conv_pwg, conv_igemm and the generic fp16x3 kernels take it at run time.
