@@ -31,7 +31,7 @@ label -> cases
   conv_stem_kernel<7,4,RELU>+pool             pool-*: the nine STEM_POOL shapes of tests/test_gpu_x3_stems.py, interval bound                              fp16, bf16
   conv_h8_kernel<RELU>+shortcut               h8ds-m (16 x 32, Cp 64 -> C 128, batch 128), h8ds-r (13 x 37 from 25 x 73, Cp 96 -> C 256, batch 61), h8ds-32 (Cp 32)    fp16, bf16
 
-Out of scope: the fused Detect kernels (tests against the oracle's Detect with their own derived box and probability bounds);
+Out of scope: the fused Detect kernels (tests/test_gpu_detect_exact.py: every anchor against float64, bound in tests/detect_ref.py);
 conv_ml / grouped launches (bit-identical to the per-layer launches by tests/test_gpu_ml.py); the folded upsample (bit-identical to the
 unfolded conv, which tests/test_gpu_conv_exact.py covers per element); the fp16x3 stem + pool (bit-identical to its per-element-tested
 two-launch form by tests/test_gpu_x3_stems.py)."""
