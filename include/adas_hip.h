@@ -714,9 +714,12 @@ typedef struct {
 #define ADAS_OVERLAY_AREA 2
 #define ADAS_OVERLAY_DISTANCE 4
 #define ADAS_OVERLAY_BIRD 8
-#define ADAS_OVERLAY_DETECTIONS 16 /* adas_overlay_run_objects / _run_arrays_objects / adas_pipeline_set_overlay_stages only */
+/* Every run entry point below is a stage mask over one path: adas_overlay_run and _run_arrays accept bits 1..8 (mask 15), _run_objects and
+ * _run_arrays_objects also 16 and 32 (mask 63), _run_trajectories, _run_arrays_trajectories and adas_pipeline_set_overlay_stages also 128.
+ * A bit outside an entry's mask is ADAS_ERR_INVALID ("<entry>: unknown stage bits"); inside it the entries draw the same bytes. */
+#define ADAS_OVERLAY_DETECTIONS 16 /* the masks 63 and 63 | 128 */
 #define ADAS_OVERLAY_TRACKS 32
-#define ADAS_OVERLAY_TRAJECTORIES 128 /* adas_overlay_run_trajectories / _run_arrays_trajectories / adas_pipeline_set_overlay_stages only; 64 is no stage */
+#define ADAS_OVERLAY_TRAJECTORIES 128 /* the mask 63 | 128 only; 64 is no stage */
 #define ADAS_OVERLAY_POLY_RANGE 1 /* frame flags: a polygon vertex outside +-32767, the frame's fill was skipped */
 #define ADAS_OVERLAY_TRACK_RANGE 2 /* a segment of a track's indicator had an endpoint outside +-32767 and was skipped */
 /* The reference's radii, alphas and colours; the four sizes are 0. */

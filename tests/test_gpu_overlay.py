@@ -7,6 +7,8 @@ import pytest
 
 from conftest import load_pkg
 import overlay_ref as ref
+import overlay_scene as OS
+from overlay_scene import noise
 
 pytestmark = pytest.mark.gpu
 load_pkg()
@@ -18,60 +20,17 @@ M = importlib.import_module("adas_amd.models")
 A = importlib.import_module("adas_amd.analysis")
 D = importlib.import_module("adas_amd.detectors")
 
-GUARD = 64          # bytes of 0xA5 on either side of a caller's destination: nothing may be written outside the frames
 MAXP = L.UFLD_MAX_POINTS
 INVALID = -1        # ADAS_ERR_INVALID
 POLY = [(10, 5), (8, 12), (8, 12), (3, 20), (2, 30), (40, 30), (35, 21), (30, 12), (28, 5)]
 BOWTIE = [(5, 2), (30, 20), (30, 2), (5, 20)]
 
 
-def noise(n, h, w, seed):
-    return np.random.default_rng(seed).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
-
-
-class Scene:
-    """Per-frame geometry of a batch, as run_arrays takes it."""
+class Scene(OS.Scene):
+    """Per-frame geometry of a batch with its area flags, offset types and colours, and the bird view's lanes."""
 
     def __init__(self, n, dist_cap=8, poly_cap=48):
-        self.n, self.dist_cap, self.poly_cap = n, dist_cap, poly_cap
-        self.lanes = [[[] for _ in range(4)] for _ in range(n)]
-        self.poly = [[] for _ in range(n)]
-        self.area = [1] * n
-        self.offset = [ref.OFFSET_UNKNOWN] * n
-        self.colour = [ref.AREA_COLOR] * n
-        self.dist = [[] for _ in range(n)]
-        self.bird = [[[] for _ in range(4)] for _ in range(n)]
-
-    @staticmethod
-    def _lane_table(frames):
-        pts, cnt = np.zeros((len(frames), 4, MAXP, 2), np.int32), np.zeros((len(frames), 4), np.int32)
-        for f, lanes in enumerate(frames):
-            for l in range(4):
-                a = np.asarray(lanes[l], np.int64).reshape(-1, 2)
-                pts[f, l, :len(a)], cnt[f, l] = a, len(a)
-        return pts, cnt
-
-    def upload(self):
-        lp, lc = self._lane_table(self.lanes)
-        bp, bc = self._lane_table(self.bird)
-        poly, pc = np.zeros((self.n, self.poly_cap, 2), np.int32), np.zeros(self.n, np.int32)
-        dist, dc = np.zeros((self.n, self.dist_cap, 2), np.int32), np.zeros(self.n, np.int32)
-        for f in range(self.n):
-            a = np.asarray(self.poly[f], np.int64).reshape(-1, 2)
-            poly[f, :len(a)], pc[f] = a, len(a)
-            a = np.asarray(self.dist[f], np.int64).reshape(-1, 2)
-            dist[f, :len(a)], dc[f] = a, len(a)
-        arrays = dict(lane_points=lp, lane_counts=lc, poly=poly, poly_counts=pc, area_status=np.array(self.area, np.int32),
-                      offset_type=np.array(self.offset, np.int32), area_bgr=np.array(self.colour, np.uint8), dist_points=dist, dist_counts=dc,
-                      bird_points=bp, bird_counts=bc)
-        self.bufs = {k: L.DeviceBuffer.from_array(v) for k, v in arrays.items()}
-        kw = {k: b.ptr for k, b in self.bufs.items()}
-        kw.update(poly_cap=self.poly_cap, dist_cap=self.dist_cap)
-        return kw
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
+        super().__init__(n, ("style", "bird"), dist_cap=dist_cap, poly_cap=poly_cap)
 
     def want(self, src, stages=7):
         out, flags = [], []
@@ -85,40 +44,10 @@ class Scene:
         return np.stack([ref.draw_lanes(img[f], self.bird[f], self.offset[f], radius=10, direct=True) for f in range(self.n)])
 
 
-def run(scene, src, stages=7, offset=16, in_place=False, own=False, bird=None, style=None):
-    """One run_arrays launch over the batch -> (frames, flags[, bird image]); a caller's destination sits at `offset` inside a canvas of 0xA5."""
-    n, h, w = src.shape[:3]
-    ov = PP.LaneOverlay((h, w), bird.shape[1:3] if bird is not None else None, n, **(style or {}))
-    kw = scene.upload()
-    nbytes = src.nbytes
-    canvas = np.full(nbytes + 2 * GUARD, 0xA5, np.uint8)
-    if in_place:
-        canvas[offset:offset + nbytes] = src.reshape(-1)
-    dbuf = L.DeviceBuffer.from_array(canvas)
-    sbuf = L.DeviceBuffer.from_array(src)
-    bbuf = L.DeviceBuffer.from_array(bird) if bird is not None else None
-    try:
-        dst = None if own else dbuf.ptr + offset
-        ov.run_arrays(dst if in_place else sbuf.ptr, n, stages=stages, dst_ptr=dst, bird_ptr=bbuf.ptr if bbuf else None, **kw)
-        L.check(L.lib().adas_synchronize())
-        if own:
-            got = np.stack([ov.fetch(f) for f in range(n)])
-            raw = np.empty_like(got)
-            L.check(L.lib().adas_memcpy_d2h(L.ptr(raw), ov.device_view(), raw.nbytes))
-            assert np.array_equal(raw, got)
-        else:
-            back = dbuf.download(canvas.shape, np.uint8)
-            assert (back[:offset] == 0xA5).all() and (back[offset + nbytes:] == 0xA5).all(), "write outside the destination"
-            got = back[offset:offset + nbytes].reshape(src.shape)
-        assert np.array_equal(sbuf.download(src.shape, np.uint8), src), "the caller's frames were written"
-        flags = [ov.flags(f) for f in range(n)] if stages & 7 else [0] * n
-        if bird is not None:
-            return got, flags, bbuf.download(bird.shape, np.uint8)
-        return got, flags
-    finally:
-        ov.close(); scene.free(); dbuf.free(); sbuf.free()
-        if bbuf:
-            bbuf.free()
+def run(scene, src, stages=7, bird=None, style=None, **kw):
+    """OS.run -> (frames, flags[, bird image])"""
+    r = OS.run(scene, src, stages, bird=bird, **kw, **(style or {}))
+    return (r.frames, r.flags) if bird is None else (r.frames, r.flags, r.bird)
 
 
 def three_frames(h=45, w=70):

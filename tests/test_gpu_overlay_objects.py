@@ -1,6 +1,7 @@
 """GPU: the overlay's object layer (boxes of the detector and of the tracker: csrc/overlay_kernels.hip, rules D6-D9 of overlay_core.h)
 through the C ABI, postproc.LaneOverlay, the fused step and the drop-in Draw* methods against the NumPy restatement
 (tests/overlay_objects_ref.py), every byte."""
+import ctypes as C
 import importlib
 
 import numpy as np
@@ -9,6 +10,8 @@ import pytest
 from conftest import load_pkg
 import overlay_ref as ref
 import overlay_objects_ref as oref
+import overlay_scene as OS
+from overlay_scene import noise
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +24,6 @@ M = importlib.import_module("adas_amd.models")
 A = importlib.import_module("adas_amd.analysis")
 D = importlib.import_module("adas_amd.detectors")
 
-GUARD = 64          # bytes of 0xA5 on either side of a caller's destination: nothing may be written outside the frames
-MAXP = L.UFLD_MAX_POINTS
 INVALID = -1        # ADAS_ERR_INVALID
 H, W = 45, 70       # three coverage words per row
 DET, TRK = oref.DETECTIONS, oref.TRACKS
@@ -31,50 +32,11 @@ DET_TABLE = [(255, 0, 0), (0, 255, 0), (0, 0, 255), (200, 100, 50), (17, 34, 51)
 TRK_TABLE = [(10, 200, 250), (250, 10, 120), (90, 90, 10)]
 
 
-def noise(n, h, w, seed):
-    return np.random.default_rng(seed).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
-
-
-class Scene:
-    """Per-frame geometry and boxes of a batch, as run_arrays takes them."""
+class Scene(OS.Scene):
+    """Per-frame geometry and boxes of a batch."""
 
     def __init__(self, n, det_cap=12, trk_cap=8, dist_cap=8, poly_cap=16):
-        self.n, self.det_cap, self.trk_cap, self.dist_cap, self.poly_cap = n, det_cap, trk_cap, dist_cap, poly_cap
-        self.lanes = [[[] for _ in range(4)] for _ in range(n)]
-        self.poly = [[] for _ in range(n)]
-        self.dist = [[] for _ in range(n)]
-        self.dets = [[] for _ in range(n)]          # (xmin, ymin, xmax, ymax, class)
-        self.trks = [[] for _ in range(n)]          # (t, l, w, h, class)
-
-    def upload(self):
-        n = self.n
-        lp, lc = np.zeros((n, 4, MAXP, 2), np.int32), np.zeros((n, 4), np.int32)
-        poly, pc = np.zeros((n, self.poly_cap, 2), np.int32), np.zeros(n, np.int32)
-        dist, dc = np.zeros((n, self.dist_cap, 2), np.int32), np.zeros(n, np.int32)
-        db, dcl, dn = np.full((n, self.det_cap, 4), 7, np.int32), np.zeros((n, self.det_cap), np.int32), np.zeros(n, np.int32)     # rows past the
-        tb, tcl, tn = np.full((n, self.trk_cap, 4), 9.0, np.float64), np.zeros((n, self.trk_cap), np.int32), np.zeros(n, np.int32)  # count: boxes
-        for f in range(n):
-            for l in range(4):
-                a = np.asarray(self.lanes[f][l], np.int64).reshape(-1, 2)
-                lp[f, l, :len(a)], lc[f, l] = a, len(a)
-            a = np.asarray(self.poly[f], np.int64).reshape(-1, 2)
-            poly[f, :len(a)], pc[f] = a, len(a)
-            a = np.asarray(self.dist[f], np.int64).reshape(-1, 2)
-            dist[f, :len(a)], dc[f] = a, len(a)
-            a = np.asarray(self.dets[f], np.int64).reshape(-1, 5)
-            db[f, :len(a)], dcl[f, :len(a)], dn[f] = a[:, :4], a[:, 4], len(a)
-            a = np.asarray(self.trks[f], np.float64).reshape(-1, 5)
-            tb[f, :len(a)], tcl[f, :len(a)], tn[f] = a[:, :4], a[:, 4].astype(np.int32), len(a)
-        arrays = dict(lane_points=lp, lane_counts=lc, poly=poly, poly_counts=pc, area_status=np.ones(n, np.int32), dist_points=dist, dist_counts=dc,
-                      det_xyxy=db, det_cls=dcl, det_counts=dn, trk_tlwh=tb, trk_cls=tcl, trk_counts=tn)
-        self.bufs = {k: L.DeviceBuffer.from_array(v) for k, v in arrays.items()}
-        kw = {k: b.ptr for k, b in self.bufs.items()}
-        kw.update(poly_cap=self.poly_cap, dist_cap=self.dist_cap, det_cap=self.det_cap, trk_cap=self.trk_cap)
-        return kw
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
+        super().__init__(n, ("boxes",), det_cap, trk_cap, dist_cap, poly_cap)
 
     def want(self, src, stages, det_table=DET_TABLE, trk_table=TRK_TABLE, **kw):
         out = []
@@ -88,43 +50,12 @@ class Scene:
 
 
 def make_overlay(n, h=H, w=W, det_table=DET_TABLE, trk_table=TRK_TABLE, **style):
-    ov = PP.LaneOverlay((h, w), None, n, **style)
-    if det_table is not None:
-        ov.set_class_colors("detections", det_table)
-    if trk_table is not None:
-        ov.set_class_colors("tracks", trk_table)
-    return ov
+    return OS.make_overlay(n, h, w, None, det_table, trk_table, **style)
 
 
-def run(scene, src, stages, offset=16, in_place=False, own=False, ov=None, **okw):
-    """One run_arrays launch over the batch -> frames; a caller's destination sits at `offset` inside a canvas of 0xA5."""
-    n = src.shape[0]
-    mine = ov is None
-    if mine:
-        ov = make_overlay(n, src.shape[1], src.shape[2], **okw)
-    kw = scene.upload()
-    nbytes = src.nbytes
-    canvas = np.full(nbytes + 2 * GUARD, 0xA5, np.uint8)
-    if in_place:
-        canvas[offset:offset + nbytes] = src.reshape(-1)
-    dbuf = L.DeviceBuffer.from_array(canvas)
-    sbuf = L.DeviceBuffer.from_array(src)
-    try:
-        dst = None if own else dbuf.ptr + offset
-        ov.run_arrays(dst if in_place else sbuf.ptr, n, stages=stages, dst_ptr=dst, **kw)
-        L.check(L.lib().adas_synchronize())
-        if own:
-            got = np.stack([ov.fetch(f) for f in range(n)])
-        else:
-            back = dbuf.download(canvas.shape, np.uint8)
-            assert (back[:offset] == 0xA5).all() and (back[offset + nbytes:] == 0xA5).all(), "write outside the destination"
-            got = back[offset:offset + nbytes].reshape(src.shape)
-        assert np.array_equal(sbuf.download(src.shape, np.uint8), src), "the caller's frames were written"
-        return got
-    finally:
-        if mine:
-            ov.close()
-        scene.free(); dbuf.free(); sbuf.free()
+def run(scene, src, stages, det_table=DET_TABLE, trk_table=TRK_TABLE, **kw):
+    """OS.run with this file's class colours -> frames"""
+    return OS.run(scene, src, stages, det_table=det_table, trk_table=trk_table, **kw).frames
 
 
 def three_frames():
@@ -271,6 +202,59 @@ def test_a_list_longer_than_the_staged_records():
     assert np.array_equal(run(s, src, DET | TRK), want)
 
 
+def test_all_six_entry_points_are_masks_over_one_path():
+    """LaneOverlay goes through the widest entry of each family, so the six are called here as the C ABI has them: the array entries draw
+    overlay_ref.compose at stages 7 and, where they take boxes, overlay_objects_ref.compose at 7 | 16 | 32; the handle entries draw a
+    decoder's uploaded lanes at stage 1; each refuses the first bit outside its own mask."""
+    lib, src, s = L.lib(), noise(3, H, W, 21), three_frames()
+    kw = s.upload()
+    sbuf = L.DeviceBuffer.from_array(src)
+    ov = make_overlay(3)
+    dec = PP.UfldDecode(100, 36, 50, 41, W, H, np.linspace(0.4, 1.0, 36), np.linspace(0.0, 1.0, 41), 1, 3)
+    for f in range(3):
+        dec.upload(s.lanes[f], [True] * 4, f)
+    lane = (kw["lane_points"], kw["lane_counts"], kw["poly"], kw["poly_cap"], kw["poly_counts"], kw["area_status"], None, None, kw["dist_points"],
+            kw["dist_cap"], kw["dist_counts"], None, None, None)
+    boxes = tuple(kw[k] for k in ("det_xyxy", "det_cap", "det_cls", "det_counts", "trk_tlwh", "trk_cap", "trk_cls", "trk_counts"))
+
+    def struct(dst, st):
+        return C.byref(L.OverlayArrays(d_src_bgr=sbuf.ptr, d_dst_bgr=dst, stages=st, n_frames=3, **{
+            k if k.endswith("_cap") else "d_" + k: v for k, v in kw.items()}))
+
+    arrays = {"adas_overlay_run_arrays": (15, lambda dst, st: lib.adas_overlay_run_arrays(ov.h, sbuf.ptr, dst, *lane, st, 3, None)),
+              "adas_overlay_run_arrays_objects": (63, lambda dst, st: lib.adas_overlay_run_arrays_objects(ov.h, sbuf.ptr, dst, *lane, *boxes, st, 3, None)),
+              "adas_overlay_run_arrays_trajectories": (63 | 128, lambda dst, st: lib.adas_overlay_run_arrays_trajectories(ov.h, struct(dst, st)))}
+    handles = {"adas_overlay_run": (15, lambda dst, st: lib.adas_overlay_run(ov.h, sbuf.ptr, dst, dec.h, None, None, None, st, 3, 1, None)),
+               "adas_overlay_run_objects": (63, lambda dst, st: lib.adas_overlay_run_objects(ov.h, sbuf.ptr, dst, dec.h, None, None, None, None, None, st, 3,
+                                                                                            1, None)),
+               "adas_overlay_run_trajectories": (63 | 128, lambda dst, st: lib.adas_overlay_run_trajectories(ov.h, sbuf.ptr, dst, dec.h, None, None, None, None,
+                                                                                                          None, st, 3, 1, None))}
+
+    def draw(call, st):                                                                  # into a fresh destination: a run that did nothing would show
+        dbuf = L.DeviceBuffer.from_array(np.full(src.nbytes, 0xA5, np.uint8))
+        L.check(call(dbuf.ptr, st))
+        L.check(lib.adas_synchronize())
+        got = dbuf.download((src.nbytes,), np.uint8).reshape(src.shape)
+        dbuf.free()
+        return got
+
+    plain = np.stack([ref.compose(src[f], s.lanes[f], s.poly[f], True, s.dist[f], ref.OFFSET_UNKNOWN, ref.AREA_COLOR, 7)[0] for f in range(3)])
+    lanes = np.stack([ref.draw_lanes(src[f], s.lanes[f]) for f in range(3)])
+    assert (plain != src).any() and (lanes != src).any() and (s.want(src, 7 | DET | TRK) != plain).any()
+    for name, (mask, call) in arrays.items():
+        assert np.array_equal(draw(call, 7), plain), name
+        if mask & DET:
+            assert np.array_equal(draw(call, 7 | DET | TRK), s.want(src, 7 | DET | TRK)), name
+    for name, (mask, call) in handles.items():
+        assert np.array_equal(draw(call, 1), lanes), name
+    for name, (mask, call) in list(arrays.items()) + list(handles.items()):
+        outside = next(b for b in (16, 32, 64, 128) if not mask & b)
+        with pytest.raises(RuntimeError, match=name + ": unknown stage bits") as ei:
+            L.check(call(None, 1 | outside))
+        assert ei.value.code == INVALID
+    ov.close(); dec.close(); s.free(); sbuf.free()
+
+
 # ------------------------------------------------------------------------------------------------ the handles
 def test_run_objects_from_a_real_post_and_a_real_tracker():
     """adas_overlay_run_objects reads a yolo_post handle's survivors (an injected head tensor, the SURVEY 8c recipe at a few candidates, on
@@ -307,6 +291,9 @@ def test_run_objects_from_a_real_post_and_a_real_tracker():
             assert np.array_equal(ov.fetch(s), want), (stages, s)
             n_boxes += len(r["xyxy_int"]) + len(act)
             assert len(r["xyxy_int"]) >= 5 and len(act) >= 3
+        via_run = [ov.fetch(s) for s in range(S)]                                         # LaneOverlay.run goes through the widest entry:
+        L.check(L.lib().adas_overlay_run_objects(ov.h, sbuf.ptr, None, None, None, None, yp.h, trk.h, None, stages, S, 1, None))
+        assert all(np.array_equal(ov.fetch(s), via_run[s]) for s in range(S)), stages     # the entry the docstring names draws the same bytes
     print("boxes drawn:", n_boxes)
     with pytest.raises(RuntimeError, match="yolo_post handle") as ei:                    # the refusals, by name
         ov.run(sbuf.ptr, tracker=trk, stages=DET | TRK, n_streams=S)

@@ -67,6 +67,22 @@ void tracker_ring_views(const ::adas_bytetrack* h, const unsigned char** tracked
 int overlay_reserve_objects(::adas_overlay* h, int det_cap, int trk_cap);
 // the same for the trajectories stage: the primitives of trk_cap tracks per frame and the stage's plane
 int overlay_reserve_trajectories(::adas_overlay* h, int trk_cap);
+// one overlay run from the handles' device arrays (overlay_kernels.hip): the arguments of adas_overlay_run_trajectories behind the handle, in
+// its order; a handle whose stages are off may be null.  who names the caller in messages, mask is the stage bits it accepts.  The public
+// adas_overlay_run* entry points and the pipeline's step all go through it
+struct overlay_handles {
+    const uint8_t* d_src_bgr;
+    uint8_t* d_dst_bgr;
+    const ::adas_ufld_decode* decode;
+    ::adas_lane_geometry* geometry;
+    ::adas_analysis* analysis;
+    ::adas_yolo_post* post;
+    ::adas_bytetrack* tracker;
+    uint8_t* d_bird_bgr;
+    int stages, n_streams, n_frames;
+    void* stream;
+};
+int overlay_run_handles(const char* who, int mask, ::adas_overlay* h, const overlay_handles& a);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

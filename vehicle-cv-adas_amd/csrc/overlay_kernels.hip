@@ -26,6 +26,12 @@
 // nothing is truncated; a record whose box misses the piece's marked pixels is skipped) and evaluates the thick segments in closed form
 // for each marked pixel.  A piece without those bits takes the path it took before; with both stages off the pass is
 // overlay_stream_kernel, which holds no object code (with the layer: overlay_stream_objects_kernel), and the record kernel is not launched.
+// The trajectories stage (ADAS_OVERLAY_TRAJECTORIES, rules D10-D12 of overlay_track_core.h) adds two launches of its own:
+// overlay_track_prims_kernel turns every drawn track into its circles and its rectangle or arrows, and overlay_tracks_draw_kernel, behind
+// the streaming pass, lists per band of rows the primitives that meet it, builds their coverage in LDS and writes the covered pixels.
+// Host side a run is described once: the six public run entry points are a name and a stage mask over adas::overlay_run_handles (sources
+// read from the other handles; the pipeline's step calls it too) or overlay_run_raw (an adas_overlay_arrays).  Both check their arguments and
+// fill one OvRun -- the tracker's rows through one OvRows view -- for overlay_launch, the only place that launches.
 // Memory-bound by design: the yardstick is a device-to-device copy of the same frames (tools/bench_overlay.py).
 #include "common.h"
 #include <stddef.h>
@@ -942,29 +948,78 @@ static int overlay_check_object_style(const adas_overlay_object_style* p, const 
     return ADAS_OK;
 }
 
-// the launches of one run; `s` holds the sources, bird_pts / bird_cnt (stride bird_cnt_stride) the bird view's, `obj` the boxes (stages 16 / 32)
-static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvSources s, const int* bird_pts, const int* bird_cnt, int bird_cnt_stride,
-                          uint8_t* d_bird, int stages, int frames, hipStream_t st, const OvObjects* obj = nullptr, const OvTracks* trk = nullptr) {
+// a tracker's rows as the tracks and the trajectories stage read them, per frame q: OvObjects::trk_* and the head of OvTracks hold a copy each
+struct OvRows {
+    const unsigned char *tlwh, *cls, *act, *cnt;   // act null: every row is activated
+    size_t frame_bytes, row_bytes, cls_frame_bytes, cls_row_bytes, cnt_bytes;
+    int cap;
+};
+
+// the live table of `tracker` (rows in the layout of adas_track); returns the streams it holds
+static int overlay_rows_of_tracker(const adas_bytetrack* tracker, OvRows* r) {
+    int ts = 0;
+    adas::tracker_live_views(tracker, &r->cnt, &r->tlwh, &r->frame_bytes, &ts, &r->cap);
+    r->cnt += offsetof(adas_track_header, n_tracked);
+    r->cnt_bytes = r->cls_frame_bytes = r->frame_bytes;
+    r->row_bytes = r->cls_row_bytes = sizeof(adas_track);
+    r->cls = r->tlwh + offsetof(adas_track, class_id);
+    r->act = r->tlwh + offsetof(adas_track, is_activated);
+    return ts;
+}
+
+static void overlay_rows_of_arrays(const adas_overlay_arrays& a, OvRows* r) {
+    r->tlwh = (const unsigned char*)a.d_trk_tlwh; r->frame_bytes = (size_t)a.trk_cap * 32; r->row_bytes = 32;
+    r->cls = (const unsigned char*)a.d_trk_cls; r->cls_frame_bytes = (size_t)a.trk_cap * 4; r->cls_row_bytes = 4; r->act = nullptr;
+    r->cnt = (const unsigned char*)a.d_trk_counts; r->cnt_bytes = 4; r->cap = a.trk_cap;
+}
+
+static void overlay_rows_to_objects(const OvRows& r, OvObjects* o) {
+    o->trk_tlwh = r.tlwh; o->trk_cls = r.cls; o->trk_act = r.act; o->trk_cnt = r.cnt; o->trk_cap = r.cap;
+    o->trk_frame_bytes = r.frame_bytes; o->trk_row_bytes = r.row_bytes; o->trk_cnt_bytes = r.cnt_bytes;
+    o->trk_cls_frame_bytes = r.cls_frame_bytes; o->trk_cls_row_bytes = r.cls_row_bytes;
+}
+
+static void overlay_rows_to_tracks(const OvRows& r, OvTracks* t) {
+    t->tlwh = r.tlwh; t->cls = r.cls; t->act = r.act; t->cnt = r.cnt; t->trk_cap = r.cap;
+    t->frame_bytes = r.frame_bytes; t->row_bytes = r.row_bytes; t->cnt_bytes = r.cnt_bytes;
+    t->cls_frame_bytes = r.cls_frame_bytes; t->cls_row_bytes = r.cls_row_bytes;
+}
+
+struct OvRun {                      // one run as overlay_launch takes it; what a stage that is off would read stays zero
+    const uint8_t* src; uint8_t* dst;   // dst null: the handle's own buffer
+    OvSources s;
+    const int *bird_pts, *bird_cnt; // the bird view's lane points and counts, bird_cnt[q * bird_cnt_stride + l]
+    int bird_cnt_stride;
+    uint8_t* d_bird;
+    OvObjects obj;                  // the boxes (stages 16 / 32)
+    OvTracks trk;                   // the tracks (stage 128)
+    int stages, frames;
+    hipStream_t st;
+};
+
+// the launches of one run
+static int overlay_launch(adas_overlay* h, const OvRun& r) {
+    const int stages = r.stages, frames = r.frames; const hipStream_t st = r.st;
     const int frame_stages = stages & (ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | ADAS_OVERLAY_DISTANCE | OV_OBJ_STAGES);
     const bool traj = (stages & ADAS_OVERLAY_TRAJECTORIES) != 0;   // two launches of its own; without it neither, and nothing else changes
     if (frame_stages || traj) {
-        if (!dst) {
+        if (!r.dst) {
             int rc = overlay_own_buffer(h);
             if (rc) return rc;
         }
         OvDevObj d;
         memset(&d, 0, sizeof(d));
-        d.s = s;
+        d.s = r.s;
         overlay_style(h->p, 0, &d.st);
         d.H = h->p.src_h; d.W = h->p.src_w; d.rw = h->rw;
         d.any = h->any; d.detail = h->detail; d.flags = h->flags;
         d.stages = frame_stages;
-        d.src = src;
-        d.dst = dst ? dst : h->d_dst;
+        d.src = r.src;
+        d.dst = r.dst ? r.dst : h->d_dst;
         int nplanes = OV_PLANES;
         size_t stream_lds = 0;
         if (frame_stages & OV_OBJ_STAGES) {   // one more launch, ahead of the coverage: the boxes' records
-            d.o = *obj;
+            d.o = r.obj;
             if (!(frame_stages & ADAS_OVERLAY_DETECTIONS)) d.o.det_cap = 0;
             if (!(frame_stages & ADAS_OVERLAY_TRACKS)) d.o.trk_cap = 0;
             int rc = overlay_reserve_records(h, d.o.det_cap + d.o.trk_cap);
@@ -982,10 +1037,10 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
         }
         OvTrkDev td;
         if (traj) {   // the tracks' primitives, beside the boxes' records
-            int rc = overlay_reserve_tracks(h, trk->trk_cap);
+            int rc = overlay_reserve_tracks(h, r.trk.trk_cap);
             if (rc) return rc;
             memset(&td, 0, sizeof(td));
-            td.t = *trk;
+            td.t = r.trk;
             td.H = d.H; td.W = d.W; td.rw = d.rw;
             td.band = overlay_band(d.rw, 2);
             td.colors = h->colors[1]; td.n_colors = h->n_colors[1];
@@ -999,10 +1054,10 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
             }
             td.radii = overlay_obj_radii(h->os.det_rect_thickness, h->os.det_arm_thickness, h->os.track_thickness);
             td.dst = d.dst;
-            hipLaunchKernelGGL(overlay_track_prims_kernel, dim3((unsigned)((trk->trk_cap + OV_TRK_LANES - 1) / OV_TRK_LANES), (unsigned)frames),
+            hipLaunchKernelGGL(overlay_track_prims_kernel, dim3((unsigned)((r.trk.trk_cap + OV_TRK_LANES - 1) / OV_TRK_LANES), (unsigned)frames),
                                dim3(OV_TRK_LANES), 0, st, td);
             ADAS_HIP_TRY(hipGetLastError());
-            h->trj_run_cap = trk->trk_cap;
+            h->trj_run_cap = r.trk.trk_cap;
             h->trj_run_frames = frames;
         }
         d.band = overlay_band(d.rw, nplanes);
@@ -1029,23 +1084,23 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
         }
         hipLaunchKernelGGL(overlay_clean_kernel, dim3(overlay_grid(words)), dim3(OV_THREADS), 0, st, plain, words);
         ADAS_HIP_TRY(hipGetLastError());
-        if (!dst && frames > h->dst_frames) h->dst_frames = frames;
+        if (!r.dst && frames > h->dst_frames) h->dst_frames = frames;
         h->run_frames = frames;
     }
     if (stages & ADAS_OVERLAY_BIRD) {
         OvDev d;
         memset(&d, 0, sizeof(d));
-        d.s.lane_pts = bird_pts;
-        d.s.lane_cnt = bird_cnt;
-        d.s.lane_cnt_stride = bird_cnt_stride;
-        d.s.offset_type = s.offset_type;
-        d.s.offset_stride = s.offset_stride;
+        d.s.lane_pts = r.bird_pts;
+        d.s.lane_cnt = r.bird_cnt;
+        d.s.lane_cnt_stride = r.bird_cnt_stride;
+        d.s.offset_type = r.s.offset_type;
+        d.s.offset_stride = r.s.offset_stride;
         overlay_style(h->p, 1, &d.st);
         d.H = h->p.bird_h; d.W = h->p.bird_w; d.rw = h->bird_rw;
         d.any = h->bird_any; d.detail = h->bird_detail; d.flags = nullptr;
         d.stages = ADAS_OVERLAY_LANES;
         d.direct = 1;
-        d.dst = d_bird;
+        d.dst = r.d_bird;
         d.band = overlay_band(d.rw, OV_PLANES);
         hipLaunchKernelGGL(overlay_mark_kernel, dim3((unsigned)((d.H + d.band - 1) / d.band), (unsigned)frames), dim3(OV_THREADS),
                            ((size_t)OV_PLANES * d.band * d.rw + OV_LIST) * 4, st, d);
@@ -1058,166 +1113,139 @@ static int overlay_launch(adas_overlay* h, const uint8_t* src, uint8_t* dst, OvS
     return ADAS_OK;
 }
 
-// who: the entry point's name; mask: the stage bits it accepts
-#define OV_RUN_REQUIRE(who, frames, mask)                                                                                                     \
-    ADAS_REQUIRE(h && (frames) > 0 && (frames) <= h->max_batch, ADAS_ERR_INVALID, "%s: bad argument (%d frames, the handle holds %d)", who,   \
-                 (int)(frames), h ? h->max_batch : 0);                                                                                        \
-    ADAS_REQUIRE(!(stages & ~(mask)), ADAS_ERR_INVALID, "%s: unknown stage bits 0x%x", who, stages);                                          \
-    ADAS_REQUIRE(!(stages & (mask) & ~ADAS_OVERLAY_BIRD) || d_src_bgr, ADAS_ERR_INVALID, "%s: the frame stages need source frames", who);     \
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (h->p.bird_h > 0 && d_bird_bgr), ADAS_ERR_INVALID,                                          \
-                 "%s: the bird stage needs a handle created with a bird-view size and a bird-view image", who)
+// what every run checks first.  who: the entry point's name; mask: the stage bits it accepts
+static int overlay_check_run(const char* who, int mask, const adas_overlay* h, long long frames, int stages, const void* d_src_bgr, const void* d_bird_bgr) {
+    ADAS_REQUIRE(h && frames > 0 && frames <= h->max_batch, ADAS_ERR_INVALID, "%s: bad argument (%d frames, the handle holds %d)", who, (int)frames,
+                 h ? h->max_batch : 0);
+    ADAS_REQUIRE(!(stages & ~mask), ADAS_ERR_INVALID, "%s: unknown stage bits 0x%x", who, stages);
+    ADAS_REQUIRE(!(stages & mask & ~ADAS_OVERLAY_BIRD) || d_src_bgr, ADAS_ERR_INVALID, "%s: the frame stages need source frames", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (h->p.bird_h > 0 && d_bird_bgr), ADAS_ERR_INVALID,
+                 "%s: the bird stage needs a handle created with a bird-view size and a bird-view image", who);
+    return ADAS_OK;
+}
 
-// adas_overlay_run (mask 15, no post / tracker) and adas_overlay_run_objects (mask 63)
-static int overlay_run_handles(const char* who, int mask, adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
-                               adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker,
-                               uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream) {
+// every run from the handles' device arrays: the three adas_overlay_run* entry points and the pipeline's step are masks over it
+int adas::overlay_run_handles(const char* who, int mask, adas_overlay* h, const adas::overlay_handles& a) {
+    const int stages = a.stages, n_streams = a.n_streams, n_frames = a.n_frames;
     ADAS_REQUIRE(n_streams > 0 && n_frames > 0, ADAS_ERR_INVALID, "%s: bad argument (%d streams x %d frames)", who, n_streams, n_frames);
     const long long frames = (long long)n_streams * n_frames;
-    OV_RUN_REQUIRE(who, frames, mask);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || decode, ADAS_ERR_INVALID, "%s: the lane stage needs a decode handle", who);
-    ADAS_REQUIRE(!decode || adas::decode_num_lanes(decode) == 4, ADAS_ERR_INVALID,
+    int rc = overlay_check_run(who, mask, h, frames, stages, a.d_src_bgr, a.d_bird_bgr);
+    if (rc) return rc;
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || a.decode, ADAS_ERR_INVALID, "%s: the lane stage needs a decode handle", who);
+    ADAS_REQUIRE(!a.decode || adas::decode_num_lanes(a.decode) == 4, ADAS_ERR_INVALID,
                  "%s: the decoder has num_lanes = %d (CurveLanes); the overlay draws the reference's four lane colours, num_lanes must be 4", who,
-                 adas::decode_num_lanes(decode));
-    ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_AREA | ADAS_OVERLAY_BIRD)) || geometry, ADAS_ERR_INVALID, "%s: the area and bird stages need a geometry handle",
+                 adas::decode_num_lanes(a.decode));
+    ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_AREA | ADAS_OVERLAY_BIRD)) || a.geometry, ADAS_ERR_INVALID, "%s: the area and bird stages need a geometry handle",
                  who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || analysis, ADAS_ERR_INVALID, "%s: the distance stage needs an analysis handle", who);
-    ADAS_REQUIRE((!decode || frames <= adas::handle_max_batch(decode)) && (!geometry || frames <= adas::handle_max_batch(geometry)), ADAS_ERR_INVALID,
-                 "%s: %d frames, the decode handle holds %d, the geometry handle %d", who, (int)frames, adas::handle_max_batch(decode),
-                 adas::handle_max_batch(geometry));
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || a.analysis, ADAS_ERR_INVALID, "%s: the distance stage needs an analysis handle", who);
+    ADAS_REQUIRE((!a.decode || frames <= adas::handle_max_batch(a.decode)) && (!a.geometry || frames <= adas::handle_max_batch(a.geometry)),
+                 ADAS_ERR_INVALID, "%s: %d frames, the decode handle holds %d, the geometry handle %d", who, (int)frames, adas::handle_max_batch(a.decode),
+                 adas::handle_max_batch(a.geometry));
     int af = 0;
-    ADAS_REQUIRE(!analysis || (adas::analysis_capacity(analysis, nullptr, &af) && frames <= af), ADAS_ERR_INVALID,
+    ADAS_REQUIRE(!a.analysis || (adas::analysis_capacity(a.analysis, nullptr, &af) && frames <= af), ADAS_ERR_INVALID,
                  "%s: %d frames, the analysis handle holds %d", who, (int)frames, af);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || post, ADAS_ERR_INVALID, "%s: the detections stage needs a yolo_post handle", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || tracker, ADAS_ERR_INVALID, "%s: the tracks stage needs a bytetrack handle", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || tracker, ADAS_ERR_INVALID, "%s: the trajectories stage needs a bytetrack handle", who);
-    OvObjects o;
-    memset(&o, 0, sizeof(o));
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || a.post, ADAS_ERR_INVALID, "%s: the detections stage needs a yolo_post handle", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || a.tracker, ADAS_ERR_INVALID, "%s: the tracks stage needs a bytetrack handle", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || a.tracker, ADAS_ERR_INVALID, "%s: the trajectories stage needs a bytetrack handle", who);
+    OvRun r = {};
     if (stages & ADAS_OVERLAY_DETECTIONS) {
-        ADAS_REQUIRE(frames <= adas::handle_max_batch(post), ADAS_ERR_INVALID, "%s: %d frames, the yolo_post handle holds %d", who, (int)frames,
-                     adas::handle_max_batch(post));
+        ADAS_REQUIRE(frames <= adas::handle_max_batch(a.post), ADAS_ERR_INVALID, "%s: %d frames, the yolo_post handle holds %d", who, (int)frames,
+                     adas::handle_max_batch(a.post));
         const int* cnt = nullptr;
-        adas::post_survivor_views(post, &o.det_xyxy, &o.det_cls, &cnt, &o.det_cap);
-        o.det_cnt = cnt + 2;   // counts[4]: n_found, n_candidates, n_keep, flags
-        o.det_cnt_stride = 4;
+        adas::post_survivor_views(a.post, &r.obj.det_xyxy, &r.obj.det_cls, &cnt, &r.obj.det_cap);
+        r.obj.det_cnt = cnt + 2; r.obj.det_cnt_stride = 4;   // counts[4]: n_found, n_candidates, n_keep, flags
     }
-    if (stages & ADAS_OVERLAY_TRACKS) {
+    if (stages & (ADAS_OVERLAY_TRACKS | ADAS_OVERLAY_TRAJECTORIES)) {   // both read the tracker's live table: one view of its rows
+        const char* stage = (stages & ADAS_OVERLAY_TRACKS) ? "tracks" : "trajectories";
         ADAS_REQUIRE(n_frames == 1, ADAS_ERR_INVALID,
-                     "%s: the tracks stage draws the tracker's live table, which holds the last frame only: n_frames must be 1 (got %d)", who, n_frames);
-        int ts = 0;
-        adas::tracker_live_views(tracker, &o.trk_cnt, &o.trk_tlwh, &o.trk_frame_bytes, &ts, &o.trk_cap);
+                     "%s: the %s stage draws the tracker's live table, which holds the last frame only: n_frames must be 1 (got %d)", who, stage, n_frames);
+        OvRows rows;
+        const int ts = overlay_rows_of_tracker(a.tracker, &rows);
         ADAS_REQUIRE(n_streams <= ts, ADAS_ERR_INVALID, "%s: %d streams, the bytetrack handle holds %d", who, n_streams, ts);
-        o.trk_cnt += offsetof(adas_track_header, n_tracked);
-        o.trk_cnt_bytes = o.trk_frame_bytes;
-        o.trk_row_bytes = sizeof(adas_track);
-        o.trk_cls = o.trk_tlwh + offsetof(adas_track, class_id);
-        o.trk_cls_frame_bytes = o.trk_frame_bytes; o.trk_cls_row_bytes = o.trk_row_bytes;
-        o.trk_act = o.trk_tlwh + offsetof(adas_track, is_activated);
+        if (stages & ADAS_OVERLAY_TRACKS) overlay_rows_to_objects(rows, &r.obj);
+        if (stages & ADAS_OVERLAY_TRAJECTORIES) {
+            overlay_rows_to_tracks(rows, &r.trk);
+            adas::tracker_ring_views(a.tracker, &r.trk.slot_ids, &r.trk.len, &r.trk.len_row_bytes, &r.trk.ring);   // the rings, through the slot each row names
+            r.trk.slot_frame_bytes = r.trk.len_frame_bytes = r.trk.ring_frame_bytes = rows.frame_bytes;
+        }
     }
-    OvTracks t;
-    memset(&t, 0, sizeof(t));
-    if (stages & ADAS_OVERLAY_TRAJECTORIES) {
-        ADAS_REQUIRE(n_frames == 1, ADAS_ERR_INVALID,
-                     "%s: the trajectories stage draws the tracker's live table, which holds the last frame only: n_frames must be 1 (got %d)", who,
-                     n_frames);
-        int ts = 0;
-        adas::tracker_live_views(tracker, &t.cnt, &t.tlwh, &t.frame_bytes, &ts, &t.trk_cap);
-        ADAS_REQUIRE(n_streams <= ts, ADAS_ERR_INVALID, "%s: %d streams, the bytetrack handle holds %d", who, n_streams, ts);
-        t.cnt += offsetof(adas_track_header, n_tracked);
-        t.cnt_bytes = t.frame_bytes;
-        t.row_bytes = sizeof(adas_track);
-        t.cls = t.tlwh + offsetof(adas_track, class_id);
-        t.cls_frame_bytes = t.frame_bytes; t.cls_row_bytes = t.row_bytes;
-        t.act = t.tlwh + offsetof(adas_track, is_activated);
-        adas::tracker_ring_views(tracker, &t.slot_ids, &t.len, &t.len_row_bytes, &t.ring);   // the rings, through the slot each row names
-        t.slot_frame_bytes = t.len_frame_bytes = t.ring_frame_bytes = t.frame_bytes;
-    }
-    OvSources s;
-    memset(&s, 0, sizeof(s));
-    if (decode) {
+    OvSources& s = r.s;
+    if (a.decode) {
         const int *cnt, *det, *pts;
-        adas::decode_lane_views(decode, &cnt, &det, &pts);
+        adas::decode_lane_views(a.decode, &cnt, &det, &pts);
         s.lane_pts = pts; s.lane_cnt = cnt; s.lane_cnt_stride = 4;
     }
-    const int* bird_pts = nullptr;
-    const int* bird_cnt = nullptr;
-    if (geometry) {
+    if (a.geometry) {
         const int32_t *hdr = nullptr, *area = nullptr;
         const double* vals = nullptr;
         int32_t area_stride = 0;
-        int rc = adas_lane_geometry_device_views(geometry, &hdr, &vals, &area, &area_stride);
+        rc = adas_lane_geometry_device_views(a.geometry, &hdr, &vals, &area, &area_stride);
         if (rc) return rc;
         s.poly = area; s.poly_stride = (size_t)area_stride; s.poly_max = area_stride / 2;
         s.poly_n0 = hdr + 1; s.poly_n1 = hdr + 2; s.poly_n_stride = 8;   // area_points = the left points, then the reversed right points
         s.area_on = hdr; s.area_on_stride = 8;
-        bird_pts = adas::geometry_bird_points(geometry);
-        bird_cnt = hdr + 4;
+        r.bird_pts = adas::geometry_bird_points(a.geometry); r.bird_cnt = hdr + 4;
     }
-    if (analysis) {
+    if (a.analysis) {
         const int *fr, *pts;
         int stride = 0, maxp = 0;
-        adas::analysis_frame_views(analysis, &fr, &stride, &pts, &maxp);
+        adas::analysis_frame_views(a.analysis, &fr, &stride, &pts, &maxp);
         s.offset_type = fr + offsetof(adas_analysis_frame, offset_msg) / 4; s.offset_stride = stride;
         s.collision = fr + offsetof(adas_analysis_frame, collision_msg) / 4; s.collision_stride = stride;
         s.dist_pts = pts; s.dist_cap = maxp;
         s.dist_cnt = fr + offsetof(adas_analysis_frame, n_points) / 4; s.dist_cnt_stride = stride;
     }
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, bird_pts, bird_cnt, 8, d_bird_bgr, stages, (int)frames, (hipStream_t)stream, &o, &t);
+    r.src = a.d_src_bgr; r.dst = a.d_dst_bgr; r.d_bird = a.d_bird_bgr; r.bird_cnt_stride = 8;
+    r.stages = stages; r.frames = (int)frames; r.st = (hipStream_t)a.stream;
+    return overlay_launch(h, r);
 }
 
-// adas_overlay_run_arrays (mask 15, no box arrays) and adas_overlay_run_arrays_objects (mask 63)
-static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points,
-                           const int32_t* d_lane_counts, const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
-                           const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
-                           const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr,
-                           const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts, const double* d_trk_tlwh,
-                           int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages, int n_frames, void* stream,
-                           const double* d_traj_tlbr = nullptr, const int32_t* d_traj_len = nullptr) {
-    OV_RUN_REQUIRE(who, n_frames, mask);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || (d_trk_tlwh && trk_cap > 0 && d_trk_cls && d_trk_counts && d_traj_tlbr && d_traj_len),
-                 ADAS_ERR_INVALID, "%s: the trajectories stage needs the tracks' boxes, classes and counts, and their trajectories and lengths", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || (d_lane_points && d_lane_counts), ADAS_ERR_INVALID, "%s: the lane stage needs lane points and counts",
-                 who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_AREA) || (d_poly && poly_cap > 0 && d_poly_counts && d_area_status), ADAS_ERR_INVALID,
+// every run from raw device arrays: the three adas_overlay_run_arrays* entry points are masks over it
+static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const adas_overlay_arrays& a) {
+    const int stages = a.stages;
+    int rc = overlay_check_run(who, mask, h, a.n_frames, stages, a.d_src_bgr, a.d_bird_bgr);
+    if (rc) return rc;
+    const bool rows_given = a.d_trk_tlwh && a.trk_cap > 0 && a.d_trk_cls && a.d_trk_counts;
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || (rows_given && a.d_traj_tlbr && a.d_traj_len), ADAS_ERR_INVALID,
+                 "%s: the trajectories stage needs the tracks' boxes, classes and counts, and their trajectories and lengths", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_LANES) || (a.d_lane_points && a.d_lane_counts), ADAS_ERR_INVALID,
+                 "%s: the lane stage needs lane points and counts", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_AREA) || (a.d_poly && a.poly_cap > 0 && a.d_poly_counts && a.d_area_status), ADAS_ERR_INVALID,
                  "%s: the area stage needs a polygon, its counts and the area flags", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || (d_dist_points && dist_cap > 0 && d_dist_counts), ADAS_ERR_INVALID,
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || (a.d_dist_points && a.dist_cap > 0 && a.d_dist_counts), ADAS_ERR_INVALID,
                  "%s: the distance stage needs distance points and counts", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (d_bird_points && d_bird_counts), ADAS_ERR_INVALID, "%s: the bird stage needs bird points and counts", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (d_det_xyxy && det_cap > 0 && d_det_cls && d_det_counts), ADAS_ERR_INVALID,
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (a.d_bird_points && a.d_bird_counts), ADAS_ERR_INVALID, "%s: the bird stage needs bird points and counts",
+                 who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (a.d_det_xyxy && a.det_cap > 0 && a.d_det_cls && a.d_det_counts), ADAS_ERR_INVALID,
                  "%s: the detections stage needs boxes, classes and counts", who);
-    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (d_trk_tlwh && trk_cap > 0 && d_trk_cls && d_trk_counts), ADAS_ERR_INVALID,
-                 "%s: the tracks stage needs boxes, classes and counts", who);
-    ADAS_REQUIRE(det_cap <= (1 << 24) && trk_cap <= (1 << 24), ADAS_ERR_INVALID, "%s: capacities above 2^24 boxes per frame (%d, %d)", who, det_cap, trk_cap);
-    OvSources s;
-    memset(&s, 0, sizeof(s));
-    s.lane_pts = d_lane_points; s.lane_cnt = d_lane_counts; s.lane_cnt_stride = 4;
-    s.poly = d_poly; s.poly_stride = (size_t)(poly_cap > 0 ? poly_cap : 0) * 2; s.poly_max = poly_cap > 0 ? poly_cap : 0;
-    s.poly_n0 = d_poly_counts; s.poly_n1 = nullptr; s.poly_n_stride = 1;
-    s.area_on = d_area_status; s.area_on_stride = 1;
-    s.offset_type = d_offset_type; s.offset_stride = 1;
-    s.area_bgr = d_area_bgr;
-    s.dist_pts = d_dist_points; s.dist_cap = dist_cap > 0 ? dist_cap : 0;
-    s.dist_cnt = d_dist_counts; s.dist_cnt_stride = 1;
-    if (!(stages & ADAS_OVERLAY_AREA)) s.poly = nullptr;
-    OvObjects o;
-    memset(&o, 0, sizeof(o));
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || rows_given, ADAS_ERR_INVALID, "%s: the tracks stage needs boxes, classes and counts", who);
+    ADAS_REQUIRE(a.det_cap <= (1 << 24) && a.trk_cap <= (1 << 24), ADAS_ERR_INVALID, "%s: capacities above 2^24 boxes per frame (%d, %d)", who, a.det_cap,
+                 a.trk_cap);
+    OvRun r = {};
+    OvSources& s = r.s;
+    s.lane_pts = a.d_lane_points; s.lane_cnt = a.d_lane_counts; s.lane_cnt_stride = 4;
+    s.poly_max = a.poly_cap > 0 ? a.poly_cap : 0;
+    s.poly = (stages & ADAS_OVERLAY_AREA) ? a.d_poly : nullptr; s.poly_stride = (size_t)s.poly_max * 2;
+    s.poly_n0 = a.d_poly_counts; s.poly_n_stride = 1; s.area_on = a.d_area_status; s.area_on_stride = 1;
+    s.offset_type = a.d_offset_type; s.offset_stride = 1; s.area_bgr = a.d_area_bgr;
+    s.dist_pts = a.d_dist_points; s.dist_cap = a.dist_cap > 0 ? a.dist_cap : 0; s.dist_cnt = a.d_dist_counts; s.dist_cnt_stride = 1;
     if (stages & ADAS_OVERLAY_DETECTIONS) {
-        o.det_xyxy = d_det_xyxy; o.det_cls = d_det_cls; o.det_cnt = d_det_counts; o.det_cap = det_cap; o.det_cnt_stride = 1;
+        r.obj.det_xyxy = a.d_det_xyxy; r.obj.det_cls = a.d_det_cls; r.obj.det_cnt = a.d_det_counts; r.obj.det_cap = a.det_cap; r.obj.det_cnt_stride = 1;
     }
-    if (stages & ADAS_OVERLAY_TRACKS) {
-        o.trk_tlwh = (const unsigned char*)d_trk_tlwh; o.trk_frame_bytes = (size_t)trk_cap * 32; o.trk_row_bytes = 32;
-        o.trk_cls = (const unsigned char*)d_trk_cls; o.trk_cls_frame_bytes = (size_t)trk_cap * 4; o.trk_cls_row_bytes = 4; o.trk_act = nullptr;
-        o.trk_cnt = (const unsigned char*)d_trk_counts; o.trk_cnt_bytes = 4; o.trk_cap = trk_cap;
+    if (stages & (ADAS_OVERLAY_TRACKS | ADAS_OVERLAY_TRAJECTORIES)) {
+        OvRows rows;
+        overlay_rows_of_arrays(a, &rows);
+        if (stages & ADAS_OVERLAY_TRACKS) overlay_rows_to_objects(rows, &r.obj);
+        if (stages & ADAS_OVERLAY_TRAJECTORIES) {
+            overlay_rows_to_tracks(rows, &r.trk);
+            r.trk.ring = (const unsigned char*)a.d_traj_tlbr; r.trk.ring_frame_bytes = (size_t)a.trk_cap * ADAS_OVERLAY_TRACK_RING * 32;
+            r.trk.len = (const unsigned char*)a.d_traj_len; r.trk.len_frame_bytes = (size_t)a.trk_cap * 4; r.trk.len_row_bytes = 4;
+        }
     }
-    OvTracks t;
-    memset(&t, 0, sizeof(t));
-    if (stages & ADAS_OVERLAY_TRAJECTORIES) {
-        t.tlwh = (const unsigned char*)d_trk_tlwh; t.frame_bytes = (size_t)trk_cap * 32; t.row_bytes = 32;
-        t.cls = (const unsigned char*)d_trk_cls; t.cls_frame_bytes = (size_t)trk_cap * 4; t.cls_row_bytes = 4; t.act = nullptr;
-        t.cnt = (const unsigned char*)d_trk_counts; t.cnt_bytes = 4; t.trk_cap = trk_cap;
-        t.ring = (const unsigned char*)d_traj_tlbr; t.ring_frame_bytes = (size_t)trk_cap * ADAS_OVERLAY_TRACK_RING * 32;
-        t.len = (const unsigned char*)d_traj_len; t.len_frame_bytes = (size_t)trk_cap * 4; t.len_row_bytes = 4;
-    }
-    return overlay_launch(h, d_src_bgr, d_dst_bgr, s, d_bird_points, d_bird_counts, 4, d_bird_bgr, stages, n_frames, (hipStream_t)stream, &o, &t);
+    r.src = a.d_src_bgr; r.dst = a.d_dst_bgr; r.d_bird = a.d_bird_bgr;
+    r.bird_pts = a.d_bird_points; r.bird_cnt = a.d_bird_counts; r.bird_cnt_stride = 4;
+    r.stages = stages; r.frames = a.n_frames; r.st = (hipStream_t)a.stream;
+    return overlay_launch(h, r);
 }
 
 extern "C" {
@@ -1296,27 +1324,25 @@ int adas_overlay_set_style(adas_overlay* h, const adas_overlay_params* p) {
     return ADAS_OK;
 }
 
+// The six run entry points: each is its name and the stage bits it accepts over overlay_run_handles / overlay_run_raw.
 int adas_overlay_run(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
                      adas_analysis* analysis, uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream) {
-    return overlay_run_handles("adas_overlay_run", 15, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, nullptr, nullptr, d_bird_bgr, stages,
-                               n_streams, n_frames, stream);
+    return adas::overlay_run_handles("adas_overlay_run", 15, h,
+                                     {d_src_bgr, d_dst_bgr, decode, geometry, analysis, nullptr, nullptr, d_bird_bgr, stages, n_streams, n_frames, stream});
 }
 
 int adas_overlay_run_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
                              adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr, int stages, int n_streams,
                              int n_frames, void* stream) {
-    return overlay_run_handles("adas_overlay_run_objects", 63, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, post, tracker, d_bird_bgr, stages,
-                               n_streams, n_frames, stream);
+    return adas::overlay_run_handles("adas_overlay_run_objects", 63, h,
+                                     {d_src_bgr, d_dst_bgr, decode, geometry, analysis, post, tracker, d_bird_bgr, stages, n_streams, n_frames, stream});
 }
 
-int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points, const int32_t* d_lane_counts,
-                            const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
-                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
-                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
-                            int n_frames, void* stream) {
-    return overlay_run_raw("adas_overlay_run_arrays", 15, h, d_src_bgr, d_dst_bgr, d_lane_points, d_lane_counts, d_poly, poly_cap, d_poly_counts,
-                           d_area_status, d_offset_type, d_area_bgr, d_dist_points, dist_cap, d_dist_counts, d_bird_points, d_bird_counts, d_bird_bgr,
-                           nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stages, n_frames, stream);
+int adas_overlay_run_trajectories(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
+                                  adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr,
+                                  int stages, int n_streams, int n_frames, void* stream) {
+    return adas::overlay_run_handles("adas_overlay_run_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h,
+                                     {d_src_bgr, d_dst_bgr, decode, geometry, analysis, post, tracker, d_bird_bgr, stages, n_streams, n_frames, stream});
 }
 
 int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points,
@@ -1326,25 +1352,32 @@ int adas_overlay_run_arrays_objects(adas_overlay* h, const uint8_t* d_src_bgr, u
                                     uint8_t* d_bird_bgr, const int32_t* d_det_xyxy, int det_cap, const int32_t* d_det_cls, const int32_t* d_det_counts,
                                     const double* d_trk_tlwh, int trk_cap, const int32_t* d_trk_cls, const int32_t* d_trk_counts, int stages,
                                     int n_frames, void* stream) {
-    return overlay_run_raw("adas_overlay_run_arrays_objects", 63, h, d_src_bgr, d_dst_bgr, d_lane_points, d_lane_counts, d_poly, poly_cap, d_poly_counts,
-                           d_area_status, d_offset_type, d_area_bgr, d_dist_points, dist_cap, d_dist_counts, d_bird_points, d_bird_counts, d_bird_bgr,
-                           d_det_xyxy, det_cap, d_det_cls, d_det_counts, d_trk_tlwh, trk_cap, d_trk_cls, d_trk_counts, stages, n_frames, stream);
+    adas_overlay_arrays a = {};
+    a.d_src_bgr = d_src_bgr; a.d_dst_bgr = d_dst_bgr; a.d_lane_points = d_lane_points; a.d_lane_counts = d_lane_counts;
+    a.d_poly = d_poly; a.poly_cap = poly_cap; a.d_poly_counts = d_poly_counts; a.d_area_status = d_area_status;
+    a.d_offset_type = d_offset_type; a.d_area_bgr = d_area_bgr; a.d_dist_points = d_dist_points; a.dist_cap = dist_cap; a.d_dist_counts = d_dist_counts;
+    a.d_bird_points = d_bird_points; a.d_bird_counts = d_bird_counts; a.d_bird_bgr = d_bird_bgr; a.stages = stages; a.n_frames = n_frames; a.stream = stream;
+    a.d_det_xyxy = d_det_xyxy; a.det_cap = det_cap; a.d_det_cls = d_det_cls; a.d_det_counts = d_det_counts;
+    a.d_trk_tlwh = d_trk_tlwh; a.trk_cap = trk_cap; a.d_trk_cls = d_trk_cls; a.d_trk_counts = d_trk_counts;
+    return overlay_run_raw("adas_overlay_run_arrays_objects", 63, h, a);
 }
 
-int adas_overlay_run_trajectories(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
-                                  adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr,
-                                  int stages, int n_streams, int n_frames, void* stream) {
-    return overlay_run_handles("adas_overlay_run_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, d_src_bgr, d_dst_bgr, decode, geometry, analysis, post,
-                               tracker, d_bird_bgr, stages, n_streams, n_frames, stream);
+int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const int32_t* d_lane_points, const int32_t* d_lane_counts,
+                            const int32_t* d_poly, int poly_cap, const int32_t* d_poly_counts, const int32_t* d_area_status,
+                            const int32_t* d_offset_type, const uint8_t* d_area_bgr, const int32_t* d_dist_points, int dist_cap,
+                            const int32_t* d_dist_counts, const int32_t* d_bird_points, const int32_t* d_bird_counts, uint8_t* d_bird_bgr, int stages,
+                            int n_frames, void* stream) {
+    adas_overlay_arrays a = {};
+    a.d_src_bgr = d_src_bgr; a.d_dst_bgr = d_dst_bgr; a.d_lane_points = d_lane_points; a.d_lane_counts = d_lane_counts;
+    a.d_poly = d_poly; a.poly_cap = poly_cap; a.d_poly_counts = d_poly_counts; a.d_area_status = d_area_status;
+    a.d_offset_type = d_offset_type; a.d_area_bgr = d_area_bgr; a.d_dist_points = d_dist_points; a.dist_cap = dist_cap; a.d_dist_counts = d_dist_counts;
+    a.d_bird_points = d_bird_points; a.d_bird_counts = d_bird_counts; a.d_bird_bgr = d_bird_bgr; a.stages = stages; a.n_frames = n_frames; a.stream = stream;
+    return overlay_run_raw("adas_overlay_run_arrays", 15, h, a);
 }
 
 int adas_overlay_run_arrays_trajectories(adas_overlay* h, const adas_overlay_arrays* a) {
     ADAS_REQUIRE(a, ADAS_ERR_INVALID, "adas_overlay_run_arrays_trajectories: null argument");
-    return overlay_run_raw("adas_overlay_run_arrays_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, a->d_src_bgr, a->d_dst_bgr, a->d_lane_points,
-                           a->d_lane_counts, a->d_poly, a->poly_cap, a->d_poly_counts, a->d_area_status, a->d_offset_type, a->d_area_bgr, a->d_dist_points,
-                           a->dist_cap, a->d_dist_counts, a->d_bird_points, a->d_bird_counts, a->d_bird_bgr, a->d_det_xyxy, a->det_cap, a->d_det_cls,
-                           a->d_det_counts, a->d_trk_tlwh, a->trk_cap, a->d_trk_cls, a->d_trk_counts, a->stages, a->n_frames, a->stream, a->d_traj_tlbr,
-                           a->d_traj_len);
+    return overlay_run_raw("adas_overlay_run_arrays_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, *a);
 }
 
 int adas_overlay_fetch_track_marks(adas_overlay* h, int frame, adas_overlay_track_mark* marks, int max_marks, int32_t* n_marks) {

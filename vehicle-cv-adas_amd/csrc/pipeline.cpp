@@ -187,29 +187,19 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             rc = adas_warp_device_view(p->bird_warp, &bird_img);
             if (rc) return rc;
         }
-        if (stages & ADAS_OVERLAY_TRAJECTORIES) {   // the tracks' trajectories and direction marks, under the conditions of the tracks stage
-            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
-                         "the overlay's detections stage needs a detector with its post handle");
-            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
-                         "the overlay's tracks stage needs a tracker (and the detector that feeds it)");
-            ADAS_REQUIRE(p->d.tracker && p->d.detector, ADAS_ERR_INVALID, "the overlay's trajectories stage needs a tracker (and the detector that feeds it)");
-            ADAS_REQUIRE(B <= 1, ADAS_ERR_INVALID,
-                         "the overlay's %s stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step",
-                         (stages & ADAS_OVERLAY_TRACKS) ? "tracks" : "trajectories", B);
-            rc = adas_overlay_run_trajectories(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
-                                               const_cast<uint8_t*>(bird_img), stages, NS, B, st);
-        } else if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the object layer: this step's survivors, the tracker after this step's update
-            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
-                         "the overlay's detections stage needs a detector with its post handle");
-            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
-                         "the overlay's tracks stage needs a tracker (and the detector that feeds it)");
-            ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || B <= 1, ADAS_ERR_INVALID,
-                         "the overlay's tracks stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step", B);
-            rc = adas_overlay_run_objects(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
-                                          const_cast<uint8_t*>(bird_img), stages, NS, B, st);
-        } else {
-            rc = adas_overlay_run(p->overlay, p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, const_cast<uint8_t*>(bird_img), stages, NS, B, st);
-        }
+        // the object layer draws this step's survivors and the tracker after this step's update; trajectories under the conditions of tracks
+        ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DETECTIONS) || (p->d.detector && p->d.post), ADAS_ERR_INVALID,
+                     "the overlay's detections stage needs a detector with its post handle");
+        ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRACKS) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
+                     "the overlay's tracks stage needs a tracker (and the detector that feeds it)");
+        ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || (p->d.tracker && p->d.detector), ADAS_ERR_INVALID,
+                     "the overlay's trajectories stage needs a tracker (and the detector that feeds it)");
+        ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_TRACKS | ADAS_OVERLAY_TRAJECTORIES)) || B <= 1, ADAS_ERR_INVALID,
+                     "the overlay's %s stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step",
+                     (stages & ADAS_OVERLAY_TRACKS) ? "tracks" : "trajectories", B);
+        rc = adas::overlay_run_handles("adas_pipeline_step (overlay)", 63 | ADAS_OVERLAY_TRAJECTORIES, p->overlay,
+                                       {p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
+                                        const_cast<uint8_t*>(bird_img), stages, NS, B, st});
         if (rc) return rc;
     }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
@@ -389,21 +379,20 @@ int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
                  stages);
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
-    if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the boxes' records are allocated now: a captured step cannot
-        int det_cap = 0, trk_cap = 0, ts = 0;
-        const int *a, *b, *c;
-        const unsigned char *hdr, *out;
-        size_t sb = 0;
-        if ((stages & ADAS_OVERLAY_DETECTIONS) && p->d.post) adas::post_survivor_views(p->d.post, &a, &b, &c, &det_cap);
-        if ((stages & ADAS_OVERLAY_TRACKS) && p->d.tracker) adas::tracker_live_views(p->d.tracker, &hdr, &out, &sb, &ts, &trk_cap);
-        int rc = adas::overlay_reserve_objects(p->overlay, det_cap, trk_cap);
-        if (rc) return rc;
-    }
-    if ((stages & ADAS_OVERLAY_TRAJECTORIES) && p->d.tracker) {   // so are the tracks' primitives and their plane
-        int trk_cap = 0, ts = 0;
+    int det_cap = 0, trk_cap = 0;
+    if ((stages & (ADAS_OVERLAY_TRACKS | ADAS_OVERLAY_TRAJECTORIES)) && p->d.tracker) {
+        int ts = 0;
         const unsigned char *hdr, *out;
         size_t sb = 0;
         adas::tracker_live_views(p->d.tracker, &hdr, &out, &sb, &ts, &trk_cap);
+    }
+    if (stages & (ADAS_OVERLAY_DETECTIONS | ADAS_OVERLAY_TRACKS)) {   // the boxes' records are allocated now: a captured step cannot
+        const int *a, *b, *c;
+        if ((stages & ADAS_OVERLAY_DETECTIONS) && p->d.post) adas::post_survivor_views(p->d.post, &a, &b, &c, &det_cap);
+        int rc = adas::overlay_reserve_objects(p->overlay, det_cap, (stages & ADAS_OVERLAY_TRACKS) ? trk_cap : 0);
+        if (rc) return rc;
+    }
+    if ((stages & ADAS_OVERLAY_TRAJECTORIES) && p->d.tracker) {   // so are the tracks' primitives and their plane
         int rc = adas::overlay_reserve_trajectories(p->overlay, trk_cap);
         if (rc) return rc;
     }

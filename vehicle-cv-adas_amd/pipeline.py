@@ -58,22 +58,19 @@ class AdasPipeline:
                 raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
             ov_stages = dict(overlay).get("stages")
             ov_mask = None if ov_stages is None else LaneOverlay.stage_mask(ov_stages)
-            if ov_mask is not None and ov_mask & L.OVERLAY_DISTANCE and analysis is None:
-                raise ValueError("the overlay's distance stage needs analysis= (the distance points it draws)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_BIRD and not (birdview is not None and dict(birdview).get("image", False)):
-                raise ValueError("the overlay's bird stage needs birdview=dict(image=True) (the bird-view image it draws on)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_DETECTIONS and not det_model:
-                raise ValueError("the overlay's detections stage needs det_model= (the survivors it draws)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_TRACKS and not (det_model and track):
-                raise ValueError("the overlay's tracks stage needs det_model= and track=True (the tracked tracks it draws)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_TRACKS and self.B > 1:
-                raise ValueError("the overlay's tracks stage needs micro_batch=1: the tracker's live table holds only the last frame of a step")
-            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and not det_model:
-                raise ValueError("the overlay's trajectories stage needs det_model= (the detector that feeds the tracker it draws from)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and not track:
-                raise ValueError("the overlay's trajectories stage needs det_model= and track=True (the tracked tracks it draws)")
-            if ov_mask is not None and ov_mask & L.OVERLAY_TRAJECTORIES and self.B > 1:
-                raise ValueError("the overlay's trajectories stage needs micro_batch=1: the tracker's live table holds only the last frame of a step")
+            has_bird = birdview is not None and dict(birdview).get("image", False)
+            live = "the tracker's live table holds only the last frame of a step"
+            for bits, ok, msg in (      # (stage bits, what they need, the refusal), in the order they are checked
+                    (L.OVERLAY_DISTANCE, analysis is not None, "distance stage needs analysis= (the distance points it draws)"),
+                    (L.OVERLAY_BIRD, has_bird, "bird stage needs birdview=dict(image=True) (the bird-view image it draws on)"),
+                    (L.OVERLAY_DETECTIONS, det_model, "detections stage needs det_model= (the survivors it draws)"),
+                    (L.OVERLAY_TRACKS, det_model and track, "tracks stage needs det_model= and track=True (the tracked tracks it draws)"),
+                    (L.OVERLAY_TRACKS, self.B <= 1, "tracks stage needs micro_batch=1: " + live),
+                    (L.OVERLAY_TRAJECTORIES, det_model, "trajectories stage needs det_model= (the detector that feeds the tracker it draws from)"),
+                    (L.OVERLAY_TRAJECTORIES, track, "trajectories stage needs det_model= and track=True (the tracked tracks it draws)"),
+                    (L.OVERLAY_TRAJECTORIES, self.B <= 1, "trajectories stage needs micro_batch=1: " + live)):
+                if ov_mask is not None and ov_mask & bits and not ok:
+                    raise ValueError("the overlay's " + msg)
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:

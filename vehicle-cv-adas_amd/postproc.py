@@ -628,19 +628,9 @@ class LaneOverlay:
         if stages is None:
             stages = ((L.OVERLAY_LANES if decode else 0) | (L.OVERLAY_AREA if geometry else 0) | (L.OVERLAY_DISTANCE if analysis else 0) |
                       (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if post else 0) | (L.OVERLAY_TRACKS if tracker else 0))
-        mask = self.stage_mask(stages)
-        if mask & L.OVERLAY_TRAJECTORIES:
-            L.check(L.lib().adas_overlay_run_trajectories(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
-                                                          analysis.h if analysis else None, post.h if post else None, tracker.h if tracker else None,
-                                                          bird_ptr, mask, int(n_streams), int(n_frames), stream))
-            return
-        if post is None and tracker is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
-            L.check(L.lib().adas_overlay_run(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
-                                             analysis.h if analysis else None, bird_ptr, mask, int(n_streams), int(n_frames), stream))
-            return
-        L.check(L.lib().adas_overlay_run_objects(self.h, src_ptr, dst_ptr, decode.h if decode else None, geometry.h if geometry else None,
-                                                 analysis.h if analysis else None, post.h if post else None, tracker.h if tracker else None, bird_ptr,
-                                                 mask, int(n_streams), int(n_frames), stream))
+        h = lambda x: x.h if x else None     # the widest entry of its family: the narrower ones are masks over the same path
+        L.check(L.lib().adas_overlay_run_trajectories(self.h, src_ptr, dst_ptr, h(decode), h(geometry), h(analysis), h(post), h(tracker), bird_ptr,
+                                                      self.stage_mask(stages), int(n_streams), int(n_frames), stream))
 
     def run_arrays(self, src_ptr, n_frames=1, lane_points=None, lane_counts=None, poly=None, poly_cap=0, poly_counts=None, area_status=None,
                    offset_type=None, area_bgr=None, dist_points=None, dist_cap=0, dist_counts=None, bird_points=None, bird_counts=None,
@@ -655,28 +645,14 @@ class LaneOverlay:
             stages = ((L.OVERLAY_LANES if lane_points else 0) | (L.OVERLAY_AREA if poly else 0) | (L.OVERLAY_DISTANCE if dist_points else 0) |
                       (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if det_xyxy else 0) |
                       (L.OVERLAY_TRACKS if (trk_tlwh and trajectories is None) else 0) | (L.OVERLAY_TRAJECTORIES if trajectories is not None else 0))
-        mask = self.stage_mask(stages)
-        if trajectories is not None or mask & L.OVERLAY_TRAJECTORIES:
-            a = L.OverlayArrays()
-            tr = trajectories if trajectories is not None else (None, None)
-            for k, v in dict(d_src_bgr=src_ptr, d_dst_bgr=dst_ptr, d_lane_points=lane_points, d_lane_counts=lane_counts, d_poly=poly,
-                             d_poly_counts=poly_counts, d_area_status=area_status, d_offset_type=offset_type, d_area_bgr=area_bgr,
-                             d_dist_points=dist_points, d_dist_counts=dist_counts, d_bird_points=bird_points, d_bird_counts=bird_counts,
-                             d_bird_bgr=bird_ptr, d_det_xyxy=det_xyxy, d_det_cls=det_cls, d_det_counts=det_counts, d_trk_tlwh=trk_tlwh,
-                             d_trk_cls=trk_cls, d_trk_counts=trk_counts, d_traj_tlbr=tr[0], d_traj_len=tr[1], stream=stream).items():
-                setattr(a, k, v)
-            a.poly_cap, a.dist_cap, a.det_cap, a.trk_cap, a.stages, a.n_frames = int(poly_cap), int(dist_cap), int(det_cap), int(trk_cap), mask, int(n_frames)
-            L.check(L.lib().adas_overlay_run_arrays_trajectories(self.h, C.byref(a)))
-            return
-        if det_xyxy is None and trk_tlwh is None and not mask & (L.OVERLAY_DETECTIONS | L.OVERLAY_TRACKS):
-            L.check(L.lib().adas_overlay_run_arrays(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
-                                                    offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts, bird_ptr,
-                                                    mask, int(n_frames), stream))
-            return
-        L.check(L.lib().adas_overlay_run_arrays_objects(self.h, src_ptr, dst_ptr, lane_points, lane_counts, poly, int(poly_cap), poly_counts, area_status,
-                                                        offset_type, area_bgr, dist_points, int(dist_cap), dist_counts, bird_points, bird_counts,
-                                                        bird_ptr, det_xyxy, int(det_cap), det_cls, det_counts, trk_tlwh, int(trk_cap), trk_cls,
-                                                        trk_counts, mask, int(n_frames), stream))
+        tr = trajectories if trajectories is not None else (None, None)
+        a = L.OverlayArrays(                # the widest entry of its family: the narrower ones are masks over the same path
+            d_src_bgr=src_ptr, d_dst_bgr=dst_ptr, d_lane_points=lane_points, d_lane_counts=lane_counts, d_poly=poly, d_poly_counts=poly_counts,
+            d_area_status=area_status, d_offset_type=offset_type, d_area_bgr=area_bgr, d_dist_points=dist_points, d_dist_counts=dist_counts,
+            d_bird_points=bird_points, d_bird_counts=bird_counts, d_bird_bgr=bird_ptr, d_det_xyxy=det_xyxy, d_det_cls=det_cls, d_det_counts=det_counts,
+            d_trk_tlwh=trk_tlwh, d_trk_cls=trk_cls, d_trk_counts=trk_counts, d_traj_tlbr=tr[0], d_traj_len=tr[1], stream=stream, poly_cap=int(poly_cap),
+            dist_cap=int(dist_cap), det_cap=int(det_cap), trk_cap=int(trk_cap), stages=self.stage_mask(stages), n_frames=int(n_frames))
+        L.check(L.lib().adas_overlay_run_arrays_trajectories(self.h, C.byref(a)))
 
     def fetch(self, frame=0):
         out = np.empty((self.src_hw[0], self.src_hw[1], 3), np.uint8)
