@@ -643,7 +643,7 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * in HBM -- UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame (ultrafastLaneDetectorV2.py:196-218, the same in v1), the
  * discs of SingleCamDistanceMeasure.DrawDetectedOnFrame (distanceMeasure.py:98) and PerspectiveTransformation.DrawDetectedOnBirdView
  * (perspectiveTransformation.py:217-226): two whole-frame cv2.addWeighted passes, a cv2.fillPoly and filled cv2.circles.
- * NOT drawn: text (putText / getTextSize) and the UI panels; the boxes of the detector and the tracker are the object layer below, the
+ * NOT drawn: text (putText / getTextSize); the UI panels are adas_overlay_run_panels below, with a mask of their own; the boxes of the detector and the tracker are the object layer below, the
  * tracker's trajectories and direction marks (thick circles, arrowedLine) the trajectories stage below that.
  * The pixel rules are modelled on OpenCV 4.5's drawing.cpp / arithm and defined in csrc/overlay_core.h (restated in NumPy,
  * tests/overlay_ref.py); parity with a real cv2 build is UNPINNED, and lines are not clipped before they are walked (OpenCV clips the
@@ -674,7 +674,7 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * A class id outside the colour table is the reference's 'unknown': black.  Where boxes overlap the result is the sequential fold of the
  * reference's calls; the distance discs still lie over everything.  The pixel rules are D6-D9 of csrc/overlay_core.h (a thick axis-aligned
  * segment is a body plus two end discs; modelled on OpenCV 4.5's ThickLine, parity UNPINNED).  NOT drawn: text, the label's background
- * rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines, the UI panels.  One more launch (the boxes' records) when one
+ * rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines.  One more launch (the boxes' records) when one
  * of the two stages is on, none when both are off; nothing is capped below the sources' capacities (max_candidates per frame, max_tracks
  * per stream).
  *
@@ -826,6 +826,78 @@ int adas_overlay_device_view(adas_overlay* h, const uint8_t** d_bgr);
 /* ADAS_OVERLAY_* flags of frame `frame` of the last run.  Synchronises. */
 int adas_overlay_fetch_flags(adas_overlay* h, int frame, int32_t* flags);
 
+/* The demo's three UI panels on frames that sit in HBM (ControlPanel.DisplayBirdViewPanel / DisplaySignsPanel / DisplayCollisionPanel,
+ * demo.py:101-214, painted in that order as at demo.py:307-309), without their putText lines and the FPS string: the bird-view image
+ * resized to W x H = int(src_w * ratio) x int(src_h * ratio) inside a black border in the top right corner; the dimmed, red-framed signs
+ * widget in the top left corner with up to two sign sprites; the dimmed, red-framed collision widget below the bird panel with one FCWS
+ * sprite.  The pixel and state rules P1-P6 are csrc/overlay_panel_core.h (the signs and collision panels and the bird panel's placement
+ * restate the reference's NumPy lines; the resize is the rule of adas_preprocess_*, parity with a real cv2 build UNPINNED).
+ * The panels are NOT stage bits of the masks above: they have a mask and calls of their own, in place on frames that have been drawn.
+ * Two launches: one lane per stream walks that stream's frames in order and writes a record per frame (the sprites chosen and the
+ * curve_status latch, which lives in the handle's device memory, so a replayed graph carries it), then one pass over the rows and column
+ * spans of the panels writes every byte at most once with the whole sequence folded in (16-byte accesses; overlapping panels on narrow
+ * frames need no second pass).  Both are plain launches: capturable. */
+#define ADAS_PANEL_BIRD 1
+#define ADAS_PANEL_SIGNS 2
+#define ADAS_PANEL_COLLISION 4
+#define ADAS_PANEL_SPRITES 9
+#define ADAS_PANEL_SPRITE_FCWS_WARNING 0 /* assets/FCWS-warning.png at 100 x 100: mask = alpha */
+#define ADAS_PANEL_SPRITE_FCWS_PROMPT 1
+#define ADAS_PANEL_SPRITE_FCWS_NORMAL 2
+#define ADAS_PANEL_SPRITE_LEFT 3         /* left_turn.png, 200 x 200: alpha */
+#define ADAS_PANEL_SPRITE_RIGHT 4
+#define ADAS_PANEL_SPRITE_STRAIGHT 5
+#define ADAS_PANEL_SPRITE_WARN 6
+#define ADAS_PANEL_SPRITE_LTA_LEFT 7     /* LTA-left_lanes.png, 300 x 200: mask = channel 2, as the reference tests [:, :, 2] */
+#define ADAS_PANEL_SPRITE_LTA_RIGHT 8
+#define ADAS_PANEL_LATCH_NONE 0          /* ControlPanel.curve_status: None / "Left" / "Right" / "Straight" */
+#define ADAS_PANEL_LATCH_LEFT 1
+#define ADAS_PANEL_LATCH_RIGHT 2
+#define ADAS_PANEL_LATCH_STRAIGHT 3
+typedef struct {
+    double show_ratio;              /* 0.25 */
+    int32_t border;                 /* 10: the bird panel's black border; the collision widget starts 2 * border below H */
+    int32_t signs_w, signs_h;       /* 400 x 365 */
+    int32_t signs_sprite_row;       /* 10: a sign sprite's row offset; its column is signs_w / 2 - sprite_w / 2 */
+    int32_t collision_sprite_row;   /* 50: the FCWS sprite's first row is H + 50 */
+    int32_t collision_sprite_col;   /* 5: its first column is src_w - W - 5 */
+    uint8_t border_color[3];        /* (0, 0, 255) */
+    uint8_t reserved;
+} adas_overlay_panel_params;
+typedef struct {
+    const uint8_t* bgra;            /* host, [h][w][4] u8; NULL: an empty sprite, draws nothing */
+    int32_t w, h;
+} adas_overlay_sprite;
+typedef struct {
+    int32_t sign[2];                /* ADAS_PANEL_SPRITE_* of the first / second if-chain of DisplaySignsPanel in paint order, -1: none */
+    int32_t collision;              /* ADAS_PANEL_SPRITE_FCWS_* or -1 */
+    int32_t latch;                  /* ADAS_PANEL_LATCH_* after the frame */
+    int32_t offset_type, curvature_type, collision_type; /* as read */
+    int32_t reserved;
+} adas_overlay_panel_record;
+int adas_overlay_default_panel_params(adas_overlay_panel_params* p);
+/* Geometry and sprites (copied into one BGRA atlas on the device; the mask channel is fixed by slot).  Checks once that every rectangle
+ * and every sprite placement lies wholly inside the frame (e.g. W + collision_sprite_col >= the FCWS sprites' width, H > 2 * border):
+ * anything else is ADAS_ERR_INVALID with a message naming the panel -- the reference would clip, wrap to the other edge or raise.
+ * Allocates the latches (max_batch of them, all NONE) and the records.  Not inside a stream capture. */
+int adas_overlay_set_panels(adas_overlay* h, const adas_overlay_panel_params* p, const adas_overlay_sprite sprites[ADAS_PANEL_SPRITES]);
+/* The panels `panels` (ADAS_PANEL_*), in place on d_frames_bgr [n_streams * n_frames][src_h][src_w][3] (any alignment); NULL: the handle's
+ * own buffer, what adas_overlay_run just wrote.  Frame b of stream s is frame b * n_streams + s; stream s uses latch s.  SIGNS and
+ * COLLISION read `analysis`' frame rows (after its three updates); BIRD reads d_bird_bgr [frames][bird_h][bird_w][3] (after the bird
+ * stage's discs) and needs a handle created with a bird size.  ADAS_ERR_INVALID, prefixed with the entry's name: unknown panel bits, a
+ * call before adas_overlay_set_panels, n_streams * n_frames > max_batch, a panel without its input. */
+int adas_overlay_run_panels(adas_overlay* h, uint8_t* d_frames_bgr, const adas_analysis* analysis, const uint8_t* d_bird_bgr, int panels,
+                            int n_streams, int n_frames, void* stream);
+/* The same kernels on raw [n_streams * n_frames] int32 arrays (ADAS_OFFSET_* / ADAS_CURVATURE_* / ADAS_COLLISION_*; a value outside its
+ * enum is UNKNOWN).  SIGNS needs the first two, COLLISION the third. */
+int adas_overlay_run_panels_arrays(adas_overlay* h, uint8_t* d_frames_bgr, const int32_t* d_offset_type, const int32_t* d_curvature_type,
+                                   const int32_t* d_collision_type, const uint8_t* d_bird_bgr, int panels, int n_streams, int n_frames,
+                                   void* stream);
+/* Latch `stream_index` back to NONE; -1: all of them.  Synchronises with the last run. */
+int adas_overlay_reset_panels(adas_overlay* h, int stream_index);
+/* The record of frame `frame` of the last panel run.  Synchronises. */
+int adas_overlay_fetch_panel_record(adas_overlay* h, int frame, adas_overlay_panel_record* rec);
+
 /* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
@@ -954,6 +1026,14 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay);
  * step's update; either with micro_batch > 1 is ADAS_ERR_INVALID at the step (the live table holds the last frame only).  Accepts
  * 63 | ADAS_OVERLAY_TRAJECTORIES; bit 64 is refused.  Cached graphs are dropped. */
 int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
+/* The panels (ADAS_PANEL_*) the step paints on the overlay's frames: adas_overlay_run_panels on the overlay handle's own buffer, recorded
+ * directly behind the attached overlay's run and inside the capture (two more launches; 0: none, the step is what it was).  Needs
+ * adas_overlay_set_panels on the attached handle.  BIRD needs a bird view with its warp attached, SIGNS and COLLISION an analysis handle:
+ * a missing one is ADAS_ERR_INVALID at the step, by name.  micro_batch > 1 is allowed (the latch walks a stream's frames in order).
+ * Cached graphs are dropped. */
+int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels);
+/* Kernel nodes of the captured step the last graph-mode step replayed.  ADAS_ERR_INVALID before the first such step. */
+int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */
 int adas_pipeline_step(adas_pipeline* p, const float* d_det_input_nchw, const float* d_lane_input_nchw);
 /* The same step from camera frames: n_streams BGR u8 frames (src_h x src_w x 3, back to back) in HBM; each branch runs its

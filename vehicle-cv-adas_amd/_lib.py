@@ -147,6 +147,26 @@ TRACK_MARK_DTYPE = np.dtype([("kind", "i4"), ("track", "i4"), ("x1", "i4"), ("y1
                              ("thickness", "i4"), ("tip", "i4", (4,)), ("color", "u1", (3,)), ("skipped", "u1")])   # adas_overlay_track_mark
 
 
+PANEL_BIRD, PANEL_SIGNS, PANEL_COLLISION = 1, 2, 4                           # adas_overlay_run_panels' mask (no stage bits: a mask of their own)
+PANELS = {"bird": PANEL_BIRD, "signs": PANEL_SIGNS, "collision": PANEL_COLLISION}
+PANEL_SPRITES = ("fcws_warning", "fcws_prompt", "fcws_normal", "left", "right", "straight", "warn", "lta_left", "lta_right")   # ADAS_PANEL_SPRITE_*
+PANEL_LATCHES = (None, "Left", "Right", "Straight")                          # ADAS_PANEL_LATCH_*: ControlPanel.curve_status
+
+
+class OverlayPanelParams(C.Structure):                                       # adas_overlay_panel_params
+    _fields_ = [("show_ratio", C.c_double), ("border", C.c_int32), ("signs_w", C.c_int32), ("signs_h", C.c_int32), ("signs_sprite_row", C.c_int32),
+                ("collision_sprite_row", C.c_int32), ("collision_sprite_col", C.c_int32), ("border_color", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class OverlaySprite(C.Structure):                                            # adas_overlay_sprite
+    _fields_ = [("bgra", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class OverlayPanelRecord(C.Structure):                                       # adas_overlay_panel_record
+    _fields_ = [("sign", C.c_int32 * 2), ("collision", C.c_int32), ("latch", C.c_int32), ("offset_type", C.c_int32), ("curvature_type", C.c_int32),
+                ("collision_type", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -317,6 +337,14 @@ _SIGS = {
     "adas_overlay_fetch": (C.c_int, [_P, C.c_int, _P]),
     "adas_overlay_device_view": (C.c_int, [_P, C.POINTER(_P)]),
     "adas_overlay_fetch_flags": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "adas_overlay_default_panel_params": (C.c_int, [C.POINTER(OverlayPanelParams)]),
+    "adas_overlay_set_panels": (C.c_int, [_P, C.POINTER(OverlayPanelParams), C.POINTER(OverlaySprite)]),
+    "adas_overlay_run_panels": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_panels_arrays": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_reset_panels": (C.c_int, [_P, C.c_int]),
+    "adas_overlay_fetch_panel_record": (C.c_int, [_P, C.c_int, C.POINTER(OverlayPanelRecord)]),
+    "adas_pipeline_set_overlay_panels": (C.c_int, [_P, C.c_int]),
+    "adas_pipeline_graph_kernels": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "adas_pipeline_attach_overlay": (C.c_int, [_P, _P]),
     "adas_pipeline_set_overlay_stages": (C.c_int, [_P, C.c_int]),
     "adas_warp_create": (C.c_int, [C.POINTER(WarpParams), C.c_int, C.POINTER(_P)]),

@@ -25,6 +25,7 @@ UNITS = [
     ("birdview_kernels.hip", ["-ffp-contract=off"]),
     ("analysis_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_kernels.hip", ["-ffp-contract=off"]),
+    ("overlay_panels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

@@ -83,6 +83,18 @@ struct overlay_handles {
     void* stream;
 };
 int overlay_run_handles(const char* who, int mask, ::adas_overlay* h, const overlay_handles& a);
+// the UI panels (overlay_panels.hip) keep their state -- geometry, sprite atlas, latches, records -- behind one pointer of the overlay handle
+// (overlay_kernels.hip: overlay_panel_slot; adas_overlay_destroy frees it through overlay_panels_free).  overlay_own_frames: the handle's own
+// buffer and how many of its frames some run has written; overlay_note_stream: the stream the fetches drain.  overlay_run_panels: the run of
+// adas_overlay_run_panels under the caller's name (the pipeline's step); overlay_panels_ready: adas_overlay_set_panels has been called
+struct overlay_panels;
+overlay_panels** overlay_panel_slot(::adas_overlay* h);
+void overlay_panels_free(overlay_panels* s);
+int overlay_own_frames(::adas_overlay* h, uint8_t** d_bgr, int* frames_written);
+void overlay_note_stream(::adas_overlay* h, void* stream);
+bool overlay_panels_ready(::adas_overlay* h);
+int overlay_run_panels(const char* who, ::adas_overlay* h, uint8_t* d_frames_bgr, const ::adas_analysis* analysis, const uint8_t* d_bird_bgr, int panels,
+                       int n_streams, int n_frames, void* stream);
 }  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                      \

@@ -844,6 +844,7 @@ struct adas_overlay {
     int* trj_cnt = nullptr;                                 // [max_batch]
     int trj_cap = 0;
     int trj_run_cap = 0, trj_run_frames = 0;                // the last run with the stage: its trk_cap and frames (0: none yet)
+    adas::overlay_panels* panels = nullptr;                 // the UI panels' state (overlay_panels.hip), after adas_overlay_set_panels
     size_t frame_bytes() const { return (size_t)p.src_h * p.src_w * 3; }
 };
 
@@ -853,10 +854,20 @@ int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_
     *src_h = h->p.src_h; *src_w = h->p.src_w; *bird_h = h->p.bird_h; *bird_w = h->p.bird_w; *max_batch = h->max_batch;
     return 1;
 }
+overlay_panels** overlay_panel_slot(::adas_overlay* h) { return &h->panels; }
+void overlay_note_stream(::adas_overlay* h, void* stream) { h->last = (hipStream_t)stream; }
 }  // namespace adas
 
 static int overlay_own_buffer(adas_overlay* h) {
     if (!h->d_dst) ADAS_HIP_TRY(hipMalloc((void**)&h->d_dst, h->frame_bytes() * h->max_batch));
+    return ADAS_OK;
+}
+
+int adas::overlay_own_frames(adas_overlay* h, uint8_t** d_bgr, int* frames_written) {
+    int rc = overlay_own_buffer(h);
+    if (rc) return rc;
+    *d_bgr = h->d_dst;
+    *frames_written = h->dst_frames;
     return ADAS_OK;
 }
 
@@ -1309,6 +1320,7 @@ int adas_overlay_destroy(adas_overlay* h) {
                     (void*)h->rec_cnt, (void*)h->recs, (void*)h->colors[0], (void*)h->colors[1], (void*)h->trj_prims, (void*)h->trj_heads,
                     (void*)h->trj_cnt})
         if (q) (void)hipFree(q);
+    adas::overlay_panels_free(h->panels);
     delete h;
     return ADAS_OK;
 }

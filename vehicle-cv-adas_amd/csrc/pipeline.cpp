@@ -18,6 +18,7 @@ struct adas_pipeline {
     // optional drawing stage behind it (adas_pipeline_attach_overlay): discs, area polygon and alpha blends into the overlay handle's buffer
     adas_overlay* overlay = nullptr;
     int overlay_stages = -1;   // ADAS_OVERLAY_*; -1: everything the attached handles allow
+    int overlay_panels = 0;    // ADAS_PANEL_* painted behind the overlay's run (adas_pipeline_set_overlay_panels); 0: none
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -38,6 +39,7 @@ struct adas_pipeline {
         hipGraphExec_t exec;
     };
     std::vector<Cached> graphs;              // one captured step per distinct key
+    hipGraph_t last_graph = nullptr;         // the capture the last graph-mode step replayed (adas_pipeline_graph_kernels)
     unsigned long long graphs_gen = 0;       // config generation the cached captures were recorded under
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
@@ -201,6 +203,18 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
                                        {p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
                                         const_cast<uint8_t*>(bird_img), stages, NS, B, st});
         if (rc) return rc;
+        if (p->overlay_panels) {   // directly behind the overlay's run, in place on the frames it just wrote
+            const int panels = p->overlay_panels;
+            ADAS_REQUIRE(!(panels & (ADAS_PANEL_SIGNS | ADAS_PANEL_COLLISION)) || p->analysis, ADAS_ERR_INVALID,
+                         "the overlay's %s panel needs an attached analysis handle", (panels & ADAS_PANEL_SIGNS) ? "signs" : "collision");
+            ADAS_REQUIRE(!(panels & ADAS_PANEL_BIRD) || p->bird_warp, ADAS_ERR_INVALID, "the overlay's bird panel needs an attached bird view with its warp");
+            if ((panels & ADAS_PANEL_BIRD) && !bird_img) {   // the bird stage is off: the panel shows the warped image without discs
+                rc = adas_warp_device_view(p->bird_warp, &bird_img);
+                if (rc) return rc;
+            }
+            rc = adas::overlay_run_panels("adas_pipeline_step (overlay panels)", p->overlay, nullptr, p->analysis, bird_img, panels, NS, B, st);
+            if (rc) return rc;
+        }
     }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
     return ADAS_OK;
@@ -212,6 +226,7 @@ static void drop_graphs(adas_pipeline* p) {
         if (g.graph) (void)hipGraphDestroy(g.graph);
     }
     p->graphs.clear();
+    p->last_graph = nullptr;
 }
 
 extern "C" {
@@ -370,6 +385,7 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
     drop_graphs(p);
     p->overlay = overlay;
     p->overlay_stages = -1;
+    p->overlay_panels = 0;
     return ADAS_OK;
 }
 
@@ -397,6 +413,35 @@ int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages) {
         if (rc) return rc;
     }
     p->overlay_stages = stages;
+    return ADAS_OK;
+}
+
+int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels) {
+    ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_panels: no overlay handle attached");
+    ADAS_REQUIRE(panels >= 0 && !(panels & ~(ADAS_PANEL_BIRD | ADAS_PANEL_SIGNS | ADAS_PANEL_COLLISION)), ADAS_ERR_INVALID,
+                 "adas_pipeline_set_overlay_panels: unknown panel bits 0x%x", panels);
+    ADAS_REQUIRE(!panels || adas::overlay_panels_ready(p->overlay), ADAS_ERR_INVALID,
+                 "adas_pipeline_set_overlay_panels: no panels set on the attached overlay handle (call adas_overlay_set_panels first)");
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->overlay_panels = panels;
+    return ADAS_OK;
+}
+
+int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels) {
+    ADAS_REQUIRE(p && n_kernels, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: bad argument");
+    ADAS_REQUIRE(p->last_graph, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: no captured step has been replayed yet");
+    size_t n = 0;
+    ADAS_HIP_TRY(hipGraphGetNodes(p->last_graph, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    if (n) ADAS_HIP_TRY(hipGraphGetNodes(p->last_graph, nodes.data(), &n));
+    int k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        ADAS_HIP_TRY(hipGraphNodeGetType(nodes[i], &t));
+        if (t == hipGraphNodeTypeKernel) ++k;
+    }
+    *n_kernels = k;
     return ADAS_OK;
 }
 
@@ -440,7 +485,10 @@ static int replay_step(adas_pipeline* p, const adas_pipeline::GraphKey& key, con
     }
     hipGraphExec_t exec = nullptr;
     for (auto& g : p->graphs)
-        if (g.key == key) exec = g.exec;
+        if (g.key == key) {
+            exec = g.exec;
+            p->last_graph = g.graph;
+        }
     if (!exec) {
         ADAS_REQUIRE(p->graphs.size() < 64, ADAS_ERR_CAPACITY, "more than 64 distinct input buffers: reuse staging buffers with use_graph");
         adas_pipeline::Cached g{key, nullptr, nullptr};
@@ -467,6 +515,7 @@ static int replay_step(adas_pipeline* p, const adas_pipeline::GraphKey& key, con
         }
         p->graphs.push_back(g);
         exec = g.exec;
+        p->last_graph = g.graph;
     }
     ADAS_HIP_TRY(hipEventRecord(p->ev[0], p->st));
     ADAS_HIP_TRY(hipGraphLaunch(exec, p->st));

@@ -45,7 +45,12 @@ class AdasPipeline:
         overlay["detection_colors"] / overlay["track_colors"] (BGR by class id; none: black).  Also only by name: "trajectories" -- what
         the demo's DrawTrackedOnFrame(frame_show, False) draws per tracked track, behind its box: plot_trajectories' circles over its last 30
         boxes and plot_directions' lock-on rectangle or shadowed arrow, in overlay["track_colors"]; read from the tracker's live state on the
-        device (needs det_model=, track=True and micro_batch 1 like "tracks").  No labels, key points or other text."""
+        device (needs det_model=, track=True and micro_batch 1 like "tracks").  No labels, key points or other text.
+        overlay["panels"]: names out of "bird", "signs", "collision" (or a mask) -- the demo's three UI panels (ControlPanel.Display*Panel
+        without their text), painted in place behind the overlay's stages from the step's analysis rows and bird-view image, with
+        overlay["panel_sprites"] = {name: (h, w, 4) uint8 BGRA} (LaneOverlay.set_panels) and optionally overlay["panel_params"] = dict(...).
+        "bird" needs birdview=dict(image=True), "signs" and "collision" need analysis=.  overlay_image(frame) then holds the panels;
+        self.overlay.panel_record(frame) what was chosen.  The curve_status latch of every stream lives on the device."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
@@ -70,6 +75,15 @@ class AdasPipeline:
                     (L.OVERLAY_TRAJECTORIES, track, "trajectories stage needs det_model= and track=True (the tracked tracks it draws)"),
                     (L.OVERLAY_TRAJECTORIES, self.B <= 1, "trajectories stage needs micro_batch=1: " + live)):
                 if ov_mask is not None and ov_mask & bits and not ok:
+                    raise ValueError("the overlay's " + msg)
+            pn_mask = LaneOverlay.panel_mask(dict(overlay).get("panels") or 0)
+            for bits, ok, msg in (
+                    (L.PANEL_BIRD, has_bird, "bird panel needs birdview=dict(image=True) (the bird-view image it shows)"),
+                    (L.PANEL_SIGNS, analysis is not None, "signs panel needs analysis= (the offset and curvature messages it shows)"),
+                    (L.PANEL_COLLISION, analysis is not None, "collision panel needs analysis= (the collision message it shows)"),
+                    (pn_mask, not (pn_mask & ~7), "panels= holds unknown bits 0x%x" % pn_mask),
+                    (pn_mask, dict(overlay).get("panel_sprites") is not None, "panels= needs panel_sprites= (the BGRA arrays ControlPanel loads)")):
+                if pn_mask & bits and not ok:
                     raise ValueError("the overlay's " + msg)
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
@@ -123,7 +137,8 @@ class AdasPipeline:
             self.analysis = Analysis(n_streams=n_tracks, max_frames=n_streams, **kw)
             L.check(L.lib().adas_pipeline_attach_analysis(self.h, self.analysis.h))
         if overlay is not None:
-            style = {k: v for k, v in dict(overlay).items() if k not in ("stages", "detection_colors", "track_colors")}
+            style = {k: v for k, v in dict(overlay).items() if k not in ("stages", "detection_colors", "track_colors", "panels", "panel_sprites",
+                                                                         "panel_params")}
             self.overlay = LaneOverlay(src_hw, self.warp.dst_hw if self.warp else None, n_streams, **style)
             for key, which in (("detection_colors", "detections"), ("track_colors", "tracks")):
                 if dict(overlay).get(key) is not None:
@@ -131,6 +146,9 @@ class AdasPipeline:
             L.check(L.lib().adas_pipeline_attach_overlay(self.h, self.overlay.h))
             if ov_mask is not None:
                 L.check(L.lib().adas_pipeline_set_overlay_stages(self.h, ov_mask))
+            if pn_mask:
+                self.overlay.set_panels(overlay["panel_sprites"], **dict(dict(overlay).get("panel_params") or {}))
+                L.check(L.lib().adas_pipeline_set_overlay_panels(self.h, pn_mask))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -177,6 +195,12 @@ class AdasPipeline:
         if self.overlay is None:
             raise ValueError("the pipeline was created without overlay=")
         return self.overlay.fetch(frame)
+
+    def graph_kernels(self):
+        """Kernel launches of the captured step the last step replayed (use_graph=True)."""
+        n = C.c_int32()
+        L.check(L.lib().adas_pipeline_graph_kernels(self.h, C.byref(n)))
+        return int(n.value)
 
     def wait_upload(self):
         """Block until the last step_frames_host upload has read its host buffer (then the buffer may be refilled)."""

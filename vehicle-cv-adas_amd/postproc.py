@@ -546,7 +546,8 @@ class LaneOverlay:
     activated tracked track over min_box_area.  The trajectories stage ("trajectories", bit 128; off unless asked for) adds what the demo's
     DrawTrackedOnFrame(frame_show, False) draws per such track, behind its box: plot_trajectories' growing circles over the track's last 30
     boxes and plot_directions' lock-on rectangle or shadowed arrow (csrc/overlay_track_core.h).  Not drawn: text, the label's background
-    rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines and the UI panels.
+    rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines.  The demo's three UI panels are painted by set_panels /
+    run_panels below (a mask of their own, not a stage).
     The pixel rules are csrc/overlay_core.h (modelled on OpenCV 4.5; parity with a real cv2 build is unpinned, lines are not clipped
     before they are walked)."""
     STAGES = L.OVERLAY_STAGES
@@ -679,6 +680,87 @@ class LaneOverlay:
         out = np.zeros(max(1, n.value), L.TRACK_MARK_DTYPE)
         L.check(L.lib().adas_overlay_fetch_track_marks(self.h, int(frame), L.ptr(out), len(out), C.byref(n)))
         return out[:n.value]
+
+    # ---- the demo's three UI panels (adas_overlay_*panel*; rules P1-P6 of csrc/overlay_panel_core.h), in place on drawn frames
+    PANELS = L.PANELS
+    PANEL_PARAMS = ("show_ratio", "border", "signs_w", "signs_h", "signs_sprite_row", "collision_sprite_row", "collision_sprite_col", "border_color")
+
+    @classmethod
+    def panel_mask(cls, names):
+        """An int, or names out of "bird", "signs", "collision"."""
+        if isinstance(names, int):
+            return names
+        names = [names] if isinstance(names, str) else list(names)
+        for n in names:
+            if n not in cls.PANELS:
+                raise ValueError("unknown overlay panel %r (one of %s)" % (n, ", ".join(cls.PANELS)))
+        m = 0
+        for n in names:
+            m |= cls.PANELS[n]
+        return m
+
+    def set_panels(self, sprites, **params):
+        """sprites: {name: (h, w, 4) uint8 BGRA array} by L.PANEL_SPRITES name ("fcws_warning", "fcws_prompt", "fcws_normal", "left", "right",
+        "straight", "warn", "lta_left", "lta_right") -- the arrays ControlPanel.__init__ builds (cv2.imread(..., IMREAD_UNCHANGED) + cv2.resize);
+        a missing or None entry is empty and draws nothing.  params: show_ratio (0.25), border (10), signs_w / signs_h (400 x 365),
+        signs_sprite_row (10), collision_sprite_row (50), collision_sprite_col (5), border_color ((0, 0, 255)).  Raises when a rectangle or a
+        sprite placement would leave the frame.  Resets the latches."""
+        for k in sprites:
+            if k not in L.PANEL_SPRITES:
+                raise ValueError("unknown panel sprite %r (one of %s)" % (k, ", ".join(L.PANEL_SPRITES)))
+        p = L.OverlayPanelParams()
+        L.check(L.lib().adas_overlay_default_panel_params(C.byref(p)))
+        for k, v in params.items():
+            if k not in self.PANEL_PARAMS:
+                raise TypeError("unknown overlay panel parameter %r" % k)
+            if k == "border_color":
+                for j in range(3):
+                    p.border_color[j] = int(v[j])
+            else:
+                setattr(p, k, v)
+        table, keep = (L.OverlaySprite * len(L.PANEL_SPRITES))(), []
+        for i, name in enumerate(L.PANEL_SPRITES):
+            a = sprites.get(name)
+            if a is None:
+                continue
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+                raise ValueError("panel sprite %r must be an (h, w, 4) uint8 BGRA array, got %s %s" % (name, a.dtype, a.shape))
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            table[i].bgra, table[i].w, table[i].h = a.ctypes.data, a.shape[1], a.shape[0]
+        L.check(L.lib().adas_overlay_set_panels(self.h, C.byref(p), table))
+
+    def run_panels(self, frames_ptr=None, analysis=None, bird_ptr=None, panels=None, n_streams=1, n_frames=1, stream=None):
+        """The panels in place on the device frames frames_ptr (None: the handle's own buffer, what run() just wrote), from an Analysis
+        handle's frame rows ("signs", "collision") and the bird-view image bird_ptr ("bird").  Frame b of stream s is frame b * n_streams + s;
+        the curve_status latch of stream s lives on the device and walks its frames in order.  panels=None: every panel whose input is given."""
+        if panels is None:
+            panels = (L.PANEL_BIRD if bird_ptr else 0) | ((L.PANEL_SIGNS | L.PANEL_COLLISION) if analysis else 0)
+        L.check(L.lib().adas_overlay_run_panels(self.h, frames_ptr, analysis.h if analysis else None, bird_ptr, self.panel_mask(panels), int(n_streams),
+                                                int(n_frames), stream))
+
+    def run_panels_arrays(self, frames_ptr=None, offset_type=None, curvature_type=None, collision_type=None, bird_ptr=None, panels=None, n_streams=1,
+                          n_frames=1, stream=None):
+        """The same kernels on raw device pointers to [n_streams * n_frames] int32 types (ADAS_OFFSET_* / ADAS_CURVATURE_* / ADAS_COLLISION_*)."""
+        if panels is None:
+            panels = ((L.PANEL_BIRD if bird_ptr else 0) | (L.PANEL_SIGNS if (offset_type and curvature_type) else 0) |
+                      (L.PANEL_COLLISION if collision_type else 0))
+        L.check(L.lib().adas_overlay_run_panels_arrays(self.h, frames_ptr, offset_type, curvature_type, collision_type, bird_ptr, self.panel_mask(panels),
+                                                       int(n_streams), int(n_frames), stream))
+
+    def reset_panels(self, stream=-1):
+        """curve_status of stream `stream` back to None; -1: every stream."""
+        L.check(L.lib().adas_overlay_reset_panels(self.h, int(stream)))
+
+    def panel_record(self, frame=0):
+        """What the device chose for the frame in the last panel run: {"signs": [names in paint order], "collision": name or None, "latch":
+        None / "Left" / "Right" / "Straight" after the frame, "offset_type", "curvature_type", "collision_type": as read}.  Synchronises."""
+        r = L.OverlayPanelRecord()
+        L.check(L.lib().adas_overlay_fetch_panel_record(self.h, int(frame), C.byref(r)))
+        return {"signs": [L.PANEL_SPRITES[s] for s in r.sign if s >= 0], "collision": L.PANEL_SPRITES[r.collision] if r.collision >= 0 else None,
+                "latch": L.PANEL_LATCHES[r.latch], "offset_type": int(r.offset_type), "curvature_type": int(r.curvature_type),
+                "collision_type": int(r.collision_type)}
 
     def close(self):
         if getattr(self, "h", None):
