@@ -899,6 +899,45 @@ int adas_overlay_reset_panels(adas_overlay* h, int stream_index);
 int adas_overlay_fetch_panel_record(adas_overlay* h, int frame, adas_overlay_panel_record* rec);
 
 /* ===================================================================================
+ * Baseline JPEG on the device: what the demo's loop ends with, vout.write(frame_show) (demo.py:314), as one compressed stream per
+ * frame -- a finished frame leaves the device as a few hundred KB instead of width x height x 3 bytes (adas_overlay_fetch).
+ * Baseline sequential DCT (SOF0), 8 bit, 4:2:0, the Annex K tables of ITU-T T.81 scaled by a quality of 1..100, one restart interval per
+ * MCU row, no APP0; any width and height in 1..65535 (edges are replicated).  The rules J1-J9 are csrc/jpeg_core.h, all of them integer
+ * arithmetic.  Three plain launches (transform and quantise per block; entropy-code per restart segment; lay the segments out per
+ * frame): capturable, no allocation and no host synchronisation in adas_jpeg_run.
+ * =================================================================================== */
+typedef struct adas_jpeg adas_jpeg;
+#define ADAS_JPEG_OVERFLOW 1      /* flags: the frame's stream would not fit the capacity; its length is 0 and no byte of it was written */
+#define ADAS_JPEG_SRC_OVERLAY 0   /* adas_pipeline_attach_jpeg: the attached overlay's own buffer, behind its stages and panels */
+#define ADAS_JPEG_SRC_FRAMES 1    /* the u8 frames adas_pipeline_step_frames* was given */
+typedef struct {
+    int32_t width, height;
+    int32_t quality;              /* 1..100 (90) */
+    int32_t reserved;
+    int64_t capacity;             /* bytes per frame of the handle's stream buffer; 0: width * height * 3 */
+} adas_jpeg_params;
+int adas_jpeg_default_params(adas_jpeg_params* p);
+/* The most bytes a width x height frame can take at any quality: header + blocks * 416 + markers (0 for a size outside 1..65535). */
+int64_t adas_jpeg_bound(int width, int height);
+/* ADAS_ERR_INVALID by name: a size outside 1..65535, a quality outside 1..100, max_batch < 1, a capacity below the 611 header bytes.
+ * Allocates every table, the level arena, the segment arena (worst case: 416 bytes per block) and max_batch streams of `capacity` bytes. */
+int adas_jpeg_create(const adas_jpeg_params* p, int max_batch, adas_jpeg** out);
+int adas_jpeg_destroy(adas_jpeg* h);
+/* New quantisation tables and header bytes from the next run on, at the old addresses (a captured run picks them up).  Synchronises; not
+ * inside a stream capture. */
+int adas_jpeg_set_quality(adas_jpeg* h, int quality);
+/* d_frames_bgr [batch][height][width][3] u8, starting on any byte -> the handle's streams, lengths and flags.  Every byte below a frame's
+ * length is written once, the bytes from there to the capacity are left alone; a frame that would not fit gets length 0 and
+ * ADAS_JPEG_OVERFLOW, the other frames are unaffected.  A frame's bytes depend on its pixels, its size and the quality alone. */
+int adas_jpeg_run(adas_jpeg* h, const uint8_t* d_frames_bgr, int batch, void* stream);
+/* Frame `frame` of the last run -> h_buf, after that run's stream has drained; *n_bytes is its length.  ADAS_ERR_INVALID when h_cap is
+ * below the length (*n_bytes is set all the same) or the frame was not part of the last run. */
+int adas_jpeg_fetch(adas_jpeg* h, int frame, uint8_t* h_buf, int64_t h_cap, int64_t* n_bytes, int32_t* flags);
+int adas_jpeg_fetch_lengths(adas_jpeg* h, int batch, int64_t* n_bytes, int32_t* flags);
+/* The streams on the device: frame f at d_streams + f * stride, d_lengths[f] bytes long. */
+int adas_jpeg_device_view(adas_jpeg* h, const uint8_t** d_streams, const int64_t** d_lengths, int64_t* stride);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1032,6 +1071,14 @@ int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
  * a missing one is ADAS_ERR_INVALID at the step, by name.  micro_batch > 1 is allowed (the latch walks a stream's frames in order).
  * Cached graphs are dropped. */
 int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels);
+/* Optional encoding stage, the step's last launch group on the pipeline's main stream and inside the capture: adas_jpeg_run on all
+ * n_streams x micro_batch frames of the step (frames are independent: any micro_batch).  source ADAS_JPEG_SRC_OVERLAY: the attached
+ * overlay's own buffer, behind its stages and panels (needs adas_pipeline_attach_overlay first); ADAS_JPEG_SRC_FRAMES: the camera frames
+ * the step was given.  Either needs adas_pipeline_step_frames* (the seam-tensor step is then ADAS_ERR_INVALID).  The handle must hold
+ * n_streams x micro_batch frames; its size must be the overlay's (checked here) and the step's camera geometry (checked at the step).
+ * jpeg == NULL detaches.  Cached graphs are dropped.  Without it the step, its graph and its launch count are unchanged.  The handle
+ * stays the caller's; adas_jpeg_fetch after adas_pipeline_sync. */
+int adas_pipeline_attach_jpeg(adas_pipeline* p, adas_jpeg* jpeg, int source);
 /* Kernel nodes of the captured step the last graph-mode step replayed.  ADAS_ERR_INVALID before the first such step. */
 int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */

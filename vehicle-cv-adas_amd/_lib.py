@@ -167,6 +167,14 @@ class OverlayPanelRecord(C.Structure):                                       # a
                 ("collision_type", C.c_int32), ("reserved", C.c_int32)]
 
 
+class JpegParams(C.Structure):                                               # adas_jpeg_params
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64)]
+
+
+JPEG_OVERFLOW = 1                                                            # ADAS_JPEG_OVERFLOW
+JPEG_SOURCES = {"overlay": 0, "frames": 1}                                   # ADAS_JPEG_SRC_*
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -344,6 +352,16 @@ _SIGS = {
     "adas_overlay_reset_panels": (C.c_int, [_P, C.c_int]),
     "adas_overlay_fetch_panel_record": (C.c_int, [_P, C.c_int, C.POINTER(OverlayPanelRecord)]),
     "adas_pipeline_set_overlay_panels": (C.c_int, [_P, C.c_int]),
+    "adas_jpeg_default_params": (C.c_int, [C.POINTER(JpegParams)]),
+    "adas_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
+    "adas_jpeg_create": (C.c_int, [C.POINTER(JpegParams), C.c_int, C.POINTER(_P)]),
+    "adas_jpeg_destroy": (C.c_int, [_P]),
+    "adas_jpeg_set_quality": (C.c_int, [_P, C.c_int]),
+    "adas_jpeg_run": (C.c_int, [_P, _P, C.c_int, _P]),
+    "adas_jpeg_fetch": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "adas_jpeg_fetch_lengths": (C.c_int, [_P, C.c_int, _P, _P]),
+    "adas_jpeg_device_view": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "adas_pipeline_attach_jpeg": (C.c_int, [_P, _P, C.c_int]),
     "adas_pipeline_graph_kernels": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "adas_pipeline_attach_overlay": (C.c_int, [_P, _P]),
     "adas_pipeline_set_overlay_stages": (C.c_int, [_P, C.c_int]),

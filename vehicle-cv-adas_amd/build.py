@@ -26,6 +26,7 @@ UNITS = [
     ("analysis_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_panels.hip", ["-ffp-contract=off"]),
+    ("jpeg_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

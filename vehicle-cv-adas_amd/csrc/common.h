@@ -96,8 +96,13 @@ bool overlay_panels_ready(::adas_overlay* h);
 int overlay_run_panels(const char* who, ::adas_overlay* h, uint8_t* d_frames_bgr, const ::adas_analysis* analysis, const uint8_t* d_bird_bgr, int panels,
                        int n_streams, int n_frames, void* stream);
 }  // namespace adas
+// what adas_pipeline_attach_jpeg checks (jpeg_kernels.hip); zeros for a null handle
+struct adas_jpeg;
+namespace adas {
+void jpeg_geometry_of(const ::adas_jpeg* h, int* width, int* height, int* max_batch);
+}  // namespace adas
 
-#define ADAS_HIP_TRY(expr)                                                      \
+#define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \
         hipError_t e__ = (expr);                                                \
         if (e__ != hipSuccess) return adas::hip_fail(e__, #expr, __FILE__, __LINE__); \

@@ -19,6 +19,9 @@ struct adas_pipeline {
     adas_overlay* overlay = nullptr;
     int overlay_stages = -1;   // ADAS_OVERLAY_*; -1: everything the attached handles allow
     int overlay_panels = 0;    // ADAS_PANEL_* painted behind the overlay's run (adas_pipeline_set_overlay_panels); 0: none
+    // optional encoding stage, the step's last launch group (adas_pipeline_attach_jpeg): one baseline JPEG stream per frame
+    adas_jpeg* jpeg = nullptr;
+    int jpeg_source = ADAS_JPEG_SRC_OVERLAY;
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -215,6 +218,17 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             rc = adas::overlay_run_panels("adas_pipeline_step (overlay panels)", p->overlay, nullptr, p->analysis, bird_img, panels, NS, B, st);
             if (rc) return rc;
         }
+    }
+    if (p->jpeg) {   // the finished frames leave as compressed streams: behind everything that writes them
+        ADAS_REQUIRE(p->fsrc.frames, ADAS_ERR_INVALID, "the JPEG stage needs camera frames: use adas_pipeline_step_frames");
+        const uint8_t* src = p->fsrc.frames;
+        if (p->jpeg_source == ADAS_JPEG_SRC_OVERLAY) {
+            ADAS_REQUIRE(p->overlay, ADAS_ERR_INVALID, "the JPEG stage's overlay source needs an attached overlay handle");
+            rc = adas_overlay_device_view(p->overlay, &src);
+            if (rc) return rc;
+        }
+        rc = adas_jpeg_run(p->jpeg, src, S, st);
+        if (rc) return rc;
     }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
     return ADAS_OK;
@@ -428,6 +442,31 @@ int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels) {
     return ADAS_OK;
 }
 
+int adas_pipeline_attach_jpeg(adas_pipeline* p, adas_jpeg* jpeg, int source) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_jpeg: null pipeline");
+    if (jpeg) {
+        ADAS_REQUIRE(source == ADAS_JPEG_SRC_OVERLAY || source == ADAS_JPEG_SRC_FRAMES, ADAS_ERR_INVALID, "adas_pipeline_attach_jpeg: unknown source %d",
+                     source);
+        ADAS_REQUIRE(source != ADAS_JPEG_SRC_OVERLAY || p->overlay, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_jpeg: the overlay source needs an attached overlay handle (adas_pipeline_attach_overlay first)");
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int jw = 0, jh = 0, jb = 0;
+        adas::jpeg_geometry_of(jpeg, &jw, &jh, &jb);
+        ADAS_REQUIRE(jb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_jpeg: the JPEG handle holds %d frames, a step has %d", jb, frames);
+        if (source == ADAS_JPEG_SRC_OVERLAY) {
+            int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0;
+            (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
+            ADAS_REQUIRE(oh == jh && ow == jw, ADAS_ERR_INVALID,
+                         "adas_pipeline_attach_jpeg: the JPEG handle was created for %dx%d frames, the attached overlay draws %dx%d", jw, jh, ow, oh);
+        }
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->jpeg = jpeg;
+    p->jpeg_source = source;
+    return ADAS_OK;
+}
+
 int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels) {
     ADAS_REQUIRE(p && n_kernels, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: bad argument");
     ADAS_REQUIRE(p->last_graph, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: no captured step has been replayed yet");
@@ -530,6 +569,7 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
     ADAS_REQUIRE(!p->d.lane || d_lane, ADAS_ERR_INVALID, "lane input missing");
     ADAS_REQUIRE(!p->bird_warp, ADAS_ERR_INVALID, "a bird-view image warp is attached: seam tensors carry no frame to warp, use adas_pipeline_step_frames");
     ADAS_REQUIRE(!p->overlay, ADAS_ERR_INVALID, "an overlay is attached: seam tensors carry no frame to draw on, use adas_pipeline_step_frames");
+    ADAS_REQUIRE(!p->jpeg, ADAS_ERR_INVALID, "a JPEG stage is attached: seam tensors carry no frame to encode, use adas_pipeline_step_frames");
     if (!(p->d.use_graph & 1)) {
         p->timed = true;
         return record_step(p, d_det, d_lane, true);
@@ -551,6 +591,12 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
         (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
         ADAS_REQUIRE(oh == src_h && ow == src_w, ADAS_ERR_INVALID, "the attached overlay handle was created for %dx%d frames, the step has %dx%d", oh, ow, src_h,
                      src_w);
+    }
+    if (p->jpeg) {   // and the JPEG stage
+        int jw = 0, jh = 0, jb = 0;
+        adas::jpeg_geometry_of(p->jpeg, &jw, &jh, &jb);
+        ADAS_REQUIRE(jh == src_h && jw == src_w, ADAS_ERR_INVALID, "the attached JPEG handle was created for %dx%d frames, the step has %dx%d", jw, jh, src_w,
+                     src_h);
     }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
     if (!p->det_in && !p->lane_in) {

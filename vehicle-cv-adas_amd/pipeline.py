@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -50,14 +50,31 @@ class AdasPipeline:
         without their text), painted in place behind the overlay's stages from the step's analysis rows and bird-view image, with
         overlay["panel_sprites"] = {name: (h, w, 4) uint8 BGRA} (LaneOverlay.set_panels) and optionally overlay["panel_params"] = dict(...).
         "bird" needs birdview=dict(image=True), "signs" and "collision" need analysis=.  overlay_image(frame) then holds the panels;
-        self.overlay.panel_record(frame) what was chosen.  The curve_status latch of every stream lives on the device."""
+        self.overlay.panel_record(frame) what was chosen.  The curve_status latch of every stream lives on the device.
+        jpeg: None, or dict(quality=90, source="overlay" | "frames", capacity=None): every frame of the step as a baseline JPEG stream
+        (postproc.JpegEncoder), the step's last launch group -- what the demo's vout.write(frame_show) gets, without the uncompressed frame
+        leaving the device: jpeg(frame) -> bytes after sync(), jpeg_lengths() -> (lengths, flags).  source="overlay" (the default) encodes
+        the drawn frames, behind the overlay's stages and panels, and needs overlay=; source="frames" encodes the camera frames the step was
+        given.  Either needs step_frames / step_frames_host.  capacity: bytes per frame (None: height * width * 3); a frame that would not
+        fit comes back as b"" with JpegEncoder.OVERFLOW in its flag.  Any micro_batch: frames are independent."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
-        self.overlay = None
+        self.overlay = self.jpeg_encoder = None
+        if jpeg is not None:
+            unknown = set(dict(jpeg)) - {"quality", "source", "capacity"}
+            if unknown:
+                raise ValueError("jpeg= holds unknown keys %s (quality, source, capacity)" % sorted(unknown))
+            jpeg_source = dict(jpeg).get("source", "overlay")
+            if jpeg_source not in L.JPEG_SOURCES:
+                raise ValueError("jpeg= source %r is neither \"overlay\" nor \"frames\"" % (jpeg_source,))
+            if jpeg_source == "overlay" and overlay is None:
+                raise ValueError("jpeg= with source=\"overlay\" needs overlay= (the drawn frames it encodes); source=\"frames\" encodes the camera frames")
+            if not 1 <= int(dict(jpeg).get("quality", 90)) <= 100:
+                raise ValueError("jpeg= quality %r is outside 1..100" % (dict(jpeg).get("quality"),))
         if overlay is not None:
             if geometry is None or not lane_model:
                 raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
@@ -149,6 +166,9 @@ class AdasPipeline:
             if pn_mask:
                 self.overlay.set_panels(overlay["panel_sprites"], **dict(dict(overlay).get("panel_params") or {}))
                 L.check(L.lib().adas_pipeline_set_overlay_panels(self.h, pn_mask))
+        if jpeg is not None:
+            self.jpeg_encoder = JpegEncoder(src_hw[1], src_hw[0], int(dict(jpeg).get("quality", 90)), n_streams, dict(jpeg).get("capacity"))
+            L.check(L.lib().adas_pipeline_attach_jpeg(self.h, self.jpeg_encoder.h, L.JPEG_SOURCES[jpeg_source]))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -196,6 +216,18 @@ class AdasPipeline:
             raise ValueError("the pipeline was created without overlay=")
         return self.overlay.fetch(frame)
 
+    def jpeg(self, frame=0):
+        """The JPEG stream of frame `frame` of the last step_frames (after sync()) as bytes: write it out, or append it to a raw MJPEG file."""
+        if self.jpeg_encoder is None:
+            raise ValueError("the pipeline was created without jpeg=")
+        return self.jpeg_encoder.fetch(frame)
+
+    def jpeg_lengths(self):
+        """(lengths [frames] int64, flags [frames] int32) of the last step's streams (after sync()); flag JpegEncoder.OVERFLOW: length 0."""
+        if self.jpeg_encoder is None:
+            raise ValueError("the pipeline was created without jpeg=")
+        return self.jpeg_encoder.lengths(self.S * self.B)
+
     def graph_kernels(self):
         """Kernel launches of the captured step the last step replayed (use_graph=True)."""
         n = C.c_int32()
@@ -225,7 +257,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

@@ -770,6 +770,63 @@ class LaneOverlay:
     __del__ = close
 
 
+class JpegEncoder:
+    """Baseline JPEG of BGR u8 frames that sit in HBM (adas_jpeg_*): what the demo's vout.write(frame_show) gets, as one compressed stream per
+    frame -- 4:2:0, the standard's Annex K tables scaled by `quality` (1..100), one restart interval per MCU row, any frame size.  The rules
+    J1-J9 are csrc/jpeg_core.h; any JPEG decoder reads the streams, and concatenated they are a raw MJPEG file.
+    capacity: bytes per frame of the stream buffer (None: width * height * 3; JpegEncoder.bound(width, height) always fits).  A frame whose
+    stream would not fit comes back as b"" with the overflow flag in lengths(); the other frames of the run are unaffected."""
+    OVERFLOW = L.JPEG_OVERFLOW
+
+    @staticmethod
+    def bound(width, height):
+        """The most bytes a frame of this size can take at any quality."""
+        return int(L.lib().adas_jpeg_bound(int(width), int(height)))
+
+    def __init__(self, width, height, quality=90, max_batch=1, capacity=None):
+        self.p = L.JpegParams(int(width), int(height), int(quality), 0, int(capacity or 0))
+        self.width, self.height, self.max_batch = int(width), int(height), int(max_batch)
+        self.capacity = int(capacity) if capacity else self.width * self.height * 3
+        h = C.c_void_p()
+        L.check(L.lib().adas_jpeg_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        self._host = L.PinnedBuffer((self.capacity,))      # page-locked: a fetch is one small copy for the length and one for the bytes
+
+    def set_quality(self, quality):
+        """From the next run on; a captured run picks the new tables up.  Synchronises."""
+        L.check(L.lib().adas_jpeg_set_quality(self.h, int(quality)))
+
+    def run(self, d_frames, batch=1, stream=None):
+        """d_frames: device pointer of [batch][height][width][3] u8, any alignment.  Asynchronous on `stream`."""
+        L.check(L.lib().adas_jpeg_run(self.h, d_frames, int(batch), stream))
+
+    def fetch(self, frame=0):
+        """The stream of frame `frame` of the last run as bytes (b"" for a frame that overflowed).  Waits for that run."""
+        n = C.c_int64()
+        L.check(L.lib().adas_jpeg_fetch(self.h, int(frame), self._host.ptr, self.capacity, C.byref(n), None))
+        return self._host.array[:n.value].tobytes()
+
+    def lengths(self, batch=1):
+        """(lengths [batch] int64, flags [batch] int32) of the last run.  Waits for that run."""
+        n, f = np.zeros(int(batch), np.int64), np.zeros(int(batch), np.int32)
+        L.check(L.lib().adas_jpeg_fetch_lengths(self.h, int(batch), L.ptr(n), L.ptr(f)))
+        return n, f
+
+    def device_view(self):
+        """(device pointer of the streams, device pointer of the int64 lengths, bytes between two frames' streams)."""
+        d, n, s = C.c_void_p(), C.c_void_p(), C.c_int64()
+        L.check(L.lib().adas_jpeg_device_view(self.h, C.byref(d), C.byref(n), C.byref(s)))
+        return d.value, n.value, int(s.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_jpeg_destroy(self.h)
+            self.h = None
+            self._host.free()
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
