@@ -153,7 +153,12 @@ def _dwconv(x, W, name, s=1, act="silu"):
     w = _round(_t(W, name + ".weight"))
     k = w.shape[-1]
     y = F.conv2d(x, w, _t(W, name + ".bias"), stride=s, padding=k // 2, groups=x.shape[1])
-    return _round(F.silu(y)) if act == "silu" else _round(y)
+    assert act in ("silu", "relu", "leaky", None), act     # (an activation this function does not know is never dropped silently)
+    if act == "silu":
+        return _round(F.silu(y))
+    if act == "relu":
+        return _round(F.relu(y))
+    return _round(F.leaky_relu(y, 0.1)) if act == "leaky" else _round(y)
 
 
 def _scdown(x, W, name, s=2):

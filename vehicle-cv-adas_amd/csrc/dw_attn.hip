@@ -1,6 +1,6 @@
 // dw_attn.hip -- the two YOLOv10 operators the v8-family kernels do not cover (the reference's shipped default detector is
 // yolov10n: demo.py:24-30; its head is decoded as a v8-layout tensor, yoloDetector.py:114,121):
-//   dwconv     depth-wise k x k convolution (k = 3, 5 or 7, stride 1 or 2, groups = channels) + bias [+ SiLU] [+ residual add]:
+//   dwconv     depth-wise k x k convolution (k = 3, 5 or 7, stride 1 or 2, groups = channels) + bias [+ SiLU | ReLU | LeakyReLU(0.1)] [+ residual add]:
 //              SCDown.cv2, CIB's three depth-wise layers (the fused RepVGGDW is one 7x7), v10Detect's class-branch 3x3s and
 //              the positional encoding of PSA's attention.  HBM-bound streaming: thread = (output pixel, 8-channel group), one
 //              16-byte (16-bit modes) load per tap from a window that lives in L1/L2, fp32 weights [tap][C], fp32 accumulate.
@@ -90,6 +90,9 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwDev d) {
         } else if (d.act == ACT_RELU) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = fmaxf(acc[e], 0.0f);
+        } else if (d.act == ACT_LEAKY) {   // LeakyReLU(0.1), as the conv kernels' epilogues apply it
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaxf(acc[e], 0.1f * acc[e]);
         }
         if (d.has_res) {   // x + block(x): added after the activation (RES_AFTER_ACT)
             float rv[8];
@@ -169,6 +172,9 @@ __global__ __launch_bounds__(256) void dwconv_strip_kernel(DwDev d) {
             } else if (d.act == ACT_RELU) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[t][e] = fmaxf(acc[t][e], 0.0f);
+            } else if (d.act == ACT_LEAKY) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[t][e] = fmaxf(acc[t][e], 0.1f * acc[t][e]);
             }
             const size_t pix = ((size_t)b * d.Ho + oy) * d.Wo + ox;
             if (d.has_res) {
