@@ -159,6 +159,10 @@ int adas_debug_ml_plan(const adas_ml_layer_desc* layers, int n_layers, int batch
  * adas_engine_layer_kernel gives the layer in an engine whose max_batch is `batch` (no device: tests/test_conv_route_cpu.py).  `kernel`
  * only tells 1x1 (4) from 3x3 (any other value); the kernel class comes from the plan. */
 int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precision, char* name, int name_cap);
+/* Which body of conv_h8x3_kernel such a layer runs at `batch` frames in ADAS_PREC_FP16X3: 1 the one-pass body (each 32-channel chunk
+ * streamed once, hi and lo together), 0 the two-pass body or another kernel altogether (adas_debug_conv_route names it), -1 a bad
+ * argument.  Decided by the tile plan's window size and ADAS_H8X_ONEPASS (read once); no device. */
+int adas_debug_h8x3_onepass(const adas_ml_layer_desc* layer, int batch);
 /* The load-time plan of an engine: what adas_engine_create decided before it touched a weight.  One row of ADAS_PLAN_COLS int64 per
  * layer (rows[layer * ADAS_PLAN_COLS + column]); a link column holds a layer index or -1, an offset column bytes into the weight arena:
  *    0 kernel (weight packing, CONV_* of csrc/kernels.h)   1 skip (launches nothing: fused into a neighbour)

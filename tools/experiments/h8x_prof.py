@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""scratch (round 6): per-phase cycle breakdown of conv_h8x3_kernel (the split precision's 3x3 stride-1 conv).  Needs
+"""scratch (round 6): per-phase cycle breakdown of conv_h8x3_kernel (the split precision's 3x3 stride-1 conv; both bodies).  Needs
 ADAS_LIB=<a library built with ADAS_BUILD_TAG=h8xprof ADAS_CFLAGS=-DADAS_H8X_PROF python vehicle-cv-adas_amd/build.py>:
    ADAS_LIB=vehicle-cv-adas_amd/_scratch/libadas_hip_h8xprof.so python tools/experiments/h8x_prof.py --hw 80 400 --cin 64 --cout 64 --batch 64 [--res]"""
 import argparse, ctypes as C, importlib, os, sys, tempfile
@@ -42,6 +42,13 @@ fl = 2.0 * a.batch * H * W * a.cout * 9 * a.cin
 print(f"{H}x{W}x{a.cin}->{a.cout} batch {a.batch}{' +res' if a.res else ''}: {ms*1e3:.1f} us, {fl/ms/1e9:.0f} TFLOP/s of conv work, {3*fl/ms/1e9:.0f} of MFMA work  [{e.layer_kernel(li, a.batch)}]")
 if prof:
     names = ["loop top / item set-up", "H half-chunks (not last)", "L half-chunks (not last)", "last half-chunk (L)", "epilogue: vmcnt(0) drain", "epilogue: compute + stores"]
+    # the one-pass body (ADAS_H8X_ONEPASS, default on where the plan's windows fit) stamps whole chunks: 9 taps of 24 MFMAs per wave
+    res_view = L.MlView(0x100000, a.cin, 0, a.cin, H, W) if use_res else L.MlView()
+    desc = L.MlLayerDesc(1, 1, act, M.RES_BEFORE_ACT if use_res else M.RES_NONE, 0, 0, L.MlView(0x100000, a.cin, 0, a.cin, H, W),
+                         L.MlView(0x200000, a.cout, 0, a.cout, H, W), res_view, L.MlView())
+    if L.lib().adas_debug_h8x3_onepass(C.byref(desc), a.batch) == 1:
+        print(" one-pass body")
+        names[1:4] = ["chunks (not last)", "(unused)", "last chunk"]
     for gq in (0, 1):
         n = out[7 + 16 * gq] / 5.0
         tot = sum(out[i + 16 * gq] for i in range(16) if i != 7) / 5.0

@@ -241,6 +241,7 @@ _SIGS = {
     "adas_debug_ml_plan": (C.c_int, [C.POINTER(MlLayerDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
                                      C.c_int, C.POINTER(C.c_int32)]),
     "adas_debug_conv_route": (C.c_int, [C.POINTER(MlLayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "adas_debug_h8x3_onepass": (C.c_int, [C.POINTER(MlLayerDesc), C.c_int]),
     "adas_engine_plan": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "adas_debug_engine_plan": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "adas_engine_schedule": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -420,6 +420,15 @@ int adas_debug_conv_route(const adas_ml_layer_desc* layer, int batch, int precis
     return ADAS_OK;
 }
 
+int adas_debug_h8x3_onepass(const adas_ml_layer_desc* layer, int batch) {
+    if (!layer || batch <= 0) return -1;
+    ConvArgs a = conv_args_of_desc(*layer, batch, PREC_X3);
+    const ConvPlan pl = plan_conv(PREC_X3, a.kh, a.kw, a.stride, a.pad, a.max_n, a.res_mode, a.in, a.out);
+    a.kpad = pl.kpad;
+    if (wants_x3h8_packing(PREC_X3, pl.kernel, a.kh, a.kw, a.stride, a.pad, a.res_mode, a.in, a.out)) a.wgt_h8x3 = (const void*)(uintptr_t)0x1000;
+    return (conv_route(a) == ConvRoute::H8X3 && halo8_x3_onepass(a)) ? 1 : 0;
+}
+
 int adas_engine_precision(const adas_engine* e) { return e ? e->prec : -1; }
 int adas_engine_model_io_half(const adas_engine* e) { return e ? (int)((e->hdr.in_cpad >> 16) & 1u) : 0; }
 

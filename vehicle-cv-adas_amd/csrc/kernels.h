@@ -137,6 +137,7 @@ bool halo8_x3_applicable(const ConvArgs& a);
 size_t halo8_x3_weight_bytes(int cout, int cin);
 hipError_t launch_pack_weights_h8x3(const float* src, void* dst, int cout, int cin, hipStream_t st);   // src fp32 [cout][9][cin]
 hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st);
+bool halo8_x3_onepass(const ConvArgs& a);   // an H8X3 launch of `a` runs the one-pass body (plan, window pieces per wave, ADAS_H8X_ONEPASS); false off that route
 // returns hipSuccess or the launch error
 hipError_t launch_conv(const ConvArgs& a, hipStream_t st);
 // the kernel instantiation conv_route(a) stands for; stem: the layer is the engine's fused first layer (CONV_STEM), which has no route
