@@ -942,6 +942,49 @@ int adas_jpeg_fetch_lengths(adas_jpeg* h, int batch, int64_t* n_bytes, int32_t* 
 int adas_jpeg_device_view(adas_jpeg* h, const uint8_t** d_streams, const int64_t** d_lengths, int64_t* stride);
 
 /* ===================================================================================
+ * Baseline JPEG decoding on the device: what the demo's loop starts with, cap.read() (demo.py:261), for a camera or file that delivers
+ * MJPEG -- a frame crosses the bus as a few hundred KB instead of width x height x 3 bytes and is decoded where the step reads it.
+ * Baseline sequential DCT (SOF0), 8 bit, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, the stream's own tables, any restart interval (a restart
+ * segment is the unit of parallelism: a stream without restart markers decodes on one lane).  The rules D1-D9 are csrc/jpegdec_core.h, all
+ * of them integer arithmetic.  A memset and five plain launches (header per frame; restart markers per frame; entropy-decode per
+ * segment; inverse transform per block; upsample and convert per 16 output bytes): capturable, no allocation and no host
+ * synchronisation in adas_jpegdec_run.
+ * Stream CONTENT never produces an error code: every frame gets a flag word, and a frame flagged UNSUPPORTED, FORMAT or SIZE has every
+ * pixel 0; the other frames of the batch are unaffected.  For any bytes whatever the decoder reads only the words that hold the
+ * stream's bytes and writes only its own arenas and the destination frame.
+ * =================================================================================== */
+typedef struct adas_jpegdec adas_jpegdec;
+#define ADAS_JPEGDEC_UNSUPPORTED 1   /* a valid JPEG outside the accepted kind: progressive, 12 bit, four components, other sampling, ... */
+#define ADAS_JPEGDEC_FORMAT 2        /* not a JPEG stream, a damaged header, a missing table, a length of 0 or above the capacity */
+#define ADAS_JPEGDEC_SIZE 4          /* the stream's width or height differ from the handle's */
+#define ADAS_JPEGDEC_CORRUPT 8       /* an error in the entropy data: the blocks from there to the segment's end are zero coefficients */
+typedef struct {
+    int32_t width, height;
+    int32_t reserved[2];
+    int64_t capacity;             /* most bytes per stream; 0: adas_jpeg_bound(width, height) */
+} adas_jpegdec_params;
+int adas_jpegdec_default_params(adas_jpegdec_params* p);
+/* ADAS_ERR_INVALID by name: a size outside 1..65535, max_batch < 1, a capacity outside 1..2^31-1.  Allocates every arena, max_batch
+ * frames and the two staging buffers of adas_jpegdec_run_host, pinned on the host and mirrored on the device, max_batch x capacity bytes
+ * each: with the default capacity (9 MB per 1280x720 stream) that is the handle's largest part, so give the capacity the source needs. */
+int adas_jpegdec_create(const adas_jpegdec_params* p, int max_batch, adas_jpegdec** out);
+int adas_jpegdec_destroy(adas_jpegdec* h);
+/* Streams on the device: frame f at d_streams + f * stride, d_lengths[f] bytes, starting on any byte (adas_jpeg_device_view's triple fits).
+ * d_dst_bgr [batch][height][width][3] u8, any alignment; NULL: the handle's own frames.  Every byte of the batch's frames is written,
+ * nothing behind them. */
+int adas_jpegdec_run(adas_jpegdec* h, const uint8_t* d_streams, const int64_t* d_lengths, int64_t stride, int batch, uint8_t* d_dst_bgr, void* stream);
+/* Streams on the host: packed into one of two pinned staging buffers of the handle, copied asynchronously on `stream`, then the run
+ * above.  A length above the capacity flags that frame FORMAT and copies nothing of it.  The host bytes are free again on return.  Calls may use
+ * different streams: a staging buffer is refilled only behind the run that last read it.  (adas_pipeline_step_jpeg_host shares the two
+ * buffers: do not mix it with calls of this entry point on the attached handle.) */
+int adas_jpegdec_run_host(adas_jpegdec* h, const uint8_t* const* h_streams, const int64_t* h_lengths, int batch, uint8_t* d_dst_bgr, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_bgr [height][width][3], after the last run's stream has drained.  ADAS_ERR_INVALID for a
+ * frame the last run did not write there. */
+int adas_jpegdec_fetch(adas_jpegdec* h, int frame, uint8_t* h_bgr);
+int adas_jpegdec_fetch_flags(adas_jpegdec* h, int batch, int32_t* flags);
+int adas_jpegdec_device_view(adas_jpegdec* h, const uint8_t** d_frames_bgr, const int32_t** d_flags);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1100,6 +1143,17 @@ int adas_pipeline_step_frames_host(adas_pipeline* p, const uint8_t* h_frames_bgr
 /* The call above returns when the upload is ENQUEUED: the host buffer must not be rewritten before the copy has read it.  This waits
  * for exactly that (the copy stream only, not the compute): call it before refilling a host buffer that the last step was given. */
 int adas_pipeline_wait_upload(adas_pipeline* p);
+/* Optional decoding stage in FRONT of the step, outside the capture: the handle adas_pipeline_step_jpeg_host decodes with.  It must hold
+ * n_streams x micro_batch frames; its size is the step's camera geometry and must be that of an attached warp, overlay or JPEG stage
+ * (checked at the step).  jpegdec == NULL detaches.  Nothing inside the captured step changes; the handle stays the caller's. */
+int adas_pipeline_attach_jpegdec(adas_pipeline* p, adas_jpegdec* jpegdec);
+/* The step from COMPRESSED host frames, n_streams x micro_batch baseline JPEG streams: their bytes are packed into one of the decoder's
+ * two staging buffers and copied on the pipeline's copy stream while the previous step still computes (the double buffering of
+ * adas_pipeline_step_frames_host, on a few hundred KB per frame), decoded on the main stream into the decoder's own frames, and those go
+ * through adas_pipeline_step_frames: one address, so one captured step.  The host bytes are free again on return;
+ * adas_pipeline_wait_upload keeps its meaning.  Each frame's flag word: adas_jpegdec_fetch_flags on the attached handle after
+ * adas_pipeline_sync; a rejected frame is a black frame to the step. */
+int adas_pipeline_step_jpeg_host(adas_pipeline* p, const uint8_t* const* h_streams, const int64_t* h_lengths, double lane_crop_ratio);
 int adas_pipeline_sync(adas_pipeline* p);
 /* Device time of the last `n` steps' sections in ms (hipEvents on the pipeline stream):
  * [0] detector net, [1] yolo post, [2] lane net, [3] lane decode, [4] tracker, [5] whole step. */

@@ -6,6 +6,7 @@ No window, no video codec: frames come from a seeded synthetic 1280x720 clip (mo
 .npy file of uint8 BGR frames (N, H, W, 3); one summary line per frame.
 
     python tools/demo_headless.py [--frames 30] [--det yolov8n.onnx|.hipm] [--det-type yolov8|efficientdet] [--lane culane_res18.onnx|.hipm] [--video clip.npy]
+                                  [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg]
 
 Without model paths, seeded random-weight models are built (their detections are noise: the point is the data flow)."""
 import argparse, importlib, os, sys, tempfile, time
@@ -48,6 +49,10 @@ def main():
                     help="demo.py:314 (vout.write): encode every frame on the device (postproc.JpegEncoder, quality 90) from the staged frame in HBM "
                          "and append its stream to PATH -- concatenated JPEGs are a raw MJPEG file.  This loop draws nothing, so the frames are "
                          "the camera's; the fused pipeline's jpeg= encodes the drawn overlay")
+    ap.add_argument("--from-mjpeg", default=None, metavar="PATH",
+                    help="demo.py:261 (cap.read) for a camera or file that delivers MJPEG: the inverse of --mjpeg.  PATH is a raw MJPEG file "
+                         "(concatenated baseline JPEG streams); every frame is decoded on the device (postproc.JpegDecoder) instead of coming "
+                         "from the synthetic clip.  A stream the decoder rejects is reported and shown to the loop as a black frame")
     a = ap.parse_args()
     work = tempfile.mkdtemp(prefix="adas_demo_")
     effdet = a.det_type == "efficientdet"
@@ -67,8 +72,25 @@ def main():
     else:
         objectDetector = D.YoloDetector(model_path=det_path, model_type=D.ObjectModelType.YOLOV8, classes_path=classes, box_score=0.4, box_nms_iou=0.45)
     frames = np.load(a.video) if a.video else None
-    first = frames[0] if frames is not None else next(synthetic_clip(1))
-    height, width = first.shape[:2]
+    decoder = None
+    if a.from_mjpeg:
+        streams = PP.split_mjpeg(open(a.from_mjpeg, "rb").read())
+        if not streams or streams[0][1] is None:
+            raise SystemExit("%s holds no JPEG stream with a frame header" % a.from_mjpeg)
+        width, height = streams[0][1]
+        decoder = PP.JpegDecoder(width, height, capacity=max(len(s) for s, _ in streams))
+
+        def decoded():
+            for k, (s, _) in enumerate(streams):
+                decoder.run_host([s])
+                flag = int(decoder.flags(1)[0])
+                if flag:
+                    print("stream %d of %s: decoder flags 0x%x" % (k, a.from_mjpeg, flag))
+                yield decoder.image(0)
+        frames = decoded()
+    else:
+        first = frames[0] if frames is not None else next(synthetic_clip(1))
+        height, width = first.shape[:2]
     transformView = A.PerspectiveTransformation((width, height))
     laneDetector.enable_device_geometry(transformView)
     distanceDetector = A.SingleCamDistanceMeasure()
@@ -124,6 +146,8 @@ def main():
                                                                                             n * height * width * 3 / max(written, 1)))
     print("%d frames in %.2f s (%.1f frames/s, single stream, host frames: upload + 2 nets + post-processing + fetch per frame)" % (n, dt, n / dt))
     transformView.close(); objectDetector.close(); laneDetector.close(); objectTracker.close()
+    if decoder is not None:
+        decoder.close()
     return n
 
 

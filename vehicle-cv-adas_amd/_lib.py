@@ -175,6 +175,13 @@ JPEG_OVERFLOW = 1                                                            # A
 JPEG_SOURCES = {"overlay": 0, "frames": 1}                                   # ADAS_JPEG_SRC_*
 
 
+class JpegDecParams(C.Structure):                                            # adas_jpegdec_params
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32 * 2), ("capacity", C.c_int64)]
+
+
+JPEGDEC_UNSUPPORTED, JPEGDEC_FORMAT, JPEGDEC_SIZE, JPEGDEC_CORRUPT = 1, 2, 4, 8   # ADAS_JPEGDEC_*
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -363,6 +370,16 @@ _SIGS = {
     "adas_jpeg_fetch_lengths": (C.c_int, [_P, C.c_int, _P, _P]),
     "adas_jpeg_device_view": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     "adas_pipeline_attach_jpeg": (C.c_int, [_P, _P, C.c_int]),
+    "adas_jpegdec_default_params": (C.c_int, [C.POINTER(JpegDecParams)]),
+    "adas_jpegdec_create": (C.c_int, [C.POINTER(JpegDecParams), C.c_int, C.POINTER(_P)]),
+    "adas_jpegdec_destroy": (C.c_int, [_P]),
+    "adas_jpegdec_run": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "adas_jpegdec_run_host": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    "adas_jpegdec_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_jpegdec_fetch_flags": (C.c_int, [_P, C.c_int, _P]),
+    "adas_jpegdec_device_view": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "adas_pipeline_attach_jpegdec": (C.c_int, [_P, _P]),
+    "adas_pipeline_step_jpeg_host": (C.c_int, [_P, _P, _P, C.c_double]),
     "adas_pipeline_graph_kernels": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "adas_pipeline_attach_overlay": (C.c_int, [_P, _P]),
     "adas_pipeline_set_overlay_stages": (C.c_int, [_P, C.c_int]),

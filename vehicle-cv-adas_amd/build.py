@@ -27,6 +27,7 @@ UNITS = [
     ("overlay_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_panels.hip", ["-ffp-contract=off"]),
     ("jpeg_kernels.hip", []),
+    ("jpegdec_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

@@ -101,6 +101,17 @@ struct adas_jpeg;
 namespace adas {
 void jpeg_geometry_of(const ::adas_jpeg* h, int* width, int* height, int* max_batch);
 }  // namespace adas
+// what adas_pipeline_attach_jpegdec checks and adas_pipeline_step_jpeg_host drives (jpegdec_kernels.hip): the handle's geometry (zeros for a
+// null handle) and own frame buffer; jpegdec_stage_host packs host streams into the handle's next staging slot and queues the copy on
+// copy_stream, jpegdec_run_slot decodes that slot on `stream` (the two halves of adas_jpegdec_run_host)
+struct adas_jpegdec;
+namespace adas {
+void jpegdec_geometry_of(const ::adas_jpegdec* h, int* width, int* height, int* max_batch);
+uint8_t* jpegdec_frames(::adas_jpegdec* h);
+int jpegdec_next_slot(const ::adas_jpegdec* h);   // the staging slot (0 or 1) the next jpegdec_stage_host packs into
+int jpegdec_stage_host(::adas_jpegdec* h, const uint8_t* const* h_streams, const int64_t* h_lengths, int batch, void* copy_stream, int* slot);
+int jpegdec_run_slot(::adas_jpegdec* h, int slot, int batch, uint8_t* d_dst_bgr, void* stream);
+}  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \

@@ -63,6 +63,10 @@ struct adas_pipeline {
     size_t host_stage_bytes = 0;
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
     unsigned long long host_steps = 0;
+    // step_jpeg_host: the decoder in front of the step (adas_pipeline_attach_jpegdec); its two staging slots are filled by the copy stream
+    adas_jpegdec* jpegdec = nullptr;
+    hipEvent_t ev_jcopied[2] = {nullptr, nullptr}, ev_jconsumed[2] = {nullptr, nullptr};
+    bool jslot_used[2] = {false, false};
 };
 
 using namespace adas;
@@ -507,6 +511,8 @@ int adas_pipeline_destroy(adas_pipeline* p) {
         if (p->host_stage[k]) (void)hipFree(p->host_stage[k]);
         if (p->ev_copied[k]) (void)hipEventDestroy(p->ev_copied[k]);
         if (p->ev_consumed[k]) (void)hipEventDestroy(p->ev_consumed[k]);
+        if (p->ev_jcopied[k]) (void)hipEventDestroy(p->ev_jcopied[k]);
+        if (p->ev_jconsumed[k]) (void)hipEventDestroy(p->ev_jconsumed[k]);
     }
     if (p->st_copy) (void)hipStreamDestroy(p->st_copy);
     delete p;
@@ -628,8 +634,8 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
 int adas_pipeline_step_frames_host(adas_pipeline* p, const uint8_t* h_frames_bgr, int src_h, int src_w, double lane_crop_ratio) {
     ADAS_REQUIRE(p && h_frames_bgr && src_h > 0 && src_w > 0, ADAS_ERR_INVALID, "adas_pipeline_step_frames_host: bad argument");
     const size_t bytes = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1) * src_h * src_w * 3;
-    if (!p->st_copy) {
-        ADAS_HIP_TRY(hipStreamCreateWithFlags(&p->st_copy, hipStreamNonBlocking));
+    if (!p->st_copy) ADAS_HIP_TRY(hipStreamCreateWithFlags(&p->st_copy, hipStreamNonBlocking));
+    if (!p->ev_copied[0]) {
         for (int k = 0; k < 2; ++k) {
             ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_copied[k], hipEventDisableTiming));
             ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_consumed[k], hipEventDisableTiming));
@@ -663,6 +669,50 @@ int adas_pipeline_wait_upload(adas_pipeline* p) {
     ADAS_REQUIRE(p, ADAS_ERR_INVALID, "null pipeline");
     if (p->st_copy) ADAS_HIP_TRY(hipStreamSynchronize(p->st_copy));
     return ADAS_OK;
+}
+
+int adas_pipeline_attach_jpegdec(adas_pipeline* p, adas_jpegdec* jpegdec) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_jpegdec: null pipeline");
+    if (jpegdec) {
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int jw = 0, jh = 0, jb = 0;
+        adas::jpegdec_geometry_of(jpegdec, &jw, &jh, &jb);
+        ADAS_REQUIRE(jb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_jpegdec: the decoder handle holds %d frames, a step has %d", jb, frames);
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    if (p->st_copy) ADAS_HIP_TRY(hipStreamSynchronize(p->st_copy));
+    p->jpegdec = jpegdec;
+    p->jslot_used[0] = p->jslot_used[1] = false;
+    return ADAS_OK;
+}
+
+int adas_pipeline_step_jpeg_host(adas_pipeline* p, const uint8_t* const* h_streams, const int64_t* h_lengths, double lane_crop_ratio) {
+    ADAS_REQUIRE(p && h_streams && h_lengths, ADAS_ERR_INVALID, "adas_pipeline_step_jpeg_host: bad argument");
+    ADAS_REQUIRE(p->jpegdec, ADAS_ERR_INVALID, "adas_pipeline_step_jpeg_host: no decoder handle attached (adas_pipeline_attach_jpegdec first)");
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int jw = 0, jh = 0, jb = 0;
+    adas::jpegdec_geometry_of(p->jpegdec, &jw, &jh, &jb);
+    if (!p->st_copy) ADAS_HIP_TRY(hipStreamCreateWithFlags(&p->st_copy, hipStreamNonBlocking));
+    for (int k = 0; k < 2; ++k)
+        if (!p->ev_jcopied[k]) {
+            ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_jcopied[k], hipEventDisableTiming));
+            ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_jconsumed[k], hipEventDisableTiming));
+        }
+    // the slot the decoder packs into alternates with every call: the copy waits only for the decode that last read that slot (two steps
+    // back), so it runs under the previous step's decode and nets
+    const int next = adas::jpegdec_next_slot(p->jpegdec);
+    if (p->jslot_used[next]) ADAS_HIP_TRY(hipStreamWaitEvent(p->st_copy, p->ev_jconsumed[next], 0));
+    int slot = next;
+    int rc = adas::jpegdec_stage_host(p->jpegdec, h_streams, h_lengths, frames, p->st_copy, &slot);
+    if (rc) return rc;
+    ADAS_REQUIRE(slot == next, ADAS_ERR_INVALID, "adas_pipeline_step_jpeg_host: the decoder's staging slot moved under the step");
+    ADAS_HIP_TRY(hipEventRecord(p->ev_jcopied[slot], p->st_copy));
+    ADAS_HIP_TRY(hipStreamWaitEvent(p->st, p->ev_jcopied[slot], 0));
+    rc = adas::jpegdec_run_slot(p->jpegdec, slot, frames, nullptr, p->st);
+    if (rc) return rc;
+    ADAS_HIP_TRY(hipEventRecord(p->ev_jconsumed[slot], p->st));
+    p->jslot_used[slot] = true;
+    return adas_pipeline_step_frames(p, adas::jpegdec_frames(p->jpegdec), jh, jw, lane_crop_ratio);
 }
 
 int adas_pipeline_sync(adas_pipeline* p) {

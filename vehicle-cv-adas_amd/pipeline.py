@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, host_streams, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None, jpeg=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -56,14 +56,26 @@ class AdasPipeline:
         leaving the device: jpeg(frame) -> bytes after sync(), jpeg_lengths() -> (lengths, flags).  source="overlay" (the default) encodes
         the drawn frames, behind the overlay's stages and panels, and needs overlay=; source="frames" encodes the camera frames the step was
         given.  Either needs step_frames / step_frames_host.  capacity: bytes per frame (None: height * width * 3); a frame that would not
-        fit comes back as b"" with JpegEncoder.OVERFLOW in its flag.  Any micro_batch: frames are independent."""
+        fit comes back as b"" with JpegEncoder.OVERFLOW in its flag.  Any micro_batch: frames are independent.
+        jpeg_input: None, True or dict(capacity=None): a decoder in FRONT of the step (postproc.JpegDecoder for src_hw frames) for cameras and
+        files that deliver MJPEG: step_jpeg_host(list_of_bytes) uploads the compressed streams (a few hundred KB per frame in place of
+        height * width * 3 bytes), decodes them on the device and runs the step on the decoded frames; input_flags() -> one flag word per
+        frame after sync() (a rejected frame is a black frame to the step).  capacity: the most bytes per stream (None:
+        JpegEncoder.bound(width, height)).  Nothing inside the captured step changes."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
-        self.overlay = self.jpeg_encoder = None
+        self.overlay = self.jpeg_encoder = self.jpeg_decoder = None
+        if jpeg_input is not None and jpeg_input is not False:
+            jpeg_input = {} if jpeg_input is True else dict(jpeg_input)
+            unknown = set(jpeg_input) - {"capacity"}
+            if unknown:
+                raise ValueError("jpeg_input= holds unknown keys %s (capacity)" % sorted(unknown))
+        else:
+            jpeg_input = None
         if jpeg is not None:
             unknown = set(dict(jpeg)) - {"quality", "source", "capacity"}
             if unknown:
@@ -169,6 +181,9 @@ class AdasPipeline:
         if jpeg is not None:
             self.jpeg_encoder = JpegEncoder(src_hw[1], src_hw[0], int(dict(jpeg).get("quality", 90)), n_streams, dict(jpeg).get("capacity"))
             L.check(L.lib().adas_pipeline_attach_jpeg(self.h, self.jpeg_encoder.h, L.JPEG_SOURCES[jpeg_source]))
+        if jpeg_input is not None:
+            self.jpeg_decoder = JpegDecoder(src_hw[1], src_hw[0], n_streams, jpeg_input.get("capacity"))
+            L.check(L.lib().adas_pipeline_attach_jpegdec(self.h, self.jpeg_decoder.h))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -194,6 +209,24 @@ class AdasPipeline:
         """The same step from HOST frames (pinned: _lib.PinnedBuffer): the upload runs on a copy stream into one of two device
         staging buffers, overlapped with the previous step's compute."""
         L.check(L.lib().adas_pipeline_step_frames_host(self.h, h_frames_ptr, int(src_hw[0]), int(src_hw[1]), float(lane_crop_ratio)))
+
+    def step_jpeg_host(self, streams, lane_crop_ratio=0.6):
+        """The same step from COMPRESSED host frames: a list of n_streams x micro_batch baseline JPEG streams (bytes).  Their upload runs on
+        the copy stream, overlapped with the previous step's compute; they are decoded on the device into the decoder's frames and the
+        step runs on those.  The bytes are free again on return.  Needs jpeg_input=."""
+        if self.jpeg_decoder is None:
+            raise ValueError("the pipeline was created without jpeg_input=")
+        if len(streams) != self.S * self.B:
+            raise ValueError("step_jpeg_host got %d streams, a step has %d frames" % (len(streams), self.S * self.B))
+        ptrs, lengths, keep = host_streams(streams)
+        L.check(L.lib().adas_pipeline_step_jpeg_host(self.h, ptrs, L.ptr(lengths), float(lane_crop_ratio)))
+
+    def input_flags(self):
+        """The decoder's flag word of every frame of the last step_jpeg_host (after sync()): int32 [frames], 0 for a clean frame
+        (JpegDecoder.UNSUPPORTED / FORMAT / SIZE: the step saw a black frame; CORRUPT: damaged entropy data)."""
+        if self.jpeg_decoder is None:
+            raise ValueError("the pipeline was created without jpeg_input=")
+        return self.jpeg_decoder.flags(self.S * self.B)
 
     def request_transform(self, stream, mode_name):
         """updateTransformParams(..., type=mode_name) for local stream `stream` on its NEXT step ("Default" | "Top" | "Bottom"): applied
@@ -257,7 +290,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

@@ -827,6 +827,108 @@ class JpegEncoder:
     __del__ = close
 
 
+def host_streams(streams):
+    """A list of bytes-like objects -> (array of their addresses, int64 array of their lengths, what keeps them alive during the call)."""
+    keep = [np.frombuffer(s, np.uint8) if len(s) else np.zeros(1, np.uint8) for s in streams]
+    ptrs = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+    lengths = np.array([len(s) for s in streams], np.int64)
+    return ptrs, lengths, keep
+
+
+def split_mjpeg(data):
+    """A raw MJPEG file (concatenated JPEG streams, what JpegEncoder's streams are when appended) -> [(stream bytes, (width, height) or None)].
+    Every stream is walked marker by marker: the segments in front of the scan by their lengths, the entropy data up to the first marker
+    that is neither a restart marker nor a stuffed 0xFF; a stream runs from its SOI to its EOI (or to the next SOI / the file's end when
+    the EOI is missing).  The size is SOFn's; None when the stream has none in front of its scan."""
+    data = bytes(data)
+    out, i, n = [], 0, len(data)
+    while True:
+        a = data.find(b"\xff\xd8", i)
+        if a < 0:
+            return out
+        p, size = a + 2, None
+        while p + 4 <= n and data[p] == 0xFF:              # marker segments
+            m = data[p + 1]
+            if m == 0xFF:
+                p += 1
+                continue
+            if m in (0xD8, 0xD9):
+                break
+            if m == 0x01 or 0xD0 <= m <= 0xD7:
+                p += 2
+                continue
+            length = int.from_bytes(data[p + 2:p + 4], "big")
+            if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC) and length >= 7:
+                size = (int.from_bytes(data[p + 7:p + 9], "big"), int.from_bytes(data[p + 5:p + 7], "big"))
+            p += 2 + length
+            if m == 0xDA:                                  # entropy data
+                while True:
+                    p = data.find(b"\xff", p)
+                    if p < 0 or p + 1 >= n:
+                        p = n
+                        break
+                    if data[p + 1] in (0x00, 0xFF) or 0xD0 <= data[p + 1] <= 0xD7:
+                        p += 1 if data[p + 1] == 0xFF else 2
+                        continue
+                    break
+        end = p + 2 if p + 2 <= n and data[p:p + 2] == b"\xff\xd9" else min(max(p, a + 2), n)
+        out.append((data[a:end], size))
+        i = end
+
+
+class JpegDecoder:
+    """Baseline JPEG decoding on the device (adas_jpegdec_*): compressed camera frames in -- from the host, or where a JpegEncoder left them --
+    BGR u8 frames out in HBM, where AdasPipeline.step_frames reads them.  Grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, the stream's own tables, any
+    restart interval (restart segments decode in parallel; a stream without restart markers on one lane).  The rules D1-D9 are
+    csrc/jpegdec_core.h.  Stream content never raises: flags(n) holds one word per frame, and a frame flagged UNSUPPORTED, FORMAT or SIZE is
+    black; CORRUPT marks an error in the entropy data, after which the rest of that restart segment is flat.
+    capacity: the most bytes per stream (None: JpegEncoder.bound(width, height))."""
+    UNSUPPORTED, FORMAT, SIZE, CORRUPT = L.JPEGDEC_UNSUPPORTED, L.JPEGDEC_FORMAT, L.JPEGDEC_SIZE, L.JPEGDEC_CORRUPT
+
+    def __init__(self, width, height, max_batch=1, capacity=None):
+        self.p = L.JpegDecParams(int(width), int(height), (C.c_int32 * 2)(0, 0), int(capacity or 0))
+        self.width, self.height, self.max_batch = int(width), int(height), int(max_batch)
+        h = C.c_void_p()
+        L.check(L.lib().adas_jpegdec_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        self.capacity = int(capacity) if capacity else JpegEncoder.bound(width, height)
+
+    def run_host(self, streams, d_dst=None, stream=None):
+        """streams: a list of bytes, one JPEG stream per frame.  Asynchronous on `stream`; the bytes are free again on return.  d_dst: device
+        pointer of [len(streams)][height][width][3] u8 (None: the handle's own frames)."""
+        ptrs, lengths, keep = host_streams(streams)
+        L.check(L.lib().adas_jpegdec_run_host(self.h, ptrs, L.ptr(lengths), len(streams), d_dst, stream))
+
+    def run_device(self, d_ptr, d_lengths_ptr, stride, n, d_dst=None, stream=None):
+        """Streams on the device: frame f at d_ptr + f * stride (any byte), its int64 length at d_lengths_ptr[f]: JpegEncoder.device_view()."""
+        L.check(L.lib().adas_jpegdec_run(self.h, d_ptr, d_lengths_ptr, int(stride), int(n), d_dst, stream))
+
+    def image(self, frame=0):
+        """Frame `frame` of the last run into the handle's own frames: (height, width, 3) uint8 BGR.  Waits for that run."""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        L.check(L.lib().adas_jpegdec_fetch(self.h, int(frame), L.ptr(out)))
+        return out
+
+    def flags(self, n=1):
+        """The flag words of the last run's first n frames (int32).  Waits for that run."""
+        f = np.zeros(int(n), np.int32)
+        L.check(L.lib().adas_jpegdec_fetch_flags(self.h, int(n), L.ptr(f)))
+        return f
+
+    def device_view(self):
+        """(device pointer of the handle's frames [max_batch][height][width][3], device pointer of the int32 flags)."""
+        d, f = C.c_void_p(), C.c_void_p()
+        L.check(L.lib().adas_jpegdec_device_view(self.h, C.byref(d), C.byref(f)))
+        return d.value, f.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_jpegdec_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
