@@ -1,4 +1,5 @@
 """Adapters that give the HIP library the same call shape as tests/emu_api.py."""
+import ctypes as C
 import numpy as np
 from conftest import load_pkg
 import importlib
@@ -20,6 +21,34 @@ def yolo_post(head, layout, lb, box_score, iou, nms_mode=0, cap=1024, batch_copi
     finally:
         yp.close()
     return res if batch_copies > 1 else res[0]
+
+
+def scan_views(yp):
+    """Device addresses of a YoloPost's per-anchor scan results: best_conf float32 [max_batch][A], best_cls int32 [max_batch][A]."""
+    conf, cls = C.c_void_p(), C.c_void_p()
+    L.check(L.lib().adas_yolo_post_scan_views(yp.h, C.byref(conf), C.byref(cls)))
+    return conf.value, cls.value
+
+
+def yolo_scan(heads, layout, lb, box_score, iou, nms_mode=0, cap=1024):
+    """heads [frames, ...]: one launch over all frames -> (best_conf [frames, A] float32, best_cls [frames, A] int32 as the scan kernel
+    left them for EVERY anchor, the per-frame results of fetch())."""
+    heads = np.ascontiguousarray(heads, np.float32)
+    F = heads.shape[0]
+    if layout == 0:
+        nc, A = heads.shape[1] - 4, heads.shape[2]
+    else:
+        A, nc = heads.shape[1], heads.shape[2] - 5
+    yp = PP.YoloPost(layout, A, nc, box_score, iou, lb, nms_mode, cap, max_batch=F)
+    try:
+        res = yp.run_host(heads)                                   # fetch() waits for the launch
+        d_conf, d_cls = scan_views(yp)
+        conf, cls = np.empty((F, A), np.float32), np.empty((F, A), np.int32)
+        L.check(L.lib().adas_memcpy_d2h(L.ptr(conf), d_conf, conf.nbytes))
+        L.check(L.lib().adas_memcpy_d2h(L.ptr(cls), d_cls, cls.nbytes))
+    finally:
+        yp.close()
+    return conf, cls, res
 
 
 def ufld(outs, cfg, W, H, lw=1):
