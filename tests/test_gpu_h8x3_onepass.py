@@ -8,7 +8,11 @@ adas_debug_h8x3_onepass answers for its layer and batch: a case that lands on th
   1p-ragged   13x37  80 -> 80  SiLU, res RA   slice of wider buffers between guards: padded Cin chunk (3 chunks), trimmed wave group, ragged
                                               strips, out-of-image lanes
   1p-blocks   16x32  64 -> 256 ReLU           batch 61: two 64-channel blocks per unit, the weights switch between two items of one window
-  2p-wide     40x40  64 -> 64                 batch 16: windows of more than 384 pixels: the predicate refuses, the two-pass body serves it
+  2p-wide     40x40  64 -> 64                 batch 16: windows of more than 384 pixels (420: four window pieces per wave): the predicate
+                                              refuses, the two-pass body serves it
+  2p-wide5    17x91  64 -> 64                 batch 13: windows of 558 pixels, five window pieces per wave.  The smallest map and batch at
+                                              which the fifth piece (window pixels 512 and up) holds pixels that outputs read (up to 523, tile
+                                              1); smaller maps with such plans (4x63 at 89 frames) fill it with out-of-image lanes only
   1p-2rounds  16x32  64 -> 64                 batch 256: 512 items on 256 workgroups, every one decodes and prefetches a second tile"""
 import ctypes as C_
 import importlib
@@ -22,7 +26,7 @@ pytestmark = pytest.mark.gpu
 load_pkg()
 L = importlib.import_module("adas_amd._lib")
 
-MIN1, RAG1, WIDE = (16, 32), (13, 37), (40, 40)
+MIN1, RAG1, WIDE, WIDE5 = (16, 32), (13, 37), (40, 40), (17, 91)
 LABEL = "conv_h8x3_kernel<{A}>"
 #        case                                                                                         one-pass body?
 CASES = [(C("1p-1chunk", LABEL, MIN1, 32, 64, act=LEAKY, res=RN, batch=45, precs=PX3), True),
@@ -30,6 +34,7 @@ CASES = [(C("1p-1chunk", LABEL, MIN1, 32, 64, act=LEAKY, res=RN, batch=45, precs
          (C("1p-ragged", LABEL, RAG1, 80, 80, act=SILU, res=RA, batch=22, precs=PX3, sl=True), True),
          (C("1p-blocks", LABEL, MIN1, 64, 256, act=RELU, res=RN, batch=61, precs=PX3), True),
          (C("2p-wide", LABEL, WIDE, 64, 64, act=NONE, res=RN, batch=16, precs=PX3), False),
+         (C("2p-wide5", LABEL, WIDE5, 64, 64, act=LEAKY, res=RA, batch=13, precs=PX3), False),
          (C("1p-2rounds", LABEL, MIN1, 64, 64, act=SILU, res=RN, batch=256, precs=PX3), True)]
 
 

@@ -13,9 +13,13 @@
 //   epilogue  out = act(main + 2^-11 cross [+ residual]) -> split -> G8 store (8 B hi + 8 B lo per lane and 16-channel tile)
 // = the three-MFMA product of elem16.h with no operand re-fetch.  Weight slabs [64-row block][half-chunk][tap][64 rows][32] are packed at
 // load time (launch_pack_weights_h8x3); an eligible conv keeps both this packing and the generic one, the launch picks by batch.
-// Two bodies share the route, the label, the slabs and the epilogue: the two-pass stream described above (conv_h8x3_kernel) and the one-pass
-// body (x8_onepass_body = conv_h8x3_kernel<ACT, 3, ...>, further down: whole 128-byte lines in the window, all three products in one tap), which takes every
-// launch whose windows fit 384 pixels (halo8_x3_onepass; ADAS_H8X_ONEPASS=0 turns it off).
+// Two bodies share the route, the label, the slabs and the epilogue: the two-pass stream described above (conv_h8x3_kernel<ACT, X8_TWOPASS,
+// NWP>) and the one-pass body (x8_onepass_body = conv_h8x3_kernel<ACT, X8_ONEPASS, 3>, further down: whole 128-byte lines in the window, all
+// three products in one tap), which takes every launch whose windows fit 384 pixels (halo8_x3_onepass; ADAS_H8X_ONEPASS=0 turns it off).
+// These two are what the measurements left.  The forms that lost -- wave groups a barrier apart (ping-pong), a weight tile per half-chunk
+// (whole, or the cross rows only for an L half-chunk), 8-byte stores, the one-value epilogue, the wait behind a tap's MFMAs, untrimmed
+// wave groups -- are on record in profiles/r06/ (ab_h8x3_lhalf_modes.txt: ping-pong -4.3 % end to end; ab_h8x3_share_plan_epilogue.txt;
+// ab_h8x3_variants.txt) and in DESIGN.md; they are no longer built.
 #include "kernels.h"
 #include "elem16.h"
 #include <stdlib.h>
@@ -57,8 +61,9 @@ constexpr int X8_NWP = X8_MAXPIX / 16 / 8;      // window pieces per wave (5)
 constexpr int X8_SLAB = 9 * 64 * 64;            // bytes of one (64-row block, half-chunk) weight slab
 constexpr uint32_t X8_OOB = 0xF0000000u;
 constexpr int X8_SLOTS = 32;
-
-__host__ __device__ constexpr int x8_look(int mode) { return mode == 2 ? 6 : 4; }
+constexpr int X8_LOOK = 6;                      // weight tiles the two-pass prologue puts into the ring (two tap rows)
+// conv_h8x3_kernel's BODY parameter (the values are part of the kernel names that profiles are read by)
+constexpr int X8_TWOPASS = 2, X8_ONEPASS = 3;
 
 template <int N>
 __device__ __forceinline__ void x8_wait_vm() {
@@ -73,7 +78,7 @@ __device__ __forceinline__ float x8_act(float v) {
     return v;
 }
 
-// ---- the epilogue's arithmetic two values at a time (round 6; ADAS_H8X_SCALAR_EPI builds keep the one-value form).  An item's epilogue was
+// ---- the epilogue's arithmetic two values at a time (round 6; the one-value form measured 0.6 % slower end to end).  An item's epilogue was
 // ~16 VALU instructions per output value, 32 values per lane, two waves per SIMD: ~4,000 cycles in which no MFMA issues.  gfx950 has
 // v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32 and v_cvt_pk_f16_f32: join, residual add and split take 12 instructions per four values
 // instead of 28 + 12.  x3_split's "no subnormal hi" rule costs a compare and a select per value in the scalar form; here the hi
@@ -102,13 +107,6 @@ __device__ __forceinline__ uint32_t x8_lo2(yf32x2 v, uint32_t h) {   // the lo h
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(d, e_f16x2));
 }
 
-__host__ __device__ constexpr int x8_issued(int k) { return 1 + ((k >= 1 && k <= X8_NWP) ? 1 : 0); }
-__host__ __device__ constexpr int x8_allow(int mode, int k) {
-    return mode == 2 ? x8_issued(k) + x8_issued(k - 1) + x8_issued(k - 2)
-                     : x8_issued(k) + x8_issued((k + 8) % 9) + x8_issued((k + 7) % 9);
-}
-// loads queued under the last tap row of an item besides the stream's pieces: the next item's bias (2 float4) and, with a residual,
-// 16 eight-byte loads (4 pixel tiles x 2 channel tiles x {hi, lo})
 // X8_RES_TAP: the tap of an item's LAST half-chunk under which the residual tile and the next item's bias are requested.  Round 4 asked
 // at tap 6 (the last tap row), which leaves an HBM read ~1.5 k cycles before the epilogue needs it -- the phase counters showed the last
 // half-chunk of a residual layer at 11.9 k cycles against 6.5 k without (profiles/r06/h8x_phases.txt); at tap 0 the loads have the whole
@@ -116,15 +114,10 @@ __host__ __device__ constexpr int x8_allow(int mode, int k) {
 // +0.2 % end to end (inside the noise: the item's other fixed costs hide most of it), kept.  (Later in round 6: one residual load per tap,
 // taps 0-7, instead of eight under tap 0 -- counted waits adjusted per tap row -- changed nothing: layer1's conv2 0.515 / 0.509 ms either
 // way, -0.3 % end to end; the 3 k cycles a residual item costs are its 64 KB of extra HBM reads, not the issue burst.  Not kept.)
-#ifndef ADAS_H8X_RES_TAP
-#define ADAS_H8X_RES_TAP 0
-#endif
-constexpr int X8_RES_TAP = ADAS_H8X_RES_TAP;
-#ifdef ADAS_H8X_NARROW_ST
-constexpr int X8_NBIAS = 2, X8_NRES = 16;
-#else
-constexpr int X8_NBIAS = 2, X8_NRES = 8;    // (wide form: one 16-byte load per pixel tile and channel tile)
-#endif
+constexpr int X8_RES_TAP = 0;
+// the loads queued under that tap besides the stream's pieces: the next item's bias (2 float4) and, with a residual, one 16-byte load per
+// pixel tile and channel tile (4 x 2)
+constexpr int X8_NBIAS = 2, X8_NRES = 8;
 
 #ifdef ADAS_H8X_PROF   // scratch instrumentation (tools/experiments/h8x_prof.py): shader cycles of waves 0 and 4 per item phase
 __device__ unsigned long long g_h8x_prof[256][32];
@@ -138,8 +131,7 @@ __device__ unsigned long long g_h8x_prof[256][32];
 #define H8XP(i)
 #endif
 
-#if !defined(ADAS_H8X_SCALAR_EPI) && !defined(ADAS_H8X_NARROW_ST)
-// the wide epilogue of one item (both bodies): join main and cross, residual, activation, split, one 16-byte store per lane and 16-channel
+// the epilogue of one item (both bodies): join main and cross, residual, activation, split, one 16-byte store per lane and 16-channel
 // tile; leaves the accumulators at the next item's bias / zero
 template <int ACT, int RM>
 __device__ __forceinline__ void x8_write_out(const H8XDev& a, __amdgpu_buffer_rsrc_t rout, yf32x4 (&acc)[4][4], const yu32x4 (&rraw)[4][2],
@@ -190,28 +182,29 @@ __device__ __forceinline__ void x8_write_out(const H8XDev& a, __amdgpu_buffer_rs
         }
     }
 }
-#endif
 
-// LH: the weight tiles of an L half-chunk are fetched as their CROSS rows only (rows 32-63 of each 64-row block: the main rows are
-// zeros that no MFMA reads) -- every wave still issues one piece per tap, with the upper half of its lanes masked off: 512 B = 8 rows
-// SH (round 6, MODE 2 only): the L half-chunk of a 32-channel chunk multiplies the lo activations by w_hi -- the MAIN rows of the H
-// half-chunk's own weight tiles, which sit in the 9-slot ring while the H taps run.  With SH the ring keeps a chunk's nine tiles through
-// BOTH half-chunks and the L taps read those main rows: no weight tile is fetched for an L half-chunk at all (half the weight DMA
-// instructions and bytes of the stream).  Tile t of the next chunk may overwrite slot t once the L tap row that reads it has passed its
-// barrier, and must be issued two tap rows before the H tap row that reads it: exactly one tap row fits -- tiles 0-2 go out under L
-// taps 3-5, tiles 3-5 under L taps 6-8, tiles 6-8 under the next H taps 0-2 ("tile (kk + 6) % 9" as before, on those taps only).
+// ---- the two-pass stream ---------------------------------------------------------------------------------------------------------
+// Synchronisation: one barrier per tap row (taps 2, 5, 8 of a half-chunk), a counted wait ahead of it; both wave groups run in step.
+// Weights: the L half-chunk of a 32-channel chunk multiplies the lo activations by w_hi -- the MAIN rows of the H half-chunk's own weight
+// tiles, which sit in the 9-slot ring while the H taps run.  The ring keeps a chunk's nine tiles through BOTH half-chunks and the L taps
+// read those main rows: no weight tile is fetched for an L half-chunk at all (half the weight DMA instructions and bytes of a stream
+// that fetches one per half-chunk: -2.2 % end to end without, profiles/r06/ab_h8x3_share_plan_epilogue.txt).  Tile t of the next chunk
+// may overwrite slot t once the L tap row that reads it has passed its barrier, and must be issued two tap rows before the H tap row
+// that reads it: exactly one tap row fits -- tiles 0-2 go out under L taps 3-5, tiles 3-5 under L taps 6-8, tiles 6-8 under the next H
+// taps 0-2 ("tile (kk + 6) % 9", on those taps only).
 // NWP: window pieces per wave and half-chunk (1 KiB each, 16 pixels): 3 / 4 / 5 for windows up to 384 / 512 / 640 pixels -- a tile's
 // window rarely fills the 640-pixel buffer, and every piece is a DMA instruction whether its lanes are in range or not.
+// x8s_issued: loads a wave issues under tap k of an H / L half-chunk (a weight tile, a window piece); x8s_allow: what may stay in flight
+// past the wait of tap k's row -- the pieces issued in that row.
 __host__ __device__ constexpr int x8s_issued(bool lo, int k, int nwp) { return ((lo ? k >= 3 : (k >= 0 && k < 3)) ? 1 : 0) + ((k >= 1 && k <= nwp) ? 1 : 0); }
 __host__ __device__ constexpr int x8s_allow(bool lo, int k, int nwp) { return x8s_issued(lo, k, nwp) + x8s_issued(lo, k - 1, nwp) + x8s_issued(lo, k - 2, nwp); }
 
-template <int ACT, int MODE, bool LH, bool SH, int NWP>
+template <int ACT, int BODY, int NWP>
 __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
-    static_assert(!SH || (MODE == 2 && !LH), "shared weight tiles: one barrier per tap row, whole tiles");
-    static_assert(NWP >= 1 && NWP <= X8_NWP && (SH || NWP == X8_NWP), "window pieces per wave");
+    static_assert(BODY == X8_TWOPASS, "the one-pass body is a specialisation, further down");
+    static_assert(NWP >= 1 && NWP <= X8_NWP, "window pieces per wave");
     Fp16::enter();
     typedef Fp16::vec8 hvec8;
-    constexpr int LOOK = x8_look(MODE);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds8[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -237,20 +230,11 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
     // halves sit at group * 32 bytes (its lo halves 16 bytes behind)
     const uint32_t wpiece = (uint32_t)((lane & 3) ^ (((lane >> 4) & 1) << 1)) << 5;
     const uint32_t wrd = (uint32_t)(X8_WR + hb * 4096 + lrow * 64 + ((kg ^ gsw[(lrow >> 2) & 3]) << 4));
-    // LH pieces: wave grp brings rows 32 + 8 grp .. + 7 of its block (lanes 0-31: row lane >> 2), i.e. rows 8 (grp & 1) .. + 7 of the
-    // 16-row tile 2 + (grp >> 1) -- the swizzle key is the row's position in THAT tile
-    const uint32_t wlane_h = (uint32_t)((lane >> 2) * 64 + (((lane & 3) ^ gsw[(((lane >> 4) & 1) + 2 * (grp & 1)) & 3]) << 4));
-    const uint32_t wdst_h = (uint32_t)(X8_WR + hb * 4096 + 2048 + grp * 512);
-    // epilogue: lane owns channels kg*4 .. +3 of 16-channel tile i of the wave group's 32: G8 byte offset of their hi halves within
-    // the pixel's 64-channel run (lo halves 16 bytes behind): group (hb*32 + i*16 + kg*4) / 8, element (kg & 1) * 4
-    // Wide form (default): v_permlane16_swap pairs the lanes that own the two 4-channel halves of a group (kg even / odd: 16 lanes
+    // epilogue: lane owns channels kg*4 .. +3 of 16-channel tile i of the wave group's 32, in G8 group (hb*32 + i*16 + kg*4) / 8 of the
+    // pixel's 64-channel run.  v_permlane16_swap pairs the lanes that own the two 4-channel halves of a group (kg even / odd: 16 lanes
     // apart), after which the even row holds the group's 16 hi bytes and the odd row its 16 lo bytes: one 16-byte store (and residual
     // load) per lane and tile instead of two 8-byte ones -- half the vector-memory instructions of the epilogue.
-#ifdef ADAS_H8X_NARROW_ST
-    const uint32_t ch_lane = (uint32_t)((hb * 4 + (kg >> 1)) * 32 + (kg & 1) * 8);
-#else
     const uint32_t ch_lane = (uint32_t)((hb * 4 + (kg >> 1)) * 32 + (kg & 1) * 16);
-#endif
     const bool has_res = a.res_mode != RES_NONE;
 
     struct Tile {
@@ -320,12 +304,12 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
     float4 biasn[2];
     load_bias(cb, biasn);
 
-    // ---- prologue: window of half-chunk 0 into buffer 0, weights of taps 0 .. LOOK-1
+    // ---- prologue: window of half-chunk 0 into buffer 0, weights of taps 0 .. X8_LOOK-1
 #pragma unroll
     for (int i = 0; i < NWP; ++i)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (ylds_vp)(lds8 + (wave + 8 * i) * 1024), 16, gcur[i], 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < LOOK; ++t)
+    for (int t = 0; t < X8_LOOK; ++t)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rwg, (ylds_vp)(lds8 + X8_WR + t * X8_TAP + wave * 1024), 16, wlane, wcur + t * 4096, 0, 0);
     yf32x4 acc[4][4];   // [0..1]: main, starts at the bias; [2..3]: cross, starts at zero
 #pragma unroll
@@ -338,7 +322,6 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
     }
     x8_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
-    if (MODE == 1 && hb) __builtin_amdgcn_s_barrier();   // group 1 runs one segment behind group 0
 #ifdef ADAS_H8X_PROF
     unsigned long long tprev__ = clock64();
     unsigned long long pacc__[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -353,16 +336,12 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
         const uint32_t ch0 = (uint32_t)(cb * 256) + ch_lane;   // 64 channels = 256 bytes of G8 storage
         // a wave group whose 32 channels lie past Cout (the padded tail of the last 64-channel block: 80 -> 128 leaves group 1 of block 1 with
         // zero weight rows and masked stores) takes part in the DMA stream and the barriers but reads no fragments and issues no MFMAs -- its
-        // SIMD partner of group 0 has the matrix pipe to itself for that item (ADAS_H8X_NO_TRIM builds keep the zero products)
-#ifndef ADAS_H8X_NO_TRIM
+        // SIMD partner of group 0 has the matrix pipe to itself for that item
         const bool wave_on = cb * 64 + hb * 32 < a.cout;
-#else
-        constexpr bool wave_on = true;
-#endif
         Tile nxt = cur;
         uint32_t wnxt_item = 0, apn[4] = {0, 0, 0, 0};
-        yu32x4 rraw[4][2];      // residual [pixel tile][channel tile], fetched under the last row of taps of the last half-chunk: one 16-byte piece
-                                // of the lane's G8 group per entry (wide form), or its own 8 B hi + 8 B lo (ADAS_H8X_NARROW_ST builds)
+        yu32x4 rraw[4][2];      // residual [pixel tile][channel tile], fetched under tap X8_RES_TAP of the last half-chunk: one 16-byte piece
+                                // of the lane's G8 group per entry
 
         auto chunk = [&](auto last_c, auto lo_c, const int c) {
             constexpr bool lastc = decltype(last_c)::value;
@@ -391,71 +370,38 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
                         const uint32_t ro = po[j] == X8_OOB ? X8_OOB : (po[j] * (uint32_t)a.res_cs + (uint32_t)a.res_coff) * 4u + ch0;
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
-#ifdef ADAS_H8X_NARROW_ST
-                            const uint32_t ri = (cb * 64 + hb * 32 + i * 16 + kg * 4 < a.cout) ? ro + i * 64 : X8_OOB;
-                            const yu32x2 rh = __builtin_bit_cast(yu32x2, __builtin_amdgcn_raw_buffer_load_b64(rres, ri, 0, 0));
-                            const yu32x2 rl = __builtin_bit_cast(yu32x2, __builtin_amdgcn_raw_buffer_load_b64(rres, ri + 16, 0, 0));
-                            rraw[j][i] = yu32x4{rh.x, rh.y, rl.x, rl.y};
-#else
                             // one 16-byte piece of the lane's 8-channel group: its hi half on the even 16-lane rows, its lo half on the odd ones
                             const uint32_t ri = (cb * 64 + hb * 32 + i * 16 + (kg >> 1) * 8 < a.cout) ? ro + i * 64 : X8_OOB;
                             rraw[j][i] = __builtin_bit_cast(yu32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, ri, 0, 0));
-#endif
                         }
                     }
                 }
                 hvec8 wf[4], xf[4];
-                // (SH: an L tap multiplies by the MAIN rows -- w_hi -- of the chunk's H tile, still in slot kk)
+                // (an L tap multiplies by the MAIN rows -- w_hi -- of the chunk's H tile, still in slot kk)
                 if (wave_on) {
 #pragma unroll
-                    for (int i = islo ? 2 : 0; i < 4; ++i) wf[i] = *reinterpret_cast<const hvec8*>(lds8 + wrd + kk * X8_TAP + ((SH && islo) ? i - 2 : i) * 1024);
+                    for (int i = islo ? 2 : 0; i < 4; ++i) wf[i] = *reinterpret_cast<const hvec8*>(lds8 + wrd + kk * X8_TAP + (islo ? i - 2 : i) * 1024);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) xf[j] = *reinterpret_cast<const hvec8*>(lds8 + xoff[j][kk] + winr);
                 }
-                if constexpr (SH) {
-                    if constexpr (islo ? kk >= 3 : kk < 3) {
-                        constexpr int kt = (kk + 6) % 9;      // H taps 0-2: tiles 6-8 of this chunk; L taps 3-8: tiles 0-5 of the next chunk (or item)
-                        const uint32_t src = (islo ? wnext : wthis) + (uint32_t)kt * 4096u;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rwg, (ylds_vp)(lds8 + X8_WR + kt * X8_TAP + wave * 1024), 16, wlane, src, 0, 0);
-                    }
-                } else {
-                    constexpr int kt = (kk + LOOK) % 9;
-                    constexpr bool tgt_lo = (kk + LOOK < 9) ? islo : !islo;     // the half-chunk this tap tile belongs to (the chunks alternate H, L)
-                    const uint32_t src = (kk + LOOK < 9 ? wthis : wnext) + (uint32_t)kt * 4096u;
-                    if (LH && tgt_lo) {
-                        // (wthis / wnext carry this wave's grp * 1024: the cross rows of the wave's piece sit at + 2048 - 512 grp from there)
-                        if (lane < 32)
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rwg, (ylds_vp)(lds8 + wdst_h + kt * X8_TAP), 16, wlane_h, src + 2048u - (uint32_t)grp * 512u, 0, 0);
-                    } else {
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rwg, (ylds_vp)(lds8 + X8_WR + kt * X8_TAP + wave * 1024), 16, wlane, src, 0, 0);
-                    }
+                if constexpr (islo ? kk >= 3 : kk < 3) {
+                    constexpr int kt = (kk + 6) % 9;      // H taps 0-2: tiles 6-8 of this chunk; L taps 3-8: tiles 0-5 of the next chunk (or item)
+                    const uint32_t src = (islo ? wnext : wthis) + (uint32_t)kt * 4096u;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rwg, (ylds_vp)(lds8 + X8_WR + kt * X8_TAP + wave * 1024), 16, wlane, src, 0, 0);
                 }
                 if constexpr (kk >= 1 && kk <= NWP)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (ylds_vp)(lds8 + winw + (wave + 8 * (kk - 1)) * 1024), 16, lastc ? gnxt[kk - 1] : gcur[kk - 1], 0, 0, 0);
-                constexpr bool sync_here = MODE != 2 || kk % 3 == 2;
-                // what may stay in flight past this point: the pieces issued in this tap row (MODE 2) / the last three taps
-                constexpr int allow = SH ? x8s_allow(islo, kk, NWP) : x8_allow(MODE, kk);
-                // (the residual / bias loads of the last half-chunk count among the pieces of the tap row they are issued in -- MODE 2 -- or of the
-                // following taps -- MODE 1, one wait per tap: X8_RES_TAP = 6 there)
-                constexpr bool with_res = kk >= X8_RES_TAP && (MODE == 2 ? kk / 3 == X8_RES_TAP / 3 : kk < X8_RES_TAP + 3);
-                auto counted_wait = [&]() {
-                    if (sync_here && (c > 0 || kk >= 3)) {
-                        if (lastc && with_res && has_res) x8_wait_vm<allow + X8_NBIAS + X8_NRES>();
-                        else if (lastc && with_res) x8_wait_vm<allow + X8_NBIAS>();
-                        else x8_wait_vm<allow>();
-                    }
-                };
-                // (MODE 2: the wait only has to precede the row's barrier, not this tap's MFMAs; placed behind them -- ADAS_H8X_WAIT_LAST builds --
-                // it measured 0.5 % slower end to end, profiles/r06/ab_h8x3_variants.txt: the round-4 order stays)
-#ifndef ADAS_H8X_WAIT_LAST
-                counted_wait();
-#else
-                if (MODE == 1) counted_wait();
-#endif
-                if (MODE == 1) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
+                constexpr bool sync_here = kk % 3 == 2;   // one barrier per tap row
+                // what may stay in flight past this point: the pieces issued in this tap row
+                constexpr int allow = x8s_allow(islo, kk, NWP);
+                // (the residual / bias loads of the last half-chunk count among the pieces of the tap row they are issued in)
+                constexpr bool with_res = kk >= X8_RES_TAP && kk / 3 == X8_RES_TAP / 3;
+                // (the wait only has to precede the row's barrier, not this tap's MFMAs; placed behind them it measured 0.5 % slower end to
+                // end, profiles/r06/ab_h8x3_variants.txt: the round-4 order stays)
+                if (sync_here && (c > 0 || kk >= 3)) {
+                    if (lastc && with_res && has_res) x8_wait_vm<allow + X8_NBIAS + X8_NRES>();
+                    else if (lastc && with_res) x8_wait_vm<allow + X8_NBIAS>();
+                    else x8_wait_vm<allow>();
                 }
                 __builtin_amdgcn_s_setprio(1);
                 if (lastc) {
@@ -479,9 +425,6 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
                 __builtin_amdgcn_s_setprio(0);
                 if (sync_here) {
                     __builtin_amdgcn_sched_barrier(0);
-#ifdef ADAS_H8X_WAIT_LAST
-                    if (MODE != 1) counted_wait();
-#endif
                     __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -502,68 +445,9 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
         // ---------------- epilogue: lane holds channels kg*4..+3 of pixel lrow of every (i, j) tile
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         H8XP(4)
-#if !defined(ADAS_H8X_SCALAR_EPI) && !defined(ADAS_H8X_NARROW_ST)
+        // (through a lambda: called directly, hipcc hands the residual tile other registers -- the same instructions, but not the code object
+        // that was measured)
         auto write_out = [&](auto rm_c) { x8_write_out<ACT, decltype(rm_c)::value>(a, rout, acc, rraw, biasn, po, ch0, cb, hb, kg); };
-#else
-        auto write_out = [&](auto rm_c) {
-            constexpr int RM = decltype(rm_c)::value;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t oo = po[j] == X8_OOB ? X8_OOB : (po[j] * (uint32_t)a.out_cs + (uint32_t)a.out_coff) * 4u + ch0;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    // channels past cout (the padded tail of the last 64-channel block) are computed on zero weights and not stored
-#ifdef ADAS_H8X_NARROW_ST
-                    const uint32_t oi = (cb * 64 + hb * 32 + i * 16 + kg * 4 < a.cout) ? oo + i * 64 : X8_OOB;
-#else
-                    const uint32_t oi = (cb * 64 + hb * 32 + i * 16 + (kg >> 1) * 8 < a.cout) ? oo + i * 64 : X8_OOB;   // (cout is a multiple of 8)
-#endif
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + acc[i + 2][j][e] * kX3Down;
-                    if (RM != RES_NONE) {
-                        // (words copied to scalars first: hipcc's __builtin_bit_cast applied directly to a vector ELEMENT reads element 0)
-#ifdef ADAS_H8X_NARROW_ST
-                        const uint32_t wh0 = rraw[j][i].x, wh1 = rraw[j][i].y, wl0 = rraw[j][i].z, wl1 = rraw[j][i].w;
-#else
-                        // the swap that forms the 16-byte pieces is its own inverse: it hands each lane its own hi and lo words back
-                        const auto q0 = __builtin_amdgcn_permlane16_swap(rraw[j][i].x, rraw[j][i].z, false, false);
-                        const auto q1 = __builtin_amdgcn_permlane16_swap(rraw[j][i].y, rraw[j][i].w, false, false);
-                        const uint32_t wh0 = q0[0], wl0 = q0[1], wh1 = q1[0], wl1 = q1[1];
-#endif
-                        const e_f16x2 h0 = __builtin_bit_cast(e_f16x2, wh0);
-                        const e_f16x2 h1 = __builtin_bit_cast(e_f16x2, wh1);
-                        const e_f16x2 l0 = __builtin_bit_cast(e_f16x2, wl0);
-                        const e_f16x2 l1 = __builtin_bit_cast(e_f16x2, wl1);
-                        const float r[4] = {x3_join(h0[0], l0[0]), x3_join(h0[1], l0[1]), x3_join(h1[0], l1[0]), x3_join(h1[1], l1[1])};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = RM == RES_BEFORE_ACT ? x8_act<ACT>(v[e] + r[e]) : x8_act<ACT>(v[e]) + r[e];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = x8_act<ACT>(v[e]);
-                    }
-                    e_f16x2 h0, h1, l0, l1;
-                    _Float16 h, l;
-                    x3_split(v[0], h, l); h0[0] = h; l0[0] = l;
-                    x3_split(v[1], h, l); h0[1] = h; l0[1] = l;
-                    x3_split(v[2], h, l); h1[0] = h; l1[0] = l;
-                    x3_split(v[3], h, l); h1[1] = h; l1[1] = l;
-#ifdef ADAS_H8X_NARROW_ST
-                    __builtin_amdgcn_raw_buffer_store_b64(yu32x2{__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, h1)}, rout, oi, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b64(yu32x2{__builtin_bit_cast(uint32_t, l0), __builtin_bit_cast(uint32_t, l1)}, rout, oi + 16, 0, 0);
-#else
-                    {   // even rows end up with {own hi, partner's hi} = the group's 16 hi bytes, odd rows with {partner's lo, own lo}
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, l0), false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, h1), __builtin_bit_cast(uint32_t, l1), false, false);
-                        __builtin_amdgcn_raw_buffer_store_b128(yu32x4{s0[0], s1[0], s0[1], s1[1]}, rout, oi, 0, 0);
-                    }
-#endif
-                    acc[i][j] = yf32x4{biasn[i].x, biasn[i].y, biasn[i].z, biasn[i].w};
-                    acc[i + 2][j] = yf32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            }
-        };
-#endif
         if (a.res_mode == RES_NONE) write_out(std::integral_constant<int, RES_NONE>{});
         else if (a.res_mode == RES_BEFORE_ACT) write_out(std::integral_constant<int, RES_BEFORE_ACT>{});
         else write_out(std::integral_constant<int, RES_AFTER_ACT>{});
@@ -586,7 +470,6 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
         wcur = wnxt_item;
         par = (par + a.nck) & 1;
     }
-    if (MODE == 1 && !hb) __builtin_amdgcn_s_barrier();   // pairs with group 1's extra barrier
 #ifdef ADAS_H8X_PROF
     if (lane == 0 && grp == 0) {
         unsigned long long* b__ = g_h8x_prof[blockIdx.x & 255];
@@ -610,8 +493,6 @@ __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel(H8XDev a) {
 //            the 256-byte bank row, wherever the run starts.
 //   weights  the H half-chunk's tiles only (rows 0-31 w_hi, rows 32-63 w_lo * 2^11): a tile serves one tap, so the ring has six slots -- the
 //            tap row being read and the next one, whose three tiles go out at the row's first tap and are awaited ahead of its barrier.
-#if !defined(ADAS_H8X_SCALAR_EPI) && !defined(ADAS_H8X_NARROW_ST)
-#define ADAS_H8X_HAS_ONEPASS 1
 constexpr int O8_MAXPIX = 384;
 constexpr int O8_WIN = O8_MAXPIX * 128;            // bytes of one window buffer (a whole chunk)
 constexpr int O8_NWP = O8_MAXPIX / 8 / 8;          // window pieces per wave and chunk (6)
@@ -763,11 +644,7 @@ __device__ __forceinline__ void x8_onepass_body(const H8XDev& a) {
         const int cbn = newtile ? first_cb(has_next ? ti + nslot : ti) : cb + 1;
         const uint32_t ch0 = (uint32_t)(cb * 256) + ch_lane;   // 64 channels = 256 bytes of G8 storage
         // (a wave group whose 32 channels lie past Cout streams and synchronises but reads no fragments and issues no MFMAs: the two-pass body's rule)
-#ifndef ADAS_H8X_NO_TRIM
         const bool wave_on = cb * 64 + hb * 32 < a.cout;
-#else
-        constexpr bool wave_on = true;
-#endif
         Tile nxt = cur;
         uint32_t wnxt_item = 0, apn[4] = {0, 0, 0, 0};
         yu32x4 rraw[4][2];      // residual [pixel tile][channel tile]: one 16-byte piece of the lane's G8 group per entry
@@ -831,14 +708,10 @@ __device__ __forceinline__ void x8_onepass_body(const H8XDev& a) {
                     for (int j = 0; j < 4; ++j) xl[j] = *reinterpret_cast<const hvec8*>(lds8 + (xoff[j][kk] ^ 16u) + winr);
                 }
                 if constexpr (col == 2) {
-#ifdef ADAS_H8X_ONEPASS_DRAIN   // bring-up form: nothing in flight across a tap row's barrier
-                    x8_wait_vm<0>();
-#else
                     constexpr bool with_res = lastc && X8_RES_TAP / 3 == row;
                     if (with_res && has_res) x8_wait_vm<o8_allow(kk) + X8_NBIAS + X8_NRES>();
                     else if (with_res) x8_wait_vm<o8_allow(kk) + X8_NBIAS>();
                     else x8_wait_vm<o8_allow(kk)>();
-#endif
                 }
                 __builtin_amdgcn_s_setprio(1);
                 if (lastc) {
@@ -918,17 +791,16 @@ __device__ __forceinline__ void x8_onepass_body(const H8XDev& a) {
     }
 #endif
 }
-// the body as instantiations of conv_h8x3_kernel itself -- MODE 3, the two-pass count of window pieces (3) -- so that whatever picks this
-// route's launches out of a profile by kernel name (bench.py's roofline among them) finds both bodies under one name
+// the body as instantiations of conv_h8x3_kernel itself -- BODY X8_ONEPASS, the two-pass count of window pieces (3) -- so that whatever picks
+// this route's launches out of a profile by kernel name (bench.py's roofline among them) finds both bodies under one name
 #define X8_ONEPASS_KERNEL(ACT) \
     template <>                \
-    __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel<ACT, 3, false, true, 3>(H8XDev a) { x8_onepass_body<ACT>(a); }
+    __global__ __launch_bounds__(X8_THR, 1) void conv_h8x3_kernel<ACT, X8_ONEPASS, 3>(H8XDev a) { x8_onepass_body<ACT>(a); }
 X8_ONEPASS_KERNEL(ACT_NONE)
 X8_ONEPASS_KERNEL(ACT_SILU)
 X8_ONEPASS_KERNEL(ACT_RELU)
 X8_ONEPASS_KERNEL(ACT_LEAKY)
 #undef X8_ONEPASS_KERNEL
-#endif   // one-pass body
 
 #ifdef ADAS_H8X_PROF
 extern "C" int adas_debug_h8x_prof(unsigned long long* out32, int reset) {
@@ -949,13 +821,13 @@ extern "C" int adas_debug_h8x_prof(unsigned long long* out32, int reset) {
 #endif
 
 // -------------------------------------------------------------------------------------
-static int x8_mode() {   // ADAS_HALO8_X3: 0 off, 1 on (default: synchronisation variant picked per layer), 2 / 3 force variant 2 / 1
+static bool x8_mode() {   // ADAS_HALO8_X3=0: off (every such conv on the generic kernel)
     static int v = -1;
     if (v < 0) {
         const char* e = getenv("ADAS_HALO8_X3");
         v = e ? atoi(e) : 1;
     }
-    return v;
+    return v != 0;
 }
 
 static int x8_policy() {   // ADAS_H8X_PLAN: 1 (default) = smallest window among the most efficient strip widths, 0 = the widest strip (rounds 4-5)
@@ -1049,58 +921,6 @@ hipError_t launch_pack_weights_h8x3(const float* src, void* dst, int cout, int c
     return hipGetLastError();
 }
 
-static bool x8_lhalf() {   // ADAS_H8X_LHALF=0: fetch whole weight tiles for the L half-chunks too (the round-4 / 5 kernel)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("ADAS_H8X_LHALF");
-        v = e ? atoi(e) : 1;
-    }
-    return v != 0;
-}
-
-static bool x8_share() {   // ADAS_H8X_SHARE=0: every half-chunk fetches its own weight tiles (the round-4 / 5 stream)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("ADAS_H8X_SHARE");
-        v = e ? atoi(e) : 1;
-    }
-    return v != 0;
-}
-
-template <int NWP>
-static hipError_t x8_launch_sh(const H8XDev& d, int act, dim3 grid, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_NONE, 2, false, true, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_SILU, 2, false, true, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_RELU, 2, false, true, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_LEAKY, 2, false, true, NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
-    if (act == ACT_SILU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_SILU, 2, false, true, NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else if (act == ACT_RELU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_RELU, 2, false, true, NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else if (act == ACT_LEAKY) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_LEAKY, 2, false, true, NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else hipLaunchKernelGGL((conv_h8x3_kernel<ACT_NONE, 2, false, true, NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    return hipGetLastError();
-}
-
-template <int MODE, bool LH>
-static hipError_t x8_launch(const H8XDev& d, int act, dim3 grid, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_NONE, MODE, LH, false, X8_NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_SILU, MODE, LH, false, X8_NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_RELU, MODE, LH, false, X8_NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_LEAKY, MODE, LH, false, X8_NWP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
-    if (act == ACT_SILU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_SILU, MODE, LH, false, X8_NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else if (act == ACT_RELU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_RELU, MODE, LH, false, X8_NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else if (act == ACT_LEAKY) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_LEAKY, MODE, LH, false, X8_NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    else hipLaunchKernelGGL((conv_h8x3_kernel<ACT_NONE, MODE, LH, false, X8_NWP>), grid, dim3(X8_THR), X8_LDS, st, d);
-    return hipGetLastError();
-}
-
 static bool x8_onepass_on() {   // ADAS_H8X_ONEPASS=0: the two-pass stream everywhere
     static int v = -1;
     if (v < 0) {
@@ -1126,37 +946,32 @@ static bool x8_launch_plan(const ConvArgs& a, HaloPlan* pl) {
 }
 
 // which body an H8X3 launch runs: the one-pass body takes the plans whose windows fit its 384-pixel buffers (three 128-pixel pieces per
-// wave in the two-pass count; its LDS is a compile-time fact, O8_LDS); everything else -- and every launch with ADAS_H8X_ONEPASS=0,
-// ADAS_H8X_SHARE=0 or the ping-pong variant forced -- stays on the two-pass kernel.  No device needed.
+// wave in the two-pass count; its LDS is a compile-time fact, O8_LDS); everything else -- and every launch with ADAS_H8X_ONEPASS=0 --
+// stays on the two-pass kernel.  No device needed.
 bool halo8_x3_onepass(const ConvArgs& a) {
-#ifdef ADAS_H8X_HAS_ONEPASS
     HaloPlan pl;
-    if (!x8_onepass_on() || !x8_share() || x8_mode() == 3) return false;
+    if (!x8_onepass_on()) return false;
     if (!x8_launch_plan(a, &pl)) return false;
     return (pl.maxpix + 127) / 128 <= 3 && pl.maxpix <= O8_MAXPIX;
-#else
-    (void)a;
-    return false;
-#endif
 }
 
-#ifdef ADAS_H8X_HAS_ONEPASS
-static hipError_t x8_launch_onepass(const H8XDev& d, int act, dim3 grid, hipStream_t st) {
+// one body at one count of window pieces, under the launch's activation
+template <int BODY, int NWP>
+static hipError_t x8_launch(const H8XDev& d, int act, dim3 grid, hipStream_t st) {
+    constexpr int lds = BODY == X8_ONEPASS ? O8_LDS : X8_LDS;
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_NONE, 3, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_SILU, 3, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_RELU, 3, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_h8x3_kernel<ACT_LEAKY, 3, false, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (const void* k : {(const void*)conv_h8x3_kernel<ACT_NONE, BODY, NWP>, (const void*)conv_h8x3_kernel<ACT_SILU, BODY, NWP>,
+                              (const void*)conv_h8x3_kernel<ACT_RELU, BODY, NWP>, (const void*)conv_h8x3_kernel<ACT_LEAKY, BODY, NWP>})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    if (act == ACT_SILU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_SILU, 3, false, true, 3>), grid, dim3(X8_THR), O8_LDS, st, d);
-    else if (act == ACT_RELU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_RELU, 3, false, true, 3>), grid, dim3(X8_THR), O8_LDS, st, d);
-    else if (act == ACT_LEAKY) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_LEAKY, 3, false, true, 3>), grid, dim3(X8_THR), O8_LDS, st, d);
-    else hipLaunchKernelGGL((conv_h8x3_kernel<ACT_NONE, 3, false, true, 3>), grid, dim3(X8_THR), O8_LDS, st, d);
+    if (act == ACT_SILU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_SILU, BODY, NWP>), grid, dim3(X8_THR), lds, st, d);
+    else if (act == ACT_RELU) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_RELU, BODY, NWP>), grid, dim3(X8_THR), lds, st, d);
+    else if (act == ACT_LEAKY) hipLaunchKernelGGL((conv_h8x3_kernel<ACT_LEAKY, BODY, NWP>), grid, dim3(X8_THR), lds, st, d);
+    else hipLaunchKernelGGL((conv_h8x3_kernel<ACT_NONE, BODY, NWP>), grid, dim3(X8_THR), lds, st, d);
     return hipGetLastError();
 }
-#endif
 
 hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st) {
     HaloPlan pl;
@@ -1189,21 +1004,11 @@ hipError_t launch_conv_halo8_x3(const ConvArgs& a, hipStream_t st) {
     if (max_slots < 0) { const char* e = getenv("ADAS_H8X_SLOTS"); max_slots = e ? atoi(e) : X8_SLOTS; if (max_slots < 8 || max_slots > 4096) max_slots = X8_SLOTS; }
     const int slots = units8 < max_slots ? units8 : max_slots;
     dim3 grid(8 * slots);
-    const int forced = x8_mode();
-    // (the wave-groups-a-barrier-apart variant, MODE 1, lost to MODE 2 on every layer once both were measured at one commit --
-    // profiles/r06/ab_h8x3.txt: -4.3 % end to end when forced everywhere, +-0.3 % on the nck >= 24 layers it used to take; ADAS_HALO8_X3=3 keeps it reachable)
-    const bool pingpong = forced == 3;
-#ifdef ADAS_H8X_HAS_ONEPASS
-    if (halo8_x3_onepass(a)) return x8_launch_onepass(d, a.act, grid, st);
-#endif
-    if (x8_share() && forced != 3) {   // shared weight tiles (one barrier per tap row), as many window pieces as this plan's windows need
-        const int nwp = (pl.maxpix + 127) / 128;
-        if (nwp <= 3) return x8_launch_sh<3>(d, a.act, grid, st);
-        if (nwp == 4) return x8_launch_sh<4>(d, a.act, grid, st);
-        return x8_launch_sh<5>(d, a.act, grid, st);
-    }
-    if (x8_lhalf()) return pingpong ? x8_launch<1, true>(d, a.act, grid, st) : x8_launch<2, true>(d, a.act, grid, st);
-    return pingpong ? x8_launch<1, false>(d, a.act, grid, st) : x8_launch<2, false>(d, a.act, grid, st);
+    if (halo8_x3_onepass(a)) return x8_launch<X8_ONEPASS, 3>(d, a.act, grid, st);
+    const int nwp = (pl.maxpix + 127) / 128;   // two-pass: as many window pieces as this plan's windows need
+    if (nwp <= 3) return x8_launch<X8_TWOPASS, 3>(d, a.act, grid, st);
+    if (nwp == 4) return x8_launch<X8_TWOPASS, 4>(d, a.act, grid, st);
+    return x8_launch<X8_TWOPASS, 5>(d, a.act, grid, st);
 }
 
 }  // namespace adas
