@@ -985,6 +985,55 @@ int adas_jpegdec_fetch_flags(adas_jpegdec* h, int batch, int32_t* flags);
 int adas_jpegdec_device_view(adas_jpegdec* h, const uint8_t** d_frames_bgr, const int32_t** d_flags);
 
 /* ===================================================================================
+ * Uncompressed camera formats into BGR on the device: the other thing cap.read() (demo.py:261) hides.  A UVC camera delivers YUYV, an
+ * ISP, a hardware video decoder or `ffmpeg -pix_fmt nv12 / yuv420p` NV12 or I420; the frame crosses the bus as 1.5 or 2 bytes per pixel
+ * instead of 3 and is converted where the step reads it.  The rules C1-C7 are csrc/yuv_core.h: chroma by replication, BT.601 limited
+ * range in OpenCV's 20-bit integers (ADAS_YUV_MATRIX_VIDEO, what cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420 / _YUY2 / _UYVY) computes) or
+ * JFIF full range (ADAS_YUV_MATRIX_FULL, the JPEG decoder's rule D8).  One plain launch: capturable, no allocation and no host
+ * synchronisation in adas_yuv_run.
+ * =================================================================================== */
+typedef struct adas_yuv adas_yuv;
+#define ADAS_YUV_NV12 0   /* Y plane, then interleaved U,V pairs (4:2:0) */
+#define ADAS_YUV_NV21 1   /* Y plane, then interleaved V,U pairs */
+#define ADAS_YUV_I420 2   /* Y plane, U plane, V plane; YV12: swap u_offset and v_offset */
+#define ADAS_YUV_YUYV 3   /* packed 4:2:2, bytes Y0 U Y1 V */
+#define ADAS_YUV_UYVY 4   /* packed 4:2:2, bytes U Y0 V Y1 */
+#define ADAS_YUV_MATRIX_VIDEO 0
+#define ADAS_YUV_MATRIX_FULL 1
+typedef struct {
+    int32_t format, matrix;
+    int32_t width, height;        /* width even; height even for the 4:2:0 formats */
+    int64_t frame_stride;         /* bytes from one frame of a batch to the next */
+    int64_t y_offset, y_pitch;    /* the Y plane (the only plane of a packed format): bytes from the frame's start, bytes from row to row */
+    int64_t u_offset, u_pitch;    /* the U plane of I420, the interleaved plane of NV12 / NV21 */
+    int64_t v_offset, v_pitch;    /* the V plane of I420 */
+} adas_yuv_params;
+/* The tight layout of a width x height frame, matrix VIDEO.  Hardware decoders and V4L2 pad rows and plane heights: overwrite the
+ * layout fields with what the source reports. */
+int adas_yuv_default_params(adas_yuv_params* p, int format, int width, int height);
+/* Bytes of one source frame that are read (the end of its last plane); a batch is read up to (batch - 1) * frame_stride + this.  0 for
+ * parameters adas_yuv_create would refuse. */
+int64_t adas_yuv_frame_bytes(const adas_yuv_params* p);
+/* ADAS_ERR_INVALID by name: odd width, odd height for a 4:2:0 format, pitch shorter than a row, plane outside the frame, planes overlap,
+ * max_batch < 1.  Allocates max_batch BGR frames; the two staging buffers of adas_yuv_run_host (max_batch x frame_stride bytes each)
+ * with its first calls. */
+int adas_yuv_create(const adas_yuv_params* p, int max_batch, adas_yuv** out);
+int adas_yuv_destroy(adas_yuv* h);
+/* Frames on the device, frame f at d_src + f * frame_stride, any alignment (a decoder's surface as it is: nothing is padded or copied).
+ * d_dst_bgr [batch][height][width][3] u8, any alignment; NULL: the handle's own frames.  Every byte of the batch's frames is written,
+ * nothing behind them.  When width, the pitches, the offsets, frame_stride and both pointers are multiples of 16 every access is 16
+ * bytes wide; any other geometry goes byte by byte and gives the same pixels. */
+int adas_yuv_run(adas_yuv* h, const uint8_t* d_src, int batch, uint8_t* d_dst_bgr, void* stream);
+/* Frames on the host (pinned for an asynchronous copy: adas_host_alloc): copied on `stream` into one of two device buffers of the
+ * handle, then the run above.  h_src must stay as it is until the stream has passed the copy.  Calls may use different streams: a
+ * buffer is refilled only behind the run that last read it. */
+int adas_yuv_run_host(adas_yuv* h, const uint8_t* h_src, int batch, uint8_t* d_dst_bgr, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_bgr [height][width][3], after the last run's stream has drained.  ADAS_ERR_INVALID for a
+ * frame the last run did not write there. */
+int adas_yuv_fetch(adas_yuv* h, int frame, uint8_t* h_bgr);
+int adas_yuv_device_view(adas_yuv* h, const uint8_t** d_frames_bgr);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1154,6 +1203,18 @@ int adas_pipeline_attach_jpegdec(adas_pipeline* p, adas_jpegdec* jpegdec);
  * adas_pipeline_wait_upload keeps its meaning.  Each frame's flag word: adas_jpegdec_fetch_flags on the attached handle after
  * adas_pipeline_sync; a rejected frame is a black frame to the step. */
 int adas_pipeline_step_jpeg_host(adas_pipeline* p, const uint8_t* const* h_streams, const int64_t* h_lengths, double lane_crop_ratio);
+/* Optional conversion stage in FRONT of the step, outside the capture: the handle adas_pipeline_step_yuv* converts with.  It must hold
+ * n_streams x micro_batch frames; its size is the step's camera geometry and must be that of an attached warp, overlay or JPEG stage
+ * (checked at the step).  yuv == NULL detaches.  Nothing inside the captured step changes; the handle stays the caller's. */
+int adas_pipeline_attach_yuv(adas_pipeline* p, adas_yuv* yuv);
+/* The step from n_streams x micro_batch camera frames in the attached handle's format ALREADY ON THE DEVICE (a decoder's surface): they
+ * are converted on the main stream into the handle's own BGR frames, and those go through adas_pipeline_step_frames: one address, so
+ * one captured step. */
+int adas_pipeline_step_yuv(adas_pipeline* p, const uint8_t* d_src, double lane_crop_ratio);
+/* The same from HOST frames (pinned: adas_host_alloc), (frames - 1) * frame_stride + adas_yuv_frame_bytes bytes: the double buffering
+ * of adas_pipeline_step_frames_host on 1.5 or 2 bytes per pixel -- the copy runs on the copy stream into one of two device buffers
+ * while the previous step still computes, the conversion waits for it.  adas_pipeline_wait_upload keeps its meaning. */
+int adas_pipeline_step_yuv_host(adas_pipeline* p, const uint8_t* h_src, double lane_crop_ratio);
 int adas_pipeline_sync(adas_pipeline* p);
 /* Device time of the last `n` steps' sections in ms (hipEvents on the pipeline stream):
  * [0] detector net, [1] yolo post, [2] lane net, [3] lane decode, [4] tracker, [5] whole step. */

@@ -6,7 +6,7 @@ No window, no video codec: frames come from a seeded synthetic 1280x720 clip (mo
 .npy file of uint8 BGR frames (N, H, W, 3); one summary line per frame.
 
     python tools/demo_headless.py [--frames 30] [--det yolov8n.onnx|.hipm] [--det-type yolov8|efficientdet] [--lane culane_res18.onnx|.hipm] [--video clip.npy]
-                                  [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg]
+                                  [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg] [--from-yuv in.yuv --yuv-format nv12 --yuv-size 1280x720]
 
 Without model paths, seeded random-weight models are built (their detections are noise: the point is the data flow)."""
 import argparse, importlib, os, sys, tempfile, time
@@ -53,6 +53,13 @@ def main():
                     help="demo.py:261 (cap.read) for a camera or file that delivers MJPEG: the inverse of --mjpeg.  PATH is a raw MJPEG file "
                          "(concatenated baseline JPEG streams); every frame is decoded on the device (postproc.JpegDecoder) instead of coming "
                          "from the synthetic clip.  A stream the decoder rejects is reported and shown to the loop as a black frame")
+    ap.add_argument("--from-yuv", default=None, metavar="PATH",
+                    help="demo.py:261 (cap.read) for a source that delivers raw camera frames: PATH holds tightly packed frames of --yuv-size in "
+                         "--yuv-format, back to back (what `ffmpeg -f rawvideo -pix_fmt nv12` writes); every frame is converted to BGR on the "
+                         "device (postproc.YuvConverter) instead of coming from the synthetic clip -- the cv2.cvtColor that cap.read() hides")
+    ap.add_argument("--yuv-format", default="nv12", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
+    ap.add_argument("--yuv-size", default="1280x720", metavar="WxH")
+    ap.add_argument("--yuv-matrix", default="video", choices=["video", "full"])
     a = ap.parse_args()
     work = tempfile.mkdtemp(prefix="adas_demo_")
     effdet = a.det_type == "efficientdet"
@@ -88,6 +95,18 @@ def main():
                     print("stream %d of %s: decoder flags 0x%x" % (k, a.from_mjpeg, flag))
                 yield decoder.image(0)
         frames = decoded()
+    elif a.from_yuv:
+        width, height = (int(v) for v in a.yuv_size.lower().split("x"))
+        decoder = PP.YuvConverter(a.yuv_format, width, height, matrix=a.yuv_matrix)
+        raw = np.fromfile(a.from_yuv, np.uint8)
+        if len(raw) < decoder.frame_bytes:
+            raise SystemExit("%s holds %d bytes, a %dx%d %s frame has %d" % (a.from_yuv, len(raw), width, height, a.yuv_format, decoder.frame_bytes))
+
+        def converted():
+            for k in range(len(raw) // decoder.frame_bytes):
+                decoder.run_host(raw[k * decoder.frame_bytes:(k + 1) * decoder.frame_bytes], 1)
+                yield decoder.image(0)
+        frames = converted()
     else:
         first = frames[0] if frames is not None else next(synthetic_clip(1))
         height, width = first.shape[:2]

@@ -182,6 +182,17 @@ class JpegDecParams(C.Structure):                                            # a
 JPEGDEC_UNSUPPORTED, JPEGDEC_FORMAT, JPEGDEC_SIZE, JPEGDEC_CORRUPT = 1, 2, 4, 8   # ADAS_JPEGDEC_*
 
 
+class YuvParams(C.Structure):                                                # adas_yuv_params
+    _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("frame_stride", C.c_int64),
+                ("y_offset", C.c_int64), ("y_pitch", C.c_int64), ("u_offset", C.c_int64), ("u_pitch", C.c_int64), ("v_offset", C.c_int64),
+                ("v_pitch", C.c_int64)]
+
+
+YUV_FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, "yuyv": 3, "uyvy": 4}             # ADAS_YUV_*
+YUV_MATRICES = {"video": 0, "full": 1}                                       # ADAS_YUV_MATRIX_*
+YUV_LAYOUT_FIELDS = ("frame_stride", "y_offset", "y_pitch", "u_offset", "u_pitch", "v_offset", "v_pitch")
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -379,6 +390,17 @@ _SIGS = {
     "adas_jpegdec_fetch_flags": (C.c_int, [_P, C.c_int, _P]),
     "adas_jpegdec_device_view": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "adas_pipeline_attach_jpegdec": (C.c_int, [_P, _P]),
+    "adas_yuv_default_params": (C.c_int, [C.POINTER(YuvParams), C.c_int, C.c_int, C.c_int]),
+    "adas_yuv_frame_bytes": (C.c_int64, [C.POINTER(YuvParams)]),
+    "adas_yuv_create": (C.c_int, [C.POINTER(YuvParams), C.c_int, C.POINTER(_P)]),
+    "adas_yuv_destroy": (C.c_int, [_P]),
+    "adas_yuv_run": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "adas_yuv_run_host": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "adas_yuv_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_yuv_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_pipeline_attach_yuv": (C.c_int, [_P, _P]),
+    "adas_pipeline_step_yuv": (C.c_int, [_P, _P, C.c_double]),
+    "adas_pipeline_step_yuv_host": (C.c_int, [_P, _P, C.c_double]),
     "adas_pipeline_step_jpeg_host": (C.c_int, [_P, _P, _P, C.c_double]),
     "adas_pipeline_graph_kernels": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "adas_pipeline_attach_overlay": (C.c_int, [_P, _P]),

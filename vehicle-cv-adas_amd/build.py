@@ -28,6 +28,7 @@ UNITS = [
     ("overlay_panels.hip", ["-ffp-contract=off"]),
     ("jpeg_kernels.hip", []),
     ("jpegdec_kernels.hip", []),
+    ("yuv_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

@@ -113,6 +113,15 @@ int jpegdec_stage_host(::adas_jpegdec* h, const uint8_t* const* h_streams, const
 int jpegdec_run_slot(::adas_jpegdec* h, int slot, int batch, uint8_t* d_dst_bgr, void* stream);
 }  // namespace adas
 
+// what adas_pipeline_attach_yuv checks and adas_pipeline_step_yuv* use (yuv_kernels.hip): the handle's geometry and frame_stride (zeros for a
+// null handle) and its own BGR frames
+struct adas_yuv;
+namespace adas {
+void yuv_geometry_of(const ::adas_yuv* h, int* width, int* height, int* max_batch, long long* src_bytes);
+uint8_t* yuv_frames(::adas_yuv* h);
+long long yuv_extent_of(const ::adas_yuv* h);   // bytes of a source frame that are read (adas_yuv_frame_bytes)
+}  // namespace adas
+
 #define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \
         hipError_t e__ = (expr);                                                \

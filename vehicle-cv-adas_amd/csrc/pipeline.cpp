@@ -67,6 +67,13 @@ struct adas_pipeline {
     adas_jpegdec* jpegdec = nullptr;
     hipEvent_t ev_jcopied[2] = {nullptr, nullptr}, ev_jconsumed[2] = {nullptr, nullptr};
     bool jslot_used[2] = {false, false};
+    // step_yuv / step_yuv_host: the conversion in front of the step (adas_pipeline_attach_yuv); the raw frames of a host step go through two
+    // device buffers filled by the copy stream, as step_frames_host's do
+    adas_yuv* yuv = nullptr;
+    uint8_t* yuv_stage[2] = {nullptr, nullptr};
+    size_t yuv_stage_bytes = 0;
+    hipEvent_t ev_ycopied[2] = {nullptr, nullptr}, ev_yconsumed[2] = {nullptr, nullptr};
+    unsigned long long yuv_steps = 0;
 };
 
 using namespace adas;
@@ -513,6 +520,9 @@ int adas_pipeline_destroy(adas_pipeline* p) {
         if (p->ev_consumed[k]) (void)hipEventDestroy(p->ev_consumed[k]);
         if (p->ev_jcopied[k]) (void)hipEventDestroy(p->ev_jcopied[k]);
         if (p->ev_jconsumed[k]) (void)hipEventDestroy(p->ev_jconsumed[k]);
+        if (p->yuv_stage[k]) (void)hipFree(p->yuv_stage[k]);
+        if (p->ev_ycopied[k]) (void)hipEventDestroy(p->ev_ycopied[k]);
+        if (p->ev_yconsumed[k]) (void)hipEventDestroy(p->ev_yconsumed[k]);
     }
     if (p->st_copy) (void)hipStreamDestroy(p->st_copy);
     delete p;
@@ -713,6 +723,72 @@ int adas_pipeline_step_jpeg_host(adas_pipeline* p, const uint8_t* const* h_strea
     ADAS_HIP_TRY(hipEventRecord(p->ev_jconsumed[slot], p->st));
     p->jslot_used[slot] = true;
     return adas_pipeline_step_frames(p, adas::jpegdec_frames(p->jpegdec), jh, jw, lane_crop_ratio);
+}
+
+int adas_pipeline_attach_yuv(adas_pipeline* p, adas_yuv* yuv) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_yuv: null pipeline");
+    if (yuv) {
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int yw = 0, yh = 0, yb = 0;
+        long long ys = 0;
+        adas::yuv_geometry_of(yuv, &yw, &yh, &yb, &ys);
+        ADAS_REQUIRE(yb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_yuv: the conversion handle holds %d frames, a step has %d", yb, frames);
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    if (p->st_copy) ADAS_HIP_TRY(hipStreamSynchronize(p->st_copy));
+    p->yuv = yuv;
+    p->yuv_steps = 0;
+    return ADAS_OK;
+}
+
+int adas_pipeline_step_yuv(adas_pipeline* p, const uint8_t* d_src, double lane_crop_ratio) {
+    ADAS_REQUIRE(p && d_src, ADAS_ERR_INVALID, "adas_pipeline_step_yuv: bad argument");
+    ADAS_REQUIRE(p->yuv, ADAS_ERR_INVALID, "adas_pipeline_step_yuv: no conversion handle attached (adas_pipeline_attach_yuv first)");
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int yw = 0, yh = 0, yb = 0;
+    long long ys = 0;
+    adas::yuv_geometry_of(p->yuv, &yw, &yh, &yb, &ys);
+    int rc = adas_yuv_run(p->yuv, d_src, frames, nullptr, p->st);
+    if (rc) return rc;
+    return adas_pipeline_step_frames(p, adas::yuv_frames(p->yuv), yh, yw, lane_crop_ratio);
+}
+
+int adas_pipeline_step_yuv_host(adas_pipeline* p, const uint8_t* h_src, double lane_crop_ratio) {
+    ADAS_REQUIRE(p && h_src, ADAS_ERR_INVALID, "adas_pipeline_step_yuv_host: bad argument");
+    ADAS_REQUIRE(p->yuv, ADAS_ERR_INVALID, "adas_pipeline_step_yuv_host: no conversion handle attached (adas_pipeline_attach_yuv first)");
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int yw = 0, yh = 0, yb = 0;
+    long long ys = 0;
+    adas::yuv_geometry_of(p->yuv, &yw, &yh, &yb, &ys);
+    const size_t bytes = (size_t)frames * (size_t)ys;
+    if (!p->st_copy) ADAS_HIP_TRY(hipStreamCreateWithFlags(&p->st_copy, hipStreamNonBlocking));
+    for (int k = 0; k < 2; ++k)
+        if (!p->ev_ycopied[k]) {
+            ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_ycopied[k], hipEventDisableTiming));
+            ADAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_yconsumed[k], hipEventDisableTiming));
+        }
+    if (bytes > p->yuv_stage_bytes) {  // (re)size both staging buffers; no captured step reads them
+        ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+        ADAS_HIP_TRY(hipStreamSynchronize(p->st_copy));
+        for (int k = 0; k < 2; ++k) {
+            if (p->yuv_stage[k]) (void)hipFree(p->yuv_stage[k]);
+            p->yuv_stage[k] = nullptr;
+            ADAS_HIP_TRY(hipMalloc((void**)&p->yuv_stage[k], bytes));
+        }
+        p->yuv_stage_bytes = bytes;
+        p->yuv_steps = 0;
+    }
+    const int k = (int)(p->yuv_steps & 1);
+    if (p->yuv_steps >= 2) ADAS_HIP_TRY(hipStreamWaitEvent(p->st_copy, p->ev_yconsumed[k], 0));  // the conversion two steps back is done with buffer k
+    // the last frame is read up to the end of its last plane only: the host need not hold a whole frame_stride behind it
+    ADAS_HIP_TRY(hipMemcpyAsync(p->yuv_stage[k], h_src, bytes - (size_t)ys + (size_t)adas::yuv_extent_of(p->yuv), hipMemcpyHostToDevice, p->st_copy));
+    ADAS_HIP_TRY(hipEventRecord(p->ev_ycopied[k], p->st_copy));
+    ADAS_HIP_TRY(hipStreamWaitEvent(p->st, p->ev_ycopied[k], 0));
+    int rc = adas_yuv_run(p->yuv, p->yuv_stage[k], frames, nullptr, p->st);
+    if (rc) return rc;
+    ADAS_HIP_TRY(hipEventRecord(p->ev_yconsumed[k], p->st));   // the conversion alone reads the buffer: the next copy into it need not wait for the step
+    ++p->yuv_steps;
+    return adas_pipeline_step_frames(p, adas::yuv_frames(p->yuv), yh, yw, lane_crop_ratio);
 }
 
 int adas_pipeline_sync(adas_pipeline* p) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, host_streams, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, host_streams, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -61,14 +61,22 @@ class AdasPipeline:
         files that deliver MJPEG: step_jpeg_host(list_of_bytes) uploads the compressed streams (a few hundred KB per frame in place of
         height * width * 3 bytes), decodes them on the device and runs the step on the decoded frames; input_flags() -> one flag word per
         frame after sync() (a rejected frame is a black frame to the step).  capacity: the most bytes per stream (None:
-        JpegEncoder.bound(width, height)).  Nothing inside the captured step changes."""
+        JpegEncoder.bound(width, height)).  Nothing inside the captured step changes.
+        yuv_input: None, or dict(format="nv12" | "nv21" | "i420" | "yuyv" | "uyvy", matrix="video" | "full", layout=None): a colour conversion
+        in FRONT of the step (postproc.YuvConverter for src_hw frames) for sources that deliver what cameras and decoders really deliver --
+        a UVC camera's YUYV, an ISP's, a hardware decoder's or ffmpeg's NV12 / I420 -- in place of the cv2.cvtColor a caller's host code
+        would run: step_yuv_host(array_or_ptr) uploads the raw frames (1.5 or 2 bytes per pixel in place of 3) on the copy stream,
+        converts them on the device and runs the step on the result; step_yuv(d_ptr) takes frames already on the device, such as a
+        decoder's surface.  matrix: "video" (BT.601 limited range, cv2's; the default) or "full" (JFIF).  layout: None for tightly packed
+        frames, or YuvConverter's dict of byte strides and plane offsets.  Not together with jpeg_input=.  Nothing inside the captured step
+        changes."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
-        self.overlay = self.jpeg_encoder = self.jpeg_decoder = None
+        self.overlay = self.jpeg_encoder = self.jpeg_decoder = self.yuv_converter = None
         if jpeg_input is not None and jpeg_input is not False:
             jpeg_input = {} if jpeg_input is True else dict(jpeg_input)
             unknown = set(jpeg_input) - {"capacity"}
@@ -76,6 +84,17 @@ class AdasPipeline:
                 raise ValueError("jpeg_input= holds unknown keys %s (capacity)" % sorted(unknown))
         else:
             jpeg_input = None
+        if yuv_input is not None:
+            yuv_input = dict(yuv_input)
+            unknown = set(yuv_input) - {"format", "matrix", "layout"}
+            if unknown:
+                raise ValueError("yuv_input= holds unknown keys %s (format, matrix, layout)" % sorted(unknown))
+            if jpeg_input is not None:
+                raise ValueError("yuv_input= and jpeg_input= are two decoders in front of one step: choose the one the source delivers")
+            if yuv_input.get("format", "nv12") not in L.YUV_FORMATS:
+                raise ValueError("yuv_input= format %r is none of %s" % (yuv_input.get("format"), sorted(L.YUV_FORMATS)))
+            if yuv_input.get("matrix", "video") not in L.YUV_MATRICES:
+                raise ValueError("yuv_input= matrix %r is neither \"video\" nor \"full\"" % (yuv_input.get("matrix"),))
         if jpeg is not None:
             unknown = set(dict(jpeg)) - {"quality", "source", "capacity"}
             if unknown:
@@ -184,6 +203,10 @@ class AdasPipeline:
         if jpeg_input is not None:
             self.jpeg_decoder = JpegDecoder(src_hw[1], src_hw[0], n_streams, jpeg_input.get("capacity"))
             L.check(L.lib().adas_pipeline_attach_jpegdec(self.h, self.jpeg_decoder.h))
+        if yuv_input is not None:
+            self.yuv_converter = YuvConverter(yuv_input.get("format", "nv12"), src_hw[1], src_hw[0], yuv_input.get("matrix", "video"),
+                                              yuv_input.get("layout"), n_streams)
+            L.check(L.lib().adas_pipeline_attach_yuv(self.h, self.yuv_converter.h))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -220,6 +243,26 @@ class AdasPipeline:
             raise ValueError("step_jpeg_host got %d streams, a step has %d frames" % (len(streams), self.S * self.B))
         ptrs, lengths, keep = host_streams(streams)
         L.check(L.lib().adas_pipeline_step_jpeg_host(self.h, ptrs, L.ptr(lengths), float(lane_crop_ratio)))
+
+    def step_yuv(self, d_ptr, lane_crop_ratio=0.6):
+        """The same step from n_streams x micro_batch camera frames in yuv_input's format ALREADY ON THE DEVICE (frame f at d_ptr + f *
+        frame_stride): converted into the converter's frames, and the step runs on those.  Needs yuv_input=."""
+        if self.yuv_converter is None:
+            raise ValueError("the pipeline was created without yuv_input=")
+        L.check(L.lib().adas_pipeline_step_yuv(self.h, d_ptr, float(lane_crop_ratio)))
+
+    def step_yuv_host(self, frames, lane_crop_ratio=0.6):
+        """The same step from HOST frames in yuv_input's format: a uint8 array of yuv_converter.batch_bytes(frames per step) bytes, or a host
+        pointer to as many (pinned: _lib.PinnedBuffer, for the upload to overlap the previous step's compute; wait_upload() before
+        refilling it).  Needs yuv_input=."""
+        if self.yuv_converter is None:
+            raise ValueError("the pipeline was created without yuv_input=")
+        if isinstance(frames, np.ndarray):
+            need = self.yuv_converter.batch_bytes(self.S * self.B)
+            if frames.dtype != np.uint8 or not frames.flags.c_contiguous or frames.nbytes < need:
+                raise ValueError("step_yuv_host needs a contiguous uint8 array of at least %d bytes, a step has %d frames" % (need, self.S * self.B))
+            frames = L.ptr(frames)
+        L.check(L.lib().adas_pipeline_step_yuv_host(self.h, frames, float(lane_crop_ratio)))
 
     def input_flags(self):
         """The decoder's flag word of every frame of the last step_jpeg_host (after sync()): int32 [frames], 0 for a clean frame
@@ -290,7 +333,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

@@ -929,6 +929,71 @@ class JpegDecoder:
     __del__ = close
 
 
+class YuvConverter:
+    """Uncompressed camera formats into BGR on the device (adas_yuv_*): "nv12", "nv21", "i420", "yuyv" or "uyvy" frames in -- from the host, or
+    where a decoder left them -- BGR u8 frames out in HBM, where AdasPipeline.step_frames reads them.  What a caller's
+    cv2.cvtColor(frame, cv2.COLOR_YUV2BGR_NV12 / _I420 / _YUY2 / _UYVY) does on host cores.  The rules C1-C7 are csrc/yuv_core.h.
+    matrix: "video" (BT.601 limited range, cv2's) or "full" (JFIF, the JPEG decoder's).  layout: None for tightly packed frames, or a dict
+    out of frame_stride, y_offset, y_pitch, u_offset, u_pitch, v_offset, v_pitch (bytes) over the tight values -- what a decoder or V4L2
+    reports for padded rows and planes; YV12 is "i420" with u_offset and v_offset exchanged.  frame_bytes: the bytes of a frame that are
+    read; a batch of n frames is (n - 1) * params.frame_stride + frame_bytes bytes."""
+
+    def __init__(self, format, width, height, matrix="video", layout=None, max_batch=1):
+        if format not in L.YUV_FORMATS:
+            raise ValueError("format %r is none of %s" % (format, sorted(L.YUV_FORMATS)))
+        if matrix not in L.YUV_MATRICES:
+            raise ValueError("matrix %r is neither \"video\" nor \"full\"" % (matrix,))
+        unknown = set(layout or {}) - set(L.YUV_LAYOUT_FIELDS)
+        if unknown:
+            raise ValueError("layout= holds unknown keys %s (%s)" % (sorted(unknown), ", ".join(L.YUV_LAYOUT_FIELDS)))
+        self.p = L.YuvParams()
+        L.check(L.lib().adas_yuv_default_params(C.byref(self.p), L.YUV_FORMATS[format], int(width), int(height)))
+        self.p.matrix = L.YUV_MATRICES[matrix]
+        for k, v in (layout or {}).items():
+            setattr(self.p, k, int(v))
+        self.format, self.matrix, self.width, self.height, self.max_batch = format, matrix, int(width), int(height), int(max_batch)
+        h = C.c_void_p()
+        L.check(L.lib().adas_yuv_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        self.frame_bytes = int(L.lib().adas_yuv_frame_bytes(C.byref(self.p)))
+
+    def batch_bytes(self, n):
+        return (int(n) - 1) * int(self.p.frame_stride) + self.frame_bytes
+
+    def run_device(self, d_ptr, n, d_dst=None, stream=None):
+        """n frames on the device, frame f at d_ptr + f * frame_stride (any byte).  Asynchronous on `stream`.  d_dst: device pointer of
+        [n][height][width][3] u8 (None: the handle's own frames)."""
+        L.check(L.lib().adas_yuv_run(self.h, d_ptr, int(n), d_dst, stream))
+
+    def run_host(self, frames, n, d_dst=None, stream=None):
+        """n frames on the host: a uint8 array (or a host pointer) of batch_bytes(n) bytes; pinned memory (_lib.PinnedBuffer) makes the copy
+        asynchronous, and the bytes must then stay as they are until `stream` has passed it."""
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8 or not frames.flags.c_contiguous or frames.nbytes < self.batch_bytes(n):
+                raise ValueError("run_host needs a contiguous uint8 array of at least %d bytes" % self.batch_bytes(n))
+            frames = L.ptr(frames)
+        L.check(L.lib().adas_yuv_run_host(self.h, frames, int(n), d_dst, stream))
+
+    def image(self, frame=0):
+        """Frame `frame` of the last run into the handle's own frames: (height, width, 3) uint8 BGR.  Waits for that run."""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        L.check(L.lib().adas_yuv_fetch(self.h, int(frame), L.ptr(out)))
+        return out
+
+    def device_view(self):
+        """Device pointer of the handle's frames [max_batch][height][width][3]."""
+        d = C.c_void_p()
+        L.check(L.lib().adas_yuv_device_view(self.h, C.byref(d)))
+        return d.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_yuv_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
