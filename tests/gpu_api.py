@@ -77,3 +77,44 @@ def track_snapshot(hdr, tracked, lost):
                     tlwh=[float(v) for v in r["tlwh"]])
     return dict(frame_id=int(hdr.frame_id), count=int(hdr.id_count), tracked=[rec(r) for r in tracked],
                 lost=[rec(r) for r in lost])
+
+
+ERR_CAPACITY = -5      # ADAS_ERR_CAPACITY: what a fetch returns, after filling its outputs, once BtHeader.err is set
+
+
+def track_fetch(trk, stream, frame=None):
+    """(snapshot, err) of a stream, or of frame `frame` of the last update_device_frames launch.  Unlike DeviceTracker.fetch this
+    reads a stream whose err bits are set: the C call fills header and tracks and then returns the capacity error."""
+    hdr = L.TrackHeader()
+    recs = np.zeros(2 * trk.max_tracks, L.TRACK_DTYPE)
+    if frame is None:
+        rc = L.lib().adas_bytetrack_fetch(trk.h, stream, C.byref(hdr), L.ptr(recs), len(recs))
+    else:
+        rc = L.lib().adas_bytetrack_fetch_frame(trk.h, stream, frame, C.byref(hdr), L.ptr(recs), len(recs))
+    if rc not in (0, ERR_CAPACITY):
+        L.check(rc)
+    assert (rc == ERR_CAPACITY) == (hdr.err != 0), (rc, hdr.err)
+    nt, nl = hdr.n_tracked, hdr.n_lost
+    return track_snapshot(hdr, recs[:nt], recs[nt:nt + nl]), int(hdr.err)
+
+
+def upload_det_slabs(frames, det_stride, count_stride=1, count_index=0, counts=None):
+    """Per-slab detection frames dict(boxes, scores, ids) in the layout adas_bytetrack_update_device[_frames] reads: slab q holds its
+    rows at xyxy[q][det_stride][4] / score[q][det_stride] / cls[q][det_stride] and its count at counts[q * count_stride + count_index].
+    Rows past a slab's count hold a decoy (a large box of score 0.99) and the other count words -1, so a kernel that read either
+    would show it.  Returns (views for DeviceTracker.update_device*, the buffers to free)."""
+    n = len(frames)
+    xyxy = np.tile(np.asarray([10.0, 10.0, 900.0, 700.0]), (n, det_stride, 1))
+    score = np.full((n, det_stride), 0.99)
+    cls = np.full((n, det_stride), 77, np.int32)
+    cnt = np.full(n * count_stride, -1, np.int32)
+    for q, fr in enumerate(frames):
+        k = len(fr["scores"])
+        assert k <= det_stride
+        if k:
+            xyxy[q, :k] = np.asarray(fr["boxes"], np.float64).reshape(-1, 4)
+            score[q, :k] = np.asarray(fr["scores"], np.float64)
+            cls[q, :k] = np.asarray(fr["ids"], np.int32)
+        cnt[q * count_stride + count_index] = k if counts is None else counts[q]
+    bufs = [L.DeviceBuffer.from_array(a) for a in (xyxy, score, cls, cnt)]
+    return dict(xyxy=bufs[0].ptr, score=bufs[1].ptr, cls=bufs[2].ptr, counts=bufs[3].ptr), bufs

@@ -1206,6 +1206,13 @@ class DeviceTracker:
                                                      views["counts"], det_stride, count_stride, count_index,
                                                      n_streams or self.n_streams, stream))
 
+    def update_device_frames(self, views, det_stride, n_frames, n_streams=None, stream=None, count_stride=4, count_index=2):
+        """One launch over n_frames consecutive frames of every stream: frame f of stream s reads detection slab f * n_streams + s.
+        Every frame's message stays fetchable with fetch_frame()."""
+        L.check(L.lib().adas_bytetrack_update_device_frames(self.h, views["xyxy"], views["score"], views["cls"],
+                                                            views["counts"], det_stride, count_stride, count_index,
+                                                            n_streams or self.n_streams, n_frames, stream))
+
     def fetch(self, stream=0):
         hdr = L.TrackHeader()
         recs = np.zeros(2 * self.max_tracks, L.TRACK_DTYPE)
