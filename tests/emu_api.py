@@ -113,14 +113,15 @@ def lane_geometry(lanes, status, img_h, bird_wh, M, adjust=True):
     for i, l in enumerate(lanes):
         if len(l):
             pts[i, :len(l)] = np.asarray(l, np.int32)
-    hdr = np.zeros(8, np.int32); vals = np.zeros(2); area = np.zeros((2 * img_h, 2), np.int32); bird = np.zeros((4, 128, 2), np.int32)
+    hdr = np.zeros(8, np.int32); vals = np.full(2, np.nan); area = np.zeros((2 * img_h, 2), np.int32); bird = np.zeros((4, 128, 2), np.int32)
     m = np.ascontiguousarray(M, np.float64).reshape(9)
     lib().emu_lane_geometry(_p(cnt), _p(det), _p(pts), int(img_h), int(bird_wh[0]), int(bird_wh[1]), 1 if adjust else 0, _p(m),
                             _p(hdr), _p(vals), _p(area), _p(bird))
     n = int(hdr[1] + hdr[2])
     return dict(area_status=bool(hdr[0]), area_points=area[:n].copy(), n_left=int(hdr[1]), n_right=int(hdr[2]),
                 bird_points=[bird[i, :cnt[i]].copy() for i in range(4)], direction=(None, "L", "R", "F")[hdr[3]],
-                curvature=float(vals[0]) if hdr[3] else None, offset=float(vals[1]) if hdr[3] else None)
+                curvature=float(vals[0]) if hdr[3] else None, offset=float(vals[1]) if hdr[3] else None,
+                raw=(float(vals[0]), float(vals[1])))       # as the routine left them (it writes both on every frame)
 
 
 class Tracker:

@@ -69,6 +69,15 @@ def ufld1(head, cfg, input_wh, src_wh):
         ud.close()
 
 
+def lane_fetch(lg, frame=0):
+    """LaneGeometry.fetch(frame) plus raw = (curvature, offset) as the kernel left them: fetch() hides both when there is no estimate."""
+    out = lg.fetch(frame)
+    res = L.LaneGeometryResult()
+    L.check(L.lib().adas_lane_geometry_fetch(lg.h, frame, C.byref(res), None, None))
+    out["raw"] = (float(res.curvature), float(res.offset))
+    return out
+
+
 def track_snapshot(hdr, tracked, lost):
     def rec(r):
         return dict(track_id=int(r["track_id"]), state=int(r["state"]), is_activated=bool(r["is_activated"]),
