@@ -647,7 +647,7 @@ int adas_analysis_fetch_points(adas_analysis* h, int frame, int32_t* xy, double*
  * in HBM -- UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame (ultrafastLaneDetectorV2.py:196-218, the same in v1), the
  * discs of SingleCamDistanceMeasure.DrawDetectedOnFrame (distanceMeasure.py:98) and PerspectiveTransformation.DrawDetectedOnBirdView
  * (perspectiveTransformation.py:217-226): two whole-frame cv2.addWeighted passes, a cv2.fillPoly and filled cv2.circles.
- * NOT drawn: text (putText / getTextSize); the UI panels are adas_overlay_run_panels below, with a mask of their own; the boxes of the detector and the tracker are the object layer below, the
+ * Text (putText / getTextSize) is adas_overlay_run_text below, from caller-supplied glyph atlases, with a mask of its own; the UI panels are adas_overlay_run_panels below, with a mask of their own; the boxes of the detector and the tracker are the object layer below, the
  * tracker's trajectories and direction marks (thick circles, arrowedLine) the trajectories stage below that.
  * The pixel rules are modelled on OpenCV 4.5's drawing.cpp / arithm and defined in csrc/overlay_core.h (restated in NumPy,
  * tests/overlay_ref.py); parity with a real cv2 build is UNPINNED, and lines are not clipped before they are walked (OpenCV clips the
@@ -831,7 +831,7 @@ int adas_overlay_device_view(adas_overlay* h, const uint8_t** d_bgr);
 int adas_overlay_fetch_flags(adas_overlay* h, int frame, int32_t* flags);
 
 /* The demo's three UI panels on frames that sit in HBM (ControlPanel.DisplayBirdViewPanel / DisplaySignsPanel / DisplayCollisionPanel,
- * demo.py:101-214, painted in that order as at demo.py:307-309), without their putText lines and the FPS string: the bird-view image
+ * demo.py:101-214, painted in that order as at demo.py:307-309), without their putText lines (ADAS_TEXT_PANELS and ADAS_TEXT_LINES of the text block below): the bird-view image
  * resized to W x H = int(src_w * ratio) x int(src_h * ratio) inside a black border in the top right corner; the dimmed, red-framed signs
  * widget in the top left corner with up to two sign sprites; the dimmed, red-framed collision widget below the bird panel with one FCWS
  * sprite.  The pixel and state rules P1-P6 are csrc/overlay_panel_core.h (the signs and collision panels and the bird panel's placement
@@ -901,6 +901,127 @@ int adas_overlay_run_panels_arrays(adas_overlay* h, uint8_t* d_frames_bgr, const
 int adas_overlay_reset_panels(adas_overlay* h, int stream_index);
 /* The record of frame `frame` of the last panel run.  Synchronises. */
 int adas_overlay_fetch_panel_record(adas_overlay* h, int frame, adas_overlay_panel_record* rec);
+
+/* The overlay's text on frames that sit in HBM, from glyph atlases the caller supplies: the class label on its filled background
+ * (yoloDetector.py:180-191; EfficientDet's variant by the style's offsets), the tracker's "name : id" (ObjectTracker/core.py:235-239) and
+ * shadowed "ID: n" (core.py:199-210), the shadowed " 12.34 m" of a distance point (distanceMeasure.py:97-115), the three strings of the
+ * panels (demo.py:173-174, 212) and up to ADAS_TEXT_MAX_LINES caller lines (the FPS and inference-time strings are host timings of a
+ * per-frame loop: the caller prints them as lines).  The font is DATA, like the panels' sprites: a u8 coverage atlas per slot with the
+ * metrics of characters 32..126 -- on a machine with cv2 one putText per glyph renders it (tools/make_font_atlas.py); the repository
+ * ships no font and OpenCV's Hershey tables exist nowhere here.  Which strings exist, where they go, their colours, '%.2f' of a distance
+ * that only exists in HBM, ids and class names are decided on the device by the rules T1-T7 of csrc/overlay_text_core.h (restated in NumPy,
+ * tests/text_ref.py).  Stated divergences: a bitmap font cannot scale, so the two continuously scaled strings pick the slot of a LADDER
+ * (a run of consecutive slots) whose declared scale is nearest the reference's fontScale, the smaller on a tie, d == 0 as scale 1; glyphs
+ * sit on whole pixels where cv2 strokes sub-pixel polylines; text lies over every stage where the reference lets a later box cover an
+ * earlier label; parity with a real cv2 build is UNPINNED.
+ * Text is NOT a stage bit: it has a mask and calls of its own, in place on frames that have been drawn.  Two launches: a layout kernel
+ * (one wave per frame) writes the frame's item list -- rectangles and glyph runs with their clipped boxes, in paint order -- its count and
+ * flags; a draw kernel folds the items over the aligned 16-byte pieces their boxes cover, in order, each byte written by one lane with the
+ * whole sequence applied.  Both are plain launches: capturable. */
+#define ADAS_TEXT_FONTS 16
+#define ADAS_TEXT_MAX_LINES 8
+#define ADAS_TEXT_DETECTIONS 1  /* the mask of adas_overlay_run_text*: painted in this order */
+#define ADAS_TEXT_TRACKS 2
+#define ADAS_TEXT_TRACK_IDS 4
+#define ADAS_TEXT_DISTANCE 8
+#define ADAS_TEXT_PANELS 16
+#define ADAS_TEXT_LINES 32
+#define ADAS_OVERLAY_TEXT_RANGE 1    /* text flags of a frame: a number with |x| >= 2^30, or an origin beyond +-2^30: the item was skipped */
+#define ADAS_OVERLAY_TEXT_OVERFLOW 2 /* more than max_text_items items: the rest, in paint order, were dropped */
+#define ADAS_TEXT_ITEM_RECT 1
+#define ADAS_TEXT_ITEM_RUN 2
+typedef struct {
+    const uint8_t* atlas;        /* host, [cell_h][atlas_w] u8 coverage (0: nothing, 255: the colour); copied to the device */
+    int32_t atlas_w, cell_h;     /* cell_h 1 .. 64 */
+    int32_t baseline_row;        /* the cell's row that sits on the text origin's y */
+    int32_t size_h;              /* what getTextSize returns as the height */
+    int32_t size_w_extra;        /* 16.16: getTextSize's width is (sum of advances + size_w_extra + 0x8000) >> 16 (the thickness term) */
+    int32_t reserved;
+    double scale;                /* the declared fontScale: used by ladders only */
+    int32_t glyph_x[95];         /* characters 32 .. 126: the glyph's first atlas column */
+    int32_t glyph_w[95];         /* its columns, 0 .. 64 (0: draws nothing, e.g. the space) */
+    int32_t bearing_x[95];       /* first column relative to the pen, may be negative */
+    int32_t advance[95];         /* 16.16 */
+} adas_overlay_font;
+typedef struct {
+    double show_ratio;           /* 0.25: the FCWS string starts at column src_w - int(src_w * show_ratio) + fcws_dx */
+    double min_box_area;         /* 10: the gate of the tracks and their ids, as adas_overlay_object_style's */
+    int32_t max_text_items;      /* 256 per frame, 1 .. 1024: a rectangle is one item, a shadowed string two */
+    int32_t det_size_slot, det_label_slot; /* 0, 1: the font the label's box is sized by (face 0, tl / 3) and the one that is drawn */
+    int32_t det_label_dx, det_label_dy;    /* (2, -7); EfficientDet's variant: (0, -5) */
+    int32_t det_box_pad;         /* 3: the box is (xmin, ymin) .. (xmin + tw, ymin - th - 3) */
+    int32_t track_slot, track_dy; /* 2, -10 */
+    int32_t id_first, id_count, id_shadow_first, id_shadow_count; /* ladders: 3, 1 and 4, 1 */
+    int32_t dist_size_first, dist_size_count, dist_first, dist_count, dist_shadow_first, dist_shadow_count; /* 5, 1; 6, 1; 7, 1 */
+    int32_t shadow_dx, shadow_dy; /* (2, 2) */
+    int32_t ldws_slot, lkas_slot, fcws_slot; /* 8, 8, 9 */
+    int32_t ldws_x, ldws_y, lkas_x, lkas_y, fcws_dx, fcws_y; /* (10, 240), (10, 280), (100, 240) */
+    int32_t id_shadow_sub;       /* 30: the id's shadow is the class colour minus 30 per channel, saturated at 0 */
+    uint8_t label_color[3], dist_color[3], dist_shadow_color[3]; /* white, white, (150, 150, 150) */
+    uint8_t offset_colors[4][3], curvature_colors[6][3], collision_colors[4][3]; /* OffsetDict, CurvatureDict, CollisionDict (demo.py:33-54) */
+    uint8_t pad[5];
+} adas_overlay_text_style;
+typedef struct {
+    int32_t kind;                /* ADAS_TEXT_ITEM_* */
+    int32_t source;              /* the ADAS_TEXT_* bit it belongs to */
+    int32_t x, y;                /* a run's origin (putText's org); a rectangle's first corner */
+    int32_t x1, y1;              /* a rectangle's second corner, inclusive, in either order as cv2.rectangle takes them; 0 for a run */
+    int32_t bx0, by0, bx1, by1;  /* every pixel the item can touch, clipped to the frame, half open; all 0: none */
+    int32_t slot;                /* a run's font slot; -1 for a rectangle */
+    uint8_t color[3];            /* channels 0, 1, 2 */
+    uint8_t len;
+    char text[48];
+} adas_overlay_text_item;
+typedef struct {
+    int32_t x, y, slot;
+    uint8_t color[3];
+    uint8_t len;                 /* at most 47 */
+    char text[48];
+} adas_overlay_text_line;
+/* What the layout reads, as raw device arrays, frame q of n_streams * n_frames: survivors d_det_xyxy [q][det_cap][4] + d_det_cls + d_det_counts
+ * as adas_overlay_run_arrays_objects takes them; tracks d_trk_tlwh [q][trk_cap][4] fp64 + d_trk_cls + d_trk_ids + d_trk_counts, with the
+ * newest box of each row's trajectory d_trk_last_tlbr [q][trk_cap][4] fp64 and the trajectory's length d_traj_len (an id is drawn when it
+ * exceeds 1); distance points d_dist_points [q][dist_cap][2] with d_dist_d [q][dist_cap] fp64 and d_dist_counts; the three message types
+ * [q].  Arrays of kinds that are off may be NULL. */
+typedef struct {
+    const int32_t *d_det_xyxy, *d_det_cls, *d_det_counts;
+    const double* d_trk_tlwh;
+    const int32_t *d_trk_cls, *d_trk_ids, *d_trk_counts;
+    const double* d_trk_last_tlbr;
+    const int32_t* d_traj_len;
+    const int32_t* d_dist_points;
+    const double* d_dist_d;
+    const int32_t* d_dist_counts;
+    const int32_t *d_offset_type, *d_curvature_type, *d_collision_type;
+    int32_t det_cap, trk_cap, dist_cap, reserved;
+} adas_overlay_text_arrays;
+int adas_overlay_default_text_style(adas_overlay_text_style* p);
+/* Takes effect with the next run; a captured pipeline step is re-captured.  Waits for the device. */
+int adas_overlay_set_text_style(adas_overlay* h, const adas_overlay_text_style* p);
+/* Font `slot` (0 .. ADAS_TEXT_FONTS - 1), validated once: glyph rectangles inside the atlas, cell_h <= 64, glyph_w <= 64; anything else is
+ * ADAS_ERR_INVALID with a message naming the field.  A character outside 32..126 draws as '?'.  Waits for the device. */
+int adas_overlay_set_font(adas_overlay* h, int slot, const adas_overlay_font* font);
+/* Class names by id for which = ADAS_OVERLAY_DETECTIONS or ADAS_OVERLAY_TRACKS, at most 31 bytes each (longer: ADAS_ERR_INVALID).  An id
+ * outside the table prints 'unknown' (in black on the detections' label box), as get_nms_results does.  The colours are the class colours of
+ * adas_overlay_set_class_colors. */
+int adas_overlay_set_text_labels(adas_overlay* h, int which, const char* const* names, int n);
+/* Up to ADAS_TEXT_MAX_LINES caller strings, drawn last on every frame (ADAS_TEXT_LINES). */
+int adas_overlay_set_text_lines(adas_overlay* h, const adas_overlay_text_line* lines, int n);
+/* The text `mask` (ADAS_TEXT_*) in place on d_frames_bgr [n_streams * n_frames][src_h][src_w][3] (any alignment); NULL: the handle's own
+ * buffer.  ADAS_ERR_INVALID, prefixed with the entry's name: unknown mask bits, a run before any font is set, a bit whose font slot is
+ * empty, a bit whose source is missing, n_streams * n_frames > max_batch. */
+int adas_overlay_run_text_arrays(adas_overlay* h, uint8_t* d_frames_bgr, const adas_overlay_text_arrays* a, int mask, int n_streams, int n_frames,
+                                 void* stream);
+/* The same kernels on the handles' device arrays, where they already sit: DETECTIONS reads `post`'s survivors; TRACKS and TRACK_IDS read
+ * `tracker`'s live table (activated tracked rows over the area gate; the id's origin comes from the newest box of the row's trajectory ring)
+ * -- the table holds the last frame only, so they need n_frames == 1; DISTANCE reads `analysis`' distance points and their metres, PANELS
+ * its frame rows after the three updates.  A bit whose handle is NULL is ADAS_ERR_INVALID, by name; a handle whose bits are off may be NULL. */
+int adas_overlay_run_text(adas_overlay* h, uint8_t* d_frames_bgr, adas_yolo_post* post, struct adas_bytetrack* tracker, const adas_analysis* analysis,
+                          int mask, int n_streams, int n_frames, void* stream);
+/* The item list of frame `frame` of the last text run, in paint order: up to max_items are stored, *n_items is their number.  Synchronises. */
+int adas_overlay_fetch_text_items(adas_overlay* h, int frame, adas_overlay_text_item* items, int max_items, int32_t* n_items);
+/* ADAS_OVERLAY_TEXT_* of frame `frame` of the last text run.  Synchronises. */
+int adas_overlay_fetch_text_flags(adas_overlay* h, int frame, int32_t* flags);
 
 /* ===================================================================================
  * Baseline JPEG on the device: what the demo's loop ends with, vout.write(frame_show) (demo.py:314), as one compressed stream per
@@ -1167,6 +1288,13 @@ int adas_pipeline_set_overlay_stages(adas_pipeline* p, int stages);
  * a missing one is ADAS_ERR_INVALID at the step, by name.  micro_batch > 1 is allowed (the latch walks a stream's frames in order).
  * Cached graphs are dropped. */
 int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels);
+/* The text (ADAS_TEXT_*) the step paints on the overlay's frames, inside the capture (0: none, the step is what it was): one layout launch
+ * behind the overlay's run (adas_overlay_run_text on the step's post, tracker and analysis handles), a draw of the scene's text -- detections,
+ * tracks, ids, distances -- over the stages and under the panels, and a draw of the panel strings and the caller's lines behind the panels;
+ * all of it ahead of the JPEG stage.  Stated divergence: in the reference a label can be covered by a box drawn later; here text lies over
+ * all stages.  Needs adas_overlay_set_font on the attached handle; TRACKS and TRACK_IDS need micro_batch <= 1; a bit without its handle is
+ * refused at the step, by name.  Cached graphs are dropped. */
+int adas_pipeline_set_overlay_text(adas_pipeline* p, int mask);
 /* Optional encoding stage, the step's last launch group on the pipeline's main stream and inside the capture: adas_jpeg_run on all
  * n_streams x micro_batch frames of the step (frames are independent: any micro_batch).  source ADAS_JPEG_SRC_OVERLAY: the attached
  * overlay's own buffer, behind its stages and panels (needs adas_pipeline_attach_overlay first); ADAS_JPEG_SRC_FRAMES: the camera frames

@@ -57,6 +57,11 @@ def main():
                     help="demo.py:261 (cap.read) for a source that delivers raw camera frames: PATH holds tightly packed frames of --yuv-size in "
                          "--yuv-format, back to back (what `ffmpeg -f rawvideo -pix_fmt nv12` writes); every frame is converted to BGR on the "
                          "device (postproc.YuvConverter) instead of coming from the synthetic clip -- the cv2.cvtColor that cap.read() hides")
+    ap.add_argument("--fonts", default=None, metavar="DIR",
+                    help="demo.py:303-305 with their text: DIR holds glyph atlases slot<k>.npz (tools/make_font_atlas.py; slots as in "
+                         "adas_overlay_text_style: 0 / 1 the label's size and text, 2 the tracker's label, 3 / 4 'ID:' and its shadow, 5 / 6 / 7 the "
+                         "distance's size, text and shadow).  The three Draw*OnFrame calls then run on the staged frame in HBM -- boxes, "
+                         "trajectories, discs and text -- and --mjpeg encodes the drawn frames")
     ap.add_argument("--yuv-format", default="nv12", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
     ap.add_argument("--yuv-size", default="1280x720", metavar="WxH")
     ap.add_argument("--yuv-matrix", default="video", choices=["video", "full"])
@@ -113,7 +118,17 @@ def main():
     transformView = A.PerspectiveTransformation((width, height))
     laneDetector.enable_device_geometry(transformView)
     distanceDetector = A.SingleCamDistanceMeasure()
-    objectTracker = D.BYTETracker()
+    fonts = None
+    if a.fonts:
+        import glob, re
+        fonts = {int(re.search(r"slot(\d+)\.npz$", f).group(1)): {k: (v if v.ndim else v.item()) for k, v in np.load(f).items()}
+                 for f in sorted(glob.glob(os.path.join(a.fonts, "slot*.npz")))}
+        if not fonts:
+            raise SystemExit("%s holds no slot<k>.npz atlas" % a.fonts)
+    objectTracker = D.BYTETracker(names=dict(objectDetector.colors_dict), draw_trajectories=True) if fonts else D.BYTETracker()
+    if fonts:
+        for task in (objectDetector, objectTracker, distanceDetector):
+            task.set_text_fonts(fonts)
     analyzeMsg = A.TaskConditions()
 
     encoder = PP.JpegEncoder(width, height, quality=90, capacity=PP.JpegEncoder.bound(width, height)) if a.mjpeg else None
@@ -154,6 +169,11 @@ def main():
             "%.0f m" % vehicle_curvature if vehicle_curvature is not None else "-",
             "%+.2f m" % vehicle_offset if vehicle_offset is not None else "-",
             analyzeMsg.collision_msg.name, analyzeMsg.offset_msg.name, analyzeMsg.curvature_msg.name))
+        if fonts:                                                                         # demo.py:303-305, where the frame sits
+            frame_show = objectDetector.staged_frame
+            objectDetector.DrawDetectedOnFrame(frame_show)
+            objectTracker.DrawTrackedOnFrame(frame_show, False)
+            distanceDetector.DrawDetectedOnFrame(frame_show)
         if encoder is not None:                                                           # demo.py:314
             encoder.run(objectDetector.staged_frame.ptr, 1)
             written += vout.write(encoder.fetch(0))

@@ -167,6 +167,45 @@ class OverlayPanelRecord(C.Structure):                                       # a
                 ("collision_type", C.c_int32), ("reserved", C.c_int32)]
 
 
+TEXT_FONTS, TEXT_MAX_LINES = 16, 8                                           # ADAS_TEXT_FONTS, ADAS_TEXT_MAX_LINES
+TEXT = {"detections": 1, "tracks": 2, "track_ids": 4, "distance": 8, "panels": 16, "lines": 32}   # ADAS_TEXT_*: a mask of its own, painted in this order
+OVERLAY_TEXT_RANGE, OVERLAY_TEXT_OVERFLOW = 1, 2                             # the text flags of a frame
+TEXT_ITEM_RECT, TEXT_ITEM_RUN = 1, 2
+
+
+class OverlayFont(C.Structure):                                              # adas_overlay_font
+    _fields_ = [("atlas", C.c_void_p), ("atlas_w", C.c_int32), ("cell_h", C.c_int32), ("baseline_row", C.c_int32), ("size_h", C.c_int32),
+                ("size_w_extra", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("glyph_x", C.c_int32 * 95), ("glyph_w", C.c_int32 * 95),
+                ("bearing_x", C.c_int32 * 95), ("advance", C.c_int32 * 95)]
+
+
+TEXT_STYLE_INTS = ("max_text_items", "det_size_slot", "det_label_slot", "det_label_dx", "det_label_dy", "det_box_pad", "track_slot", "track_dy", "id_first",
+                   "id_count", "id_shadow_first", "id_shadow_count", "dist_size_first", "dist_size_count", "dist_first", "dist_count", "dist_shadow_first",
+                   "dist_shadow_count", "shadow_dx", "shadow_dy", "ldws_slot", "lkas_slot", "fcws_slot", "ldws_x", "ldws_y", "lkas_x", "lkas_y", "fcws_dx",
+                   "fcws_y", "id_shadow_sub")
+
+
+class OverlayTextStyle(C.Structure):                                         # adas_overlay_text_style
+    _fields_ = [("show_ratio", C.c_double), ("min_box_area", C.c_double)] + [(n, C.c_int32) for n in TEXT_STYLE_INTS] + \
+               [("label_color", C.c_uint8 * 3), ("dist_color", C.c_uint8 * 3), ("dist_shadow_color", C.c_uint8 * 3), ("offset_colors", (C.c_uint8 * 3) * 4),
+                ("curvature_colors", (C.c_uint8 * 3) * 6), ("collision_colors", (C.c_uint8 * 3) * 4), ("pad", C.c_uint8 * 5)]
+
+
+class OverlayTextLine(C.Structure):                                          # adas_overlay_text_line
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("slot", C.c_int32), ("color", C.c_uint8 * 3), ("len", C.c_uint8), ("text", C.c_char * 48)]
+
+
+class OverlayTextArrays(C.Structure):                                        # adas_overlay_text_arrays
+    _fields_ = [(n, C.c_void_p) for n in ("d_det_xyxy", "d_det_cls", "d_det_counts", "d_trk_tlwh", "d_trk_cls", "d_trk_ids", "d_trk_counts", "d_trk_last_tlbr",
+                                          "d_traj_len", "d_dist_points", "d_dist_d", "d_dist_counts", "d_offset_type", "d_curvature_type",
+                                          "d_collision_type")] + \
+               [(n, C.c_int32) for n in ("det_cap", "trk_cap", "dist_cap", "reserved")]
+
+
+TEXT_ITEM_DTYPE = np.dtype([("kind", "i4"), ("source", "i4"), ("x", "i4"), ("y", "i4"), ("x1", "i4"), ("y1", "i4"), ("box", "i4", (4,)), ("slot", "i4"),
+                            ("color", "u1", (3,)), ("len", "u1"), ("text", "S48")])   # adas_overlay_text_item
+
+
 class JpegParams(C.Structure):                                               # adas_jpeg_params
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64)]
 
@@ -371,6 +410,16 @@ _SIGS = {
     "adas_overlay_reset_panels": (C.c_int, [_P, C.c_int]),
     "adas_overlay_fetch_panel_record": (C.c_int, [_P, C.c_int, C.POINTER(OverlayPanelRecord)]),
     "adas_pipeline_set_overlay_panels": (C.c_int, [_P, C.c_int]),
+    "adas_overlay_default_text_style": (C.c_int, [C.POINTER(OverlayTextStyle)]),
+    "adas_overlay_set_text_style": (C.c_int, [_P, C.POINTER(OverlayTextStyle)]),
+    "adas_overlay_set_font": (C.c_int, [_P, C.c_int, C.POINTER(OverlayFont)]),
+    "adas_overlay_set_text_labels": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.c_int]),
+    "adas_overlay_set_text_lines": (C.c_int, [_P, C.POINTER(OverlayTextLine), C.c_int]),
+    "adas_overlay_run_text_arrays": (C.c_int, [_P, _P, C.POINTER(OverlayTextArrays), C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_text": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_pipeline_set_overlay_text": (C.c_int, [_P, C.c_int]),
+    "adas_overlay_fetch_text_items": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32)]),
+    "adas_overlay_fetch_text_flags": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
     "adas_jpeg_default_params": (C.c_int, [C.POINTER(JpegParams)]),
     "adas_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
     "adas_jpeg_create": (C.c_int, [C.POINTER(JpegParams), C.c_int, C.POINTER(_P)]),

@@ -98,6 +98,24 @@ class SingleCamDistanceMeasure:
             pts.append([(xmax + xmin) // 2, ymax, inches / 12 * 0.3048])
         self.distance_points = pts
 
+    def set_text_fonts(self, fonts, **style):
+        """fonts: {slot: atlas} (postproc.LaneOverlay.set_fonts) -- DrawDetectedOnFrame then also draws the shadowed " 12.34 m" under every
+        disc; None: the discs only."""
+        self.text_fonts, self.text_style = fonts, dict(style)
+
+    def DrawDetectedOnFrame(self, frame_show) -> None:
+        """distanceMeasure.py:95-115 on the device (postproc.LaneOverlay): a filled white disc of radius 4 at every distance point and,
+        once set_text_fonts has been given glyph atlases, its shadowed distance text (the ladder's slot nearest max(0.4, min(1, 1 / d))).
+        frame_show: an HxWx3 uint8 ndarray (drawn and copied back) or a StagedFrame.  OpenCV's disc restated, parity unpinned."""
+        if len(self.distance_points) == 0:
+            return
+        from . import postproc            # lazy, as PerspectiveTransformation's
+        if getattr(self, "_painter", None) is None:
+            self._painter = postproc.OverlayPainter()
+        self._painter.distance(frame_show, self.distance_points)
+        if getattr(self, "text_fonts", None):
+            self._painter.text(frame_show, "distance", self.text_fonts, self.text_style, points=self.distance_points)
+
     def calcCollisionPoint(self, poly) -> Optional[list]:
         """Nearest measured object whose foot point lies in (or on) the ego-lane polygon (:76-93)."""
         if not self.distance_points or poly is None or len(poly) == 0:

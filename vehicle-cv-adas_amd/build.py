@@ -26,6 +26,7 @@ UNITS = [
     ("analysis_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_panels.hip", ["-ffp-contract=off"]),
+    ("overlay_text.hip", ["-ffp-contract=off"]),
     ("jpeg_kernels.hip", []),
     ("jpegdec_kernels.hip", []),
     ("yuv_kernels.hip", []),

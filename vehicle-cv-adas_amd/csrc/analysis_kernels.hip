@@ -193,6 +193,7 @@ void analysis_frame_views(const ::adas_analysis* h, const int** frames, int* str
     *pts_xy = h->dev.pts_xy;
     *max_points = h->dev.max_points;
 }
+const double* analysis_points_d(const ::adas_analysis* h) { return h->dev.pts_d; }
 int analysis_bind_birdview(::adas_analysis* h, ::adas_birdview* bird, int n_streams, void* hip_stream) {
     h->bird = bird;
     h->bird_stream = (hipStream_t)hip_stream;

@@ -95,6 +95,22 @@ void overlay_note_stream(::adas_overlay* h, void* stream);
 bool overlay_panels_ready(::adas_overlay* h);
 int overlay_run_panels(const char* who, ::adas_overlay* h, uint8_t* d_frames_bgr, const ::adas_analysis* analysis, const uint8_t* d_bird_bgr, int panels,
                        int n_streams, int n_frames, void* stream);
+// the text (overlay_text.hip) keeps its state -- fonts, style, class names, caller lines, item lists -- behind one pointer of the overlay handle too
+// (overlay_text_slot; adas_overlay_destroy frees it through overlay_text_free).  overlay_class_colors: the packed class colours of the object
+// layer (which: 0 detections, 1 tracks), the colours the labels and ids are drawn in
+struct overlay_text;
+overlay_text** overlay_text_slot(::adas_overlay* h);
+void overlay_text_free(overlay_text* s);
+void overlay_class_colors(const ::adas_overlay* h, int which, const uint32_t** table, int* n);
+// overlay_run_text: the run of adas_overlay_run_text under the caller's name -- the layout of `mask`, then the draw of its kinds in draw_now;
+// overlay_draw_text: the kinds `sources` of that layout, painted later on the handle's own buffer (the pipeline's step paints the panel
+// strings and the lines behind the panels); overlay_text_ready: a font has been set.  analysis_points_d: the metres of the analysis
+// handle's distance points [max_frames][max_points], beside analysis_frame_views' pts_xy
+bool overlay_text_ready(::adas_overlay* h);
+int overlay_run_text(const char* who, ::adas_overlay* h, uint8_t* d_frames_bgr, const ::adas_yolo_post* post, const ::adas_bytetrack* tracker,
+                     const ::adas_analysis* analysis, int mask, int draw_now, int n_streams, int n_frames, void* stream);
+int overlay_draw_text(const char* who, ::adas_overlay* h, int sources, int n_frames_total, void* stream);
+const double* analysis_points_d(const ::adas_analysis* h);
 }  // namespace adas
 // what adas_pipeline_attach_jpeg checks (jpeg_kernels.hip); zeros for a null handle
 struct adas_jpeg;

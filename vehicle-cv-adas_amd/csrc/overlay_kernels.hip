@@ -845,6 +845,7 @@ struct adas_overlay {
     int trj_cap = 0;
     int trj_run_cap = 0, trj_run_frames = 0;                // the last run with the stage: its trk_cap and frames (0: none yet)
     adas::overlay_panels* panels = nullptr;                 // the UI panels' state (overlay_panels.hip), after adas_overlay_set_panels
+    adas::overlay_text* text = nullptr;                     // the text's state (overlay_text.hip), after the first adas_overlay_set_font / _set_text_*
     size_t frame_bytes() const { return (size_t)p.src_h * p.src_w * 3; }
 };
 
@@ -855,6 +856,8 @@ int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_
     return 1;
 }
 overlay_panels** overlay_panel_slot(::adas_overlay* h) { return &h->panels; }
+overlay_text** overlay_text_slot(::adas_overlay* h) { return &h->text; }
+void overlay_class_colors(const ::adas_overlay* h, int which, const uint32_t** table, int* n) { *table = h->colors[which]; *n = h->n_colors[which]; }
 void overlay_note_stream(::adas_overlay* h, void* stream) { h->last = (hipStream_t)stream; }
 }  // namespace adas
 
@@ -1321,6 +1324,7 @@ int adas_overlay_destroy(adas_overlay* h) {
                     (void*)h->trj_cnt})
         if (q) (void)hipFree(q);
     adas::overlay_panels_free(h->panels);
+    adas::overlay_text_free(h->text);
     delete h;
     return ADAS_OK;
 }

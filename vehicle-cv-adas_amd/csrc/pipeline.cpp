@@ -19,6 +19,7 @@ struct adas_pipeline {
     adas_overlay* overlay = nullptr;
     int overlay_stages = -1;   // ADAS_OVERLAY_*; -1: everything the attached handles allow
     int overlay_panels = 0;    // ADAS_PANEL_* painted behind the overlay's run (adas_pipeline_set_overlay_panels); 0: none
+    int overlay_text = 0;      // ADAS_TEXT_* painted over the overlay's frames (adas_pipeline_set_overlay_text); 0: none
     // optional encoding stage, the step's last launch group (adas_pipeline_attach_jpeg): one baseline JPEG stream per frame
     adas_jpeg* jpeg = nullptr;
     int jpeg_source = ADAS_JPEG_SRC_OVERLAY;
@@ -217,6 +218,15 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
                                        {p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
                                         const_cast<uint8_t*>(bird_img), stages, NS, B, st});
         if (rc) return rc;
+        const int text = p->overlay_text, text_scene = ADAS_TEXT_DETECTIONS | ADAS_TEXT_TRACKS | ADAS_TEXT_TRACK_IDS | ADAS_TEXT_DISTANCE;
+        if (text) {   // one layout of every kind; the scene's text is painted now, over the stages and under the panels
+            ADAS_REQUIRE(!(text & (ADAS_TEXT_TRACKS | ADAS_TEXT_TRACK_IDS)) || B <= 1, ADAS_ERR_INVALID,
+                         "the overlay's %s text needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step",
+                         (text & ADAS_TEXT_TRACKS) ? "tracks" : "track_ids", B);
+            rc = adas::overlay_run_text("adas_pipeline_step (overlay text)", p->overlay, nullptr, p->d.detector ? p->d.post : nullptr,
+                                        p->d.detector ? p->d.tracker : nullptr, p->analysis, text, text_scene, NS, B, st);
+            if (rc) return rc;
+        }
         if (p->overlay_panels) {   // directly behind the overlay's run, in place on the frames it just wrote
             const int panels = p->overlay_panels;
             ADAS_REQUIRE(!(panels & (ADAS_PANEL_SIGNS | ADAS_PANEL_COLLISION)) || p->analysis, ADAS_ERR_INVALID,
@@ -227,6 +237,10 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
                 if (rc) return rc;
             }
             rc = adas::overlay_run_panels("adas_pipeline_step (overlay panels)", p->overlay, nullptr, p->analysis, bird_img, panels, NS, B, st);
+            if (rc) return rc;
+        }
+        if (text & ~text_scene) {   // the panel strings and the caller's lines lie over the panels
+            rc = adas::overlay_draw_text("adas_pipeline_step (overlay text)", p->overlay, text & ~text_scene, S, st);
             if (rc) return rc;
         }
     }
@@ -411,6 +425,7 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
     p->overlay = overlay;
     p->overlay_stages = -1;
     p->overlay_panels = 0;
+    p->overlay_text = 0;
     return ADAS_OK;
 }
 
@@ -450,6 +465,17 @@ int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels) {
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
     p->overlay_panels = panels;
+    return ADAS_OK;
+}
+
+int adas_pipeline_set_overlay_text(adas_pipeline* p, int mask) {
+    ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_text: no overlay handle attached");
+    ADAS_REQUIRE(mask >= 0 && !(mask & ~63), ADAS_ERR_INVALID, "adas_pipeline_set_overlay_text: unknown text bits 0x%x", mask);
+    ADAS_REQUIRE(!mask || adas::overlay_text_ready(p->overlay), ADAS_ERR_INVALID,
+                 "adas_pipeline_set_overlay_text: no font set on the attached overlay handle (call adas_overlay_set_font first)");
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->overlay_text = mask;
     return ADAS_OK;
 }
 

@@ -113,8 +113,8 @@ def _colors_dict(class_names):
 
 class _DrawsBoxes:
     """DrawDetectedOnFrame of the two object detectors (yoloDetector.py:170-191, the same in efficientdetDetector.py) on the device: the
-    cornerRect of every RectInfo, in _object_info order, in colors_dict[label] -- (0, 0, 0) for 'unknown'.  The label, its background
-    rectangle and the key points are NOT drawn (getTextSize / putText).  `frame_show` is an HxWx3 uint8 ndarray (uploaded, drawn, copied
+    cornerRect of every RectInfo, in _object_info order, in colors_dict[label] -- (0, 0, 0) for 'unknown'.  The label and its background
+    rectangle are drawn once set_text_fonts has been given glyph atlases (none: the boxes only); the key points are NOT drawn.  `frame_show` is an HxWx3 uint8 ndarray (uploaded, drawn, copied
     back into frame_show[:]) or a StagedFrame (drawn where it sits).  OpenCV's thick line restated (csrc/overlay_core.h D6), parity unpinned."""
 
     def DrawDetectedOnFrame(self, frame_show) -> None:
@@ -125,6 +125,16 @@ class _DrawsBoxes:
         boxes = [info.tolist() for info in self._object_info]
         colors = [self.colors_dict[info.label] if info.label != 'unknown' else (0, 0, 0) for info in self._object_info]
         self._painter.detections(frame_show, boxes, list(range(len(boxes))), colors)
+        if getattr(self, "text_fonts", None):      # set_text_fonts: the label on its filled background, over the boxes
+            self._painter.text(frame_show, "detections", self.text_fonts, self.text_style, det_boxes=boxes,
+                               det_names=[info.label for info in self._object_info], det_colors=colors)
+
+    def set_text_fonts(self, fonts, **style):
+        """fonts: {slot: atlas} (postproc.LaneOverlay.set_fonts; tools/make_font_atlas.py) -- DrawDetectedOnFrame then also draws every
+        label on its filled background (yoloDetector.py:180-191) from the style's det_size_slot / det_label_slot; None: the boxes only, as
+        before.  style: fields of adas_overlay_text_style (EfficientDet's offsets are its class default)."""
+        self.text_fonts = fonts
+        self.text_style = dict(getattr(self, "TEXT_STYLE", {}), **style)
 
     def _close_painter(self):
         if getattr(self, "_painter", None) is not None:
@@ -335,6 +345,8 @@ class EfficientdetDetector(_Defaults, _DrawsBoxes):
     right and bottom only); pouring THOSE weights into this graph would shift every feature map by about a pixel per stride-2 stage against
     the anchor grid.  Valid weights for this container are the seeded synthetic ones (models.py) or a network trained with symmetric
     padding; no importer for the public checkpoint exists."""
+    TEXT_STYLE = dict(det_label_dx=0, det_label_dy=-5)      # efficientdetDetector.py:110
+
     _defaults = {
         "model_path": './models/efficientdet-d0.hipm',
         "model_type": ObjectModelType.EfficientDet,
@@ -868,8 +880,38 @@ class BYTETracker:
         drawn black).  With draw_trajectories False (the default) that is all: show_traject is accepted and ignored.  With draw_trajectories
         True show_traject adds plot_trajectories' circles and plot_directions' lock-on rectangle or shadowed arrow behind each track's box
         -- DrawTrackedOnFrame(frame, False) is then the demo's call (demo.py:304) -- drawn from the device tracker's live state: rows, boxes
-        and trajectory rings are read where they lie in HBM, nothing is fetched.  NOT drawn: the text.  `frame` is an HxWx3 uint8 ndarray
+        and trajectory rings are read where they lie in HBM, nothing is fetched.  The text is drawn once set_text_fonts has been given atlases.  `frame` is an HxWx3 uint8 ndarray
         (drawn and copied back into frame[:]) or a StagedFrame."""
+        self._draw_tracked(frame, show_box, show_traject)
+        if getattr(self, "text_fonts", None) and self._tracked:      # set_text_fonts: "name : id" with the boxes, "ID: n" with the trajectories
+            online = [t for t in self._tracked if t["is_activated"]]
+            kinds = (["tracks"] if show_box else []) + (["track_ids"] if show_traject and self.draw_trajectories else [])
+            if online and kinds:
+                traj = self.trajectories()
+                self._painter = self._painter or OverlayPainter()
+                self._painter.text(frame, kinds, self.text_fonts, dict(self.text_style, min_box_area=float(self.min_box_area)),
+                                   tlwhs=[t["tlwh"] for t in online], trk_names=[self._name_of(t["class_id"]) for t in online],
+                                   trk_colors=[self._color_of(t["class_id"]) for t in online], trk_ids=[t["track_id"] for t in online],
+                                   trajectories=[traj.get(int(t["track_id"]), []) for t in online])
+
+    def set_text_fonts(self, fonts, **style):
+        """fonts: {slot: atlas} -- DrawTrackedOnFrame then also draws plot_bbox's "name : id" (with the boxes) and, with
+        draw_trajectories, plot_trajectories' shadowed "ID: n" (core.py:199-210, 235-239); None: as before."""
+        self.text_fonts, self.text_style = fonts, dict(style)
+
+    def _name_of(self, class_id):
+        try:
+            return str(self.names[class_id])
+        except (KeyError, IndexError, TypeError):
+            return None
+
+    def _color_of(self, class_id):
+        try:
+            return tuple(int(v) for v in self.class_colors[class_id])
+        except (KeyError, IndexError, TypeError):
+            return (0, 0, 0)
+
+    def _draw_tracked(self, frame, show_box, show_traject):
         if self.draw_trajectories:
             if (show_box or show_traject) and self._tracked:
                 if self._painter is None:

@@ -51,6 +51,12 @@ class AdasPipeline:
         overlay["panel_sprites"] = {name: (h, w, 4) uint8 BGRA} (LaneOverlay.set_panels) and optionally overlay["panel_params"] = dict(...).
         "bird" needs birdview=dict(image=True), "signs" and "collision" need analysis=.  overlay_image(frame) then holds the panels;
         self.overlay.panel_record(frame) what was chosen.  The curve_status latch of every stream lives on the device.
+        overlay["text"]: names out of "detections", "track_ids", "tracks", "distance", "panels", "lines" (or a mask) -- the reference's putText
+        lines and the label's filled background, drawn on the device from overlay["fonts"] = {slot: atlas} (LaneOverlay.set_fonts; the
+        atlases are the caller's data, tools/make_font_atlas.py writes them), with overlay["text_style"] = dict(...) (slots, ladders,
+        offsets), overlay["detection_names"] / ["track_names"] (class names by id; colours are detection_colors / track_colors) and
+        overlay["text_lines"] = [(x, y, slot, colour, text)] (at most 8: FPS and the like).  The scene's text lies over every stage and
+        under the panels, the panel strings and the lines over the panels.  self.overlay.text_items(frame) is what was placed.
         jpeg: None, or dict(quality=90, source="overlay" | "frames", capacity=None): every frame of the step as a baseline JPEG stream
         (postproc.JpegEncoder), the step's last launch group -- what the demo's vout.write(frame_show) gets, without the uncompressed frame
         leaving the device: jpeg(frame) -> bytes after sync(), jpeg_lengths() -> (lengths, flags).  source="overlay" (the default) encodes
@@ -133,6 +139,17 @@ class AdasPipeline:
                     (pn_mask, dict(overlay).get("panel_sprites") is not None, "panels= needs panel_sprites= (the BGRA arrays ControlPanel loads)")):
                 if pn_mask & bits and not ok:
                     raise ValueError("the overlay's " + msg)
+            tx_mask = LaneOverlay.text_mask(dict(overlay).get("text") or 0)
+            T = L.TEXT
+            for bits, ok, msg in (
+                    (tx_mask, not (tx_mask & ~63), "text= holds unknown bits 0x%x" % tx_mask),
+                    (tx_mask, dict(overlay).get("fonts"), "text= needs fonts= ({slot: atlas}: the glyph atlases are the caller's data)"),
+                    (T["detections"], det_model, "detections text needs det_model= (the survivors it labels)"),
+                    (T["tracks"] | T["track_ids"], det_model and track, "tracks and track_ids text need det_model= and track=True"),
+                    (T["tracks"] | T["track_ids"], self.B <= 1, "tracks and track_ids text need micro_batch=1: " + live),
+                    (T["distance"] | T["panels"], analysis is not None, "distance and panels text need analysis= (the distances and messages they print)")):
+                if tx_mask & bits and not ok:
+                    raise ValueError("the overlay's " + msg)
         if birdview is not None and (geometry is None or not lane_model):
             raise ValueError("birdview= needs lane_model= and geometry= (its bird_wh is the bird view's img_size)")
         if det_model:
@@ -186,7 +203,8 @@ class AdasPipeline:
             L.check(L.lib().adas_pipeline_attach_analysis(self.h, self.analysis.h))
         if overlay is not None:
             style = {k: v for k, v in dict(overlay).items() if k not in ("stages", "detection_colors", "track_colors", "panels", "panel_sprites",
-                                                                         "panel_params")}
+                                                                         "panel_params", "text", "fonts", "text_style", "text_lines", "detection_names",
+                                                                         "track_names")}
             self.overlay = LaneOverlay(src_hw, self.warp.dst_hw if self.warp else None, n_streams, **style)
             for key, which in (("detection_colors", "detections"), ("track_colors", "tracks")):
                 if dict(overlay).get(key) is not None:
@@ -197,6 +215,17 @@ class AdasPipeline:
             if pn_mask:
                 self.overlay.set_panels(overlay["panel_sprites"], **dict(dict(overlay).get("panel_params") or {}))
                 L.check(L.lib().adas_pipeline_set_overlay_panels(self.h, pn_mask))
+            if dict(overlay).get("fonts"):
+                self.overlay.set_fonts(overlay["fonts"])
+            if dict(overlay).get("text_style"):
+                self.overlay.set_text_style(**dict(overlay["text_style"]))
+            for key, which in (("detection_names", "detections"), ("track_names", "tracks")):
+                if dict(overlay).get(key) is not None:
+                    self.overlay.set_text_labels(which, overlay[key])
+            if dict(overlay).get("text_lines") is not None:
+                self.overlay.set_text_lines(overlay["text_lines"])
+            if tx_mask:
+                L.check(L.lib().adas_pipeline_set_overlay_text(self.h, tx_mask))
         if jpeg is not None:
             self.jpeg_encoder = JpegEncoder(src_hw[1], src_hw[0], int(dict(jpeg).get("quality", 90)), n_streams, dict(jpeg).get("capacity"))
             L.check(L.lib().adas_pipeline_attach_jpeg(self.h, self.jpeg_encoder.h, L.JPEG_SOURCES[jpeg_source]))

@@ -545,8 +545,8 @@ class LaneOverlay:
     class colour) and the box part of BYTETracker.DrawTrackedOnFrame (a thickness-2 rectangle, then the region tinted 0.6 / 0.4 / + 1) per
     activated tracked track over min_box_area.  The trajectories stage ("trajectories", bit 128; off unless asked for) adds what the demo's
     DrawTrackedOnFrame(frame_show, False) draws per such track, behind its box: plot_trajectories' growing circles over the track's last 30
-    boxes and plot_directions' lock-on rectangle or shadowed arrow (csrc/overlay_track_core.h).  Not drawn: text, the label's background
-    rectangle, key points, DrawTransformFrontalViewArea's slanted thick lines.  The demo's three UI panels are painted by set_panels /
+    boxes and plot_directions' lock-on rectangle or shadowed arrow (csrc/overlay_track_core.h).  Text and the label's background rectangle are set_fonts /
+    run_text below (a mask of their own).  Not drawn: key points, DrawTransformFrontalViewArea's slanted thick lines.  The demo's three UI panels are painted by set_panels /
     run_panels below (a mask of their own, not a stage).
     The pixel rules are csrc/overlay_core.h (modelled on OpenCV 4.5; parity with a real cv2 build is unpinned, lines are not clipped
     before they are walked)."""
@@ -761,6 +761,122 @@ class LaneOverlay:
         return {"signs": [L.PANEL_SPRITES[s] for s in r.sign if s >= 0], "collision": L.PANEL_SPRITES[r.collision] if r.collision >= 0 else None,
                 "latch": L.PANEL_LATCHES[r.latch], "offset_type": int(r.offset_type), "curvature_type": int(r.curvature_type),
                 "collision_type": int(r.collision_type)}
+
+    # ---- the text (adas_overlay_*text*, adas_overlay_set_font; rules T1-T7 of csrc/overlay_text_core.h), in place on drawn frames
+    TEXT = L.TEXT
+    FONT_KEYS = ("atlas", "glyph_x", "glyph_w", "bearing_x", "advance", "baseline_row", "size_h", "size_w_extra", "scale")
+
+    @classmethod
+    def text_mask(cls, names):
+        """An int, or names out of "detections", "tracks", "track_ids", "distance", "panels", "lines"."""
+        if isinstance(names, int):
+            return names
+        names = [names] if isinstance(names, str) else list(names)
+        for n in names:
+            if n not in cls.TEXT:
+                raise ValueError("unknown overlay text %r (one of %s)" % (n, ", ".join(cls.TEXT)))
+        m = 0
+        for n in names:
+            m |= cls.TEXT[n]
+        return m
+
+    def set_fonts(self, fonts):
+        """fonts: {slot: atlas}, an atlas a dict (or the .npz tools/make_font_atlas.py writes) of "atlas" (cell_h, atlas_w) uint8 coverage,
+        "glyph_x", "glyph_w", "bearing_x", "advance" (95,) for characters 32..126 (advance in 16.16), "baseline_row", "size_h",
+        "size_w_extra" (16.16) and "scale".  The font is the caller's data: the package ships none."""
+        for slot, f in fonts.items():
+            missing = [k for k in self.FONT_KEYS if k not in f]
+            if missing:
+                raise ValueError("font slot %r lacks %s" % (slot, ", ".join(missing)))
+            a = np.asarray(f["atlas"])
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError("font slot %r: the atlas must be a (cell_h, atlas_w) uint8 array, got %s %s" % (slot, a.dtype, a.shape))
+            a = np.ascontiguousarray(a)
+            t = L.OverlayFont()
+            t.atlas, t.atlas_w, t.cell_h = a.ctypes.data, a.shape[1], a.shape[0]
+            t.baseline_row, t.size_h, t.size_w_extra, t.scale = int(f["baseline_row"]), int(f["size_h"]), int(f["size_w_extra"]), float(f["scale"])
+            for k in ("glyph_x", "glyph_w", "bearing_x", "advance"):
+                v = np.asarray(f[k]).reshape(-1)
+                if v.shape != (95,):
+                    raise ValueError("font slot %r: %s must hold 95 values (characters 32..126), got %d" % (slot, k, v.size))
+                getattr(t, k)[:] = [int(x) for x in v]
+            L.check(L.lib().adas_overlay_set_font(self.h, int(slot), C.byref(t)))
+
+    def set_text_style(self, **style):
+        """Fields of adas_overlay_text_style (slots, ladders as *_first / *_count, offsets, colours, max_text_items) over the last style set."""
+        if not hasattr(self, "ts"):
+            self.ts = L.OverlayTextStyle()
+            L.check(L.lib().adas_overlay_default_text_style(C.byref(self.ts)))
+        for k, v in style.items():
+            if k in ("offset_colors", "curvature_colors", "collision_colors"):
+                for i, c in enumerate(v):
+                    getattr(self.ts, k)[i][:] = [int(x) for x in c]
+            elif k in ("label_color", "dist_color", "dist_shadow_color"):
+                getattr(self.ts, k)[:] = [int(x) for x in v]
+            elif k in L.TEXT_STYLE_INTS or k in ("show_ratio", "min_box_area"):
+                setattr(self.ts, k, v)
+            else:
+                raise TypeError("unknown overlay text style %r" % k)
+        L.check(L.lib().adas_overlay_set_text_style(self.h, C.byref(self.ts)))
+
+    def set_text_labels(self, which, names):
+        """Class names by id for "detections" or "tracks", at most 31 bytes each; an id outside the table prints 'unknown'."""
+        which = self.stage_mask(which)
+        enc = [n.encode("latin-1") if isinstance(n, str) else bytes(n) for n in names]
+        arr = (C.c_char_p * max(1, len(enc)))(*enc)
+        L.check(L.lib().adas_overlay_set_text_labels(self.h, which, arr, len(enc)))
+
+    def set_text_lines(self, lines):
+        """Up to 8 caller strings [(x, y, slot, (b, g, r), text of at most 47 bytes)], drawn last on every frame ("lines")."""
+        lines = list(lines)
+        if len(lines) > L.TEXT_MAX_LINES:
+            raise ValueError("%d text lines, at most %d" % (len(lines), L.TEXT_MAX_LINES))
+        t = (L.OverlayTextLine * max(1, len(lines)))()
+        for i, (x, y, slot, colour, text) in enumerate(lines):
+            b = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+            if len(b) > 47:
+                raise ValueError("text line %d holds %d bytes, at most 47" % (i, len(b)))
+            t[i].x, t[i].y, t[i].slot, t[i].len, t[i].text = int(x), int(y), int(slot), len(b), b
+            t[i].color[:] = [int(c) for c in colour]
+        L.check(L.lib().adas_overlay_set_text_lines(self.h, t, len(lines)))
+
+    def run_text(self, frames_ptr=None, post=None, tracker=None, analysis=None, text=None, n_streams=1, n_frames=1, stream=None):
+        """The text `text` (names or a mask; None: every kind whose handle is given, and "lines") in place on the device frames frames_ptr
+        (None: the handle's own buffer, what run() just wrote), from the handles' device arrays: post= a YoloPost ("detections"), tracker= a
+        DeviceTracker ("tracks", "track_ids": n_frames must be 1), analysis= an Analysis ("distance", "panels")."""
+        if text is None:
+            T = L.TEXT
+            text = ((T["detections"] if post else 0) | ((T["tracks"] | T["track_ids"]) if tracker else 0) |
+                    ((T["distance"] | T["panels"]) if analysis else 0) | T["lines"])
+        h = lambda x: x.h if x else None
+        L.check(L.lib().adas_overlay_run_text(self.h, frames_ptr, h(post), h(tracker), h(analysis), self.text_mask(text), int(n_streams), int(n_frames),
+                                              stream))
+
+    def run_text_arrays(self, frames_ptr=None, text=0, n_streams=1, n_frames=1, stream=None, det_cap=0, trk_cap=0, dist_cap=0, **arrays):
+        """The text `text` (names or a mask) in place on the device frames frames_ptr (None: the handle's own buffer) from raw device pointers,
+        by the field names of adas_overlay_text_arrays without their d_ (det_xyxy, det_cls, det_counts, trk_tlwh, trk_cls, trk_ids, trk_counts,
+        trk_last_tlbr, traj_len, dist_points, dist_d, dist_counts, offset_type, curvature_type, collision_type)."""
+        a = L.OverlayTextArrays(det_cap=int(det_cap), trk_cap=int(trk_cap), dist_cap=int(dist_cap))
+        for k, v in arrays.items():
+            if not hasattr(a, "d_" + k):
+                raise TypeError("unknown text array %r" % k)
+            setattr(a, "d_" + k, v)
+        L.check(L.lib().adas_overlay_run_text_arrays(self.h, frames_ptr, C.byref(a), self.text_mask(text), int(n_streams), int(n_frames), stream))
+
+    def text_items(self, frame=0):
+        """The frame's item list of the last text run, in paint order: a structured array (L.TEXT_ITEM_DTYPE: kind L.TEXT_ITEM_RECT / _RUN,
+        source bit, x, y, x1, y1, box (clipped, half open), slot, color, len, text).  Synchronises."""
+        n = C.c_int32()
+        L.check(L.lib().adas_overlay_fetch_text_items(self.h, int(frame), None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), L.TEXT_ITEM_DTYPE)
+        L.check(L.lib().adas_overlay_fetch_text_items(self.h, int(frame), L.ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def text_flags(self, frame=0):
+        """L.OVERLAY_TEXT_RANGE | L.OVERLAY_TEXT_OVERFLOW of the frame in the last text run.  Synchronises."""
+        f = C.c_int32()
+        L.check(L.lib().adas_overlay_fetch_text_flags(self.h, int(frame), C.byref(f)))
+        return int(f.value)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1005,6 +1121,7 @@ class OverlayPainter:
         self.key = None
         self.buf = None
         self._set = {}
+        self.tov, self.tkey, self._tset, self._tcls = None, None, {}, {}     # the text's own handle (text())
 
     def _target(self, image):
         staged = hasattr(image, "ptr") and not isinstance(image, np.ndarray)
@@ -1107,6 +1224,78 @@ class OverlayPainter:
             for x in (d_b, d_c, d_n):
                 x.free()
 
+    def distance(self, image, points):
+        """SingleCamDistanceMeasure.DrawDetectedOnFrame's discs (distanceMeasure.py:98): a filled white disc of radius 4 at every (x, y)."""
+        pts = np.ascontiguousarray(np.asarray([p[:2] for p in points], np.int64).reshape(-1, 2).astype(np.int32))
+        if len(pts) == 0:
+            return
+        ptr, host = self._target(image)
+        d_p, d_n = L.DeviceBuffer.from_array(pts), L.DeviceBuffer.from_array(np.array([len(pts)], np.int32))
+        try:
+            self.ov.run_arrays(ptr, 1, dist_points=d_p.ptr, dist_cap=len(pts), dist_counts=d_n.ptr, stages=L.OVERLAY_DISTANCE, dst_ptr=ptr)
+            self._finish(ptr, host)
+        finally:
+            d_p.free()
+            d_n.free()
+
+    def text(self, image, kinds, fonts, style=None, det_boxes=(), det_names=(), det_colors=(), tlwhs=(), trk_names=(), trk_colors=(), trk_ids=(),
+             trajectories=(), points=(), types=(0, 0, 0)):
+        """The reference's putText lines of one Draw* call on the caller's image (LaneOverlay.run_text_arrays; rules T1-T7 of
+        csrc/overlay_text_core.h) from `fonts` = {slot: atlas}: kinds out of "detections" (per box its name -- 'unknown' prints black -- and
+        colour), "tracks" / "track_ids" (per row of activated tracked tracks its tlwh, name, colour, id and trajectory), "distance" (points
+        [x, y, metres]), "panels" (types: the offset, curvature and collision messages as ADAS_* ints).  Names are cut to 31 bytes."""
+        mask = LaneOverlay.text_mask(kinds)
+        ptr, host = self._target(image)
+        # the text has a handle of its own: its class tables are (name, colour) pairs, not the box stages' colours, and every setter waits
+        # for the device and makes a captured step of this process re-capture -- so each is called only when what it sets has changed
+        if self.tkey != self.key:
+            if self.tov is not None:
+                self.tov.close()
+            self.tov, self.tkey, self._tset = LaneOverlay(self.key, None, 1), self.key, {}
+            self._tcls = {"detections": [], "tracks": []}
+        if self._tset.get("fonts") is not fonts:
+            self.tov.set_fonts(fonts)
+            self._tset["fonts"] = fonts
+        st = tuple(sorted((style or {}).items(), key=lambda kv: kv[0]))
+        if self._tset.get("text_style", ()) != st:
+            self.tov.set_text_style(**dict(st))
+            self._tset["text_style"] = st
+        cut = lambda n: str(n).encode("latin-1", "replace")[:31]
+
+        def classes(which, names, colors, unknown):
+            """rows -> their indices into the handle's growing table of (name, colour) classes; -1: 'unknown', black"""
+            table, out, grew = self._tcls[which], [], False
+            for n, c in zip(names, colors):
+                if n == unknown:
+                    out.append(-1)
+                    continue
+                key = (cut(n if n is not None else "unknown"), tuple(int(v) for v in c))
+                if key not in table:
+                    table.append(key)
+                    grew = True
+                out.append(table.index(key))
+            if grew:
+                self.tov.set_class_colors(which, [k[1] for k in table])
+                self.tov.set_text_labels(which, [k[0] for k in table])
+            return out
+        d_cls = classes("detections", det_names, det_colors, "unknown") if mask & L.TEXT["detections"] else []
+        t_cls = classes("tracks", trk_names, trk_colors, object()) if mask & (L.TEXT["tracks"] | L.TEXT["track_ids"]) else []
+        nd, nt, npt = len(det_boxes), len(tlwhs), len(points)
+        arrays = dict(det_xyxy=np.asarray(det_boxes, np.int64).reshape(-1, 4).astype(np.int32), det_cls=np.asarray(d_cls, np.int32),
+                      det_counts=np.array([nd], np.int32), trk_tlwh=np.asarray(tlwhs, np.float64).reshape(-1, 4), trk_cls=np.asarray(t_cls, np.int32),
+                      trk_ids=np.asarray(trk_ids, np.int64).astype(np.int32), trk_counts=np.array([nt], np.int32),
+                      trk_last_tlbr=np.array([np.asarray(t[-1], np.float64) if len(t) else np.zeros(4) for t in trajectories], np.float64).reshape(-1, 4),
+                      traj_len=np.array([len(t) for t in trajectories], np.int32), dist_points=np.asarray([p[:2] for p in points], np.int64).reshape(-1, 2).astype(np.int32),
+                      dist_d=np.asarray([p[2] for p in points], np.float64), dist_counts=np.array([npt], np.int32),
+                      offset_type=np.array([types[0]], np.int32), curvature_type=np.array([types[1]], np.int32), collision_type=np.array([types[2]], np.int32))
+        bufs = {k: L.DeviceBuffer.from_array(v if v.size else np.zeros(4, v.dtype)) for k, v in arrays.items()}
+        try:
+            self.tov.run_text_arrays(ptr, mask, 1, 1, None, max(nd, 1), max(nt, 1), max(npt, 1), **{k: b.ptr for k, b in bufs.items()})
+            self._finish(ptr, host)
+        finally:
+            for b in bufs.values():
+                b.free()
+
     def detections(self, image, boxes, classes, colors=(), arm_thickness=5, rect_thickness=1):
         """DrawDetectedOnFrame's boxes: cornerRect on every (xmin, ymin, xmax, ymax) in order, in colors[class] (outside the table: black).
         No label, no label background, no key points."""
@@ -1176,9 +1365,11 @@ class OverlayPainter:
     def close(self):
         if self.ov is not None:
             self.ov.close()
+        if self.tov is not None:
+            self.tov.close()
         if self.buf is not None:
             self.buf.free()
-        self.ov = self.key = self.buf = None
+        self.ov = self.key = self.buf = self.tov = self.tkey = None
 
 
 class DeviceTracker:
