@@ -449,6 +449,10 @@ int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometr
  * the area polygon, frame f's (x, y) pairs at d_area + f * area_stride int32 (room for 2 * img_h points). */
 int adas_lane_geometry_device_views(adas_lane_geometry* h, const int32_t** d_header, const double** d_values, const int32_t** d_area,
                                     int32_t* area_stride);
+/* veh_pos of frame `frame`: the vehicle's bird-view column (lx + rx) / 2 that the offset is measured from (perspectiveTransformation.py:198),
+ * kept per frame in an fp64 device array of its own beside the results above; 0.0 when the frame has no curve (direction NONE).  The
+ * overlay's readouts stage draws its arrow there.  Waits for the handle's last run. */
+int adas_lane_geometry_fetch_veh_pos(adas_lane_geometry* h, int frame, double* veh_pos);
 
 /* -----------------------------------------------------------------------------------
  * Bird-view image: replaces the cv2.warpPerspective calls of PerspectiveTransformation.transformToBirdView /
@@ -829,6 +833,60 @@ int adas_overlay_fetch(adas_overlay* h, int frame, uint8_t* h_bgr);
 int adas_overlay_device_view(adas_overlay* h, const uint8_t** d_bgr);
 /* ADAS_OVERLAY_* flags of frame `frame` of the last run.  Synchronises. */
 int adas_overlay_fetch_flags(adas_overlay* h, int frame, int32_t* flags);
+
+/* The bird view's readouts: what PerspectiveTransformation.calcCurveAndOffset draws on the bird-view image it is handed
+ * (perspectiveTransformation.py:205-213) -- the white arrow at the vehicle's position, the grey arrow at the image centre and the red
+ * strings 'Offset: %.1f m' and 'R : %.1f m' -- under the bird stage's discs (demo.py:292 before :299).  Stage bit 256, accepted only by
+ * the two entries below and by adas_pipeline_set_overlay_readouts: every other entry keeps its mask and refuses it ("unknown stage bits").
+ * The rules R0-R6 are csrc/overlay_readout_core.h (D11 / D12 segments and arrows, T1-T4 numbers and glyphs; the definitions are the
+ * authority, parity with a real cv2 build UNPINNED).  Two stated divergences: a frame is drawn only when its direction is not NONE (the
+ * reference draws whenever both ego lanes are non-empty; the geometry kernel fits only with 3 points each and bird_h > 719), and the
+ * strings are the font of `slot` (adas_overlay_set_font) magnified by the integer `zoom` with nearest-neighbour glyph pixels (a Hershey face
+ * at fontScale 3 is taller than a 64-row cell: the caller renders its atlas at fontScale 3 / zoom).  READOUTS needs BIRD's inputs -- a
+ * handle with a bird size and d_bird_bgr -- and draws in place there, ahead of the discs; without BIRD it draws arrows and strings only.
+ * Two launches (a layout of one wave per frame, a draw that touches only the 16-byte pieces inside the record's boxes), none with the
+ * stage off. */
+#define ADAS_OVERLAY_READOUTS 256
+#define ADAS_OVERLAY_READOUT_RANGE 1 /* readout flags of a frame: an arrow segment beyond +-32767 or a value with |x| >= 2^30 was skipped */
+typedef struct {
+    int32_t slot, zoom;                 /* the font slot, 10; the magnification, 2 (1 .. 4) */
+    int32_t offset_x, offset_y;         /* the origin of 'Offset: ...', (20, 80) */
+    int32_t radius_x, radius_y;         /* the origin of 'R : ...', (20, 180) */
+    uint8_t text_color[3];              /* (0, 0, 255) */
+    uint8_t arrow_a_color[3];           /* the arrow at veh_pos, (255, 255, 255) */
+    uint8_t arrow_b_color[3];           /* the arrow at the image centre, (150, 150, 150) */
+    uint8_t pad[3];
+} adas_overlay_readout_style;
+int adas_overlay_default_readout_style(adas_overlay_readout_style* p);
+/* Takes effect with the next run; a captured pipeline step is re-captured.  zoom outside 1 .. 4 or a slot outside the table is
+ * ADAS_ERR_INVALID.  Allocates the per-frame records on first use: not inside a stream capture. */
+int adas_overlay_set_readout_style(adas_overlay* h, const adas_overlay_readout_style* p);
+/* adas_overlay_run_trajectories plus the readouts stage, which reads `geometry`'s direction (header word 3), curvature and offset and its
+ * veh_pos array.  READOUTS without a bird image, with an empty font slot or without a geometry handle is ADAS_ERR_INVALID, by name. */
+int adas_overlay_run_readouts(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode,
+                              adas_lane_geometry* geometry, adas_analysis* analysis, adas_yolo_post* post, struct adas_bytetrack* tracker,
+                              uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames, void* stream);
+typedef struct {
+    const int32_t* d_direction;         /* [frames]: 0 is NONE, the frame is not drawn */
+    const double *d_veh_pos, *d_curvature, *d_offset; /* [frames] each */
+} adas_overlay_readout_arrays;
+/* adas_overlay_run_arrays_trajectories plus the readouts stage from raw device arrays (r may be NULL with the stage off; with it on all
+ * four arrays are needed). */
+int adas_overlay_run_arrays_readouts(adas_overlay* h, const adas_overlay_arrays* a, const adas_overlay_readout_arrays* r);
+typedef struct {
+    int32_t x, y;                       /* the origin */
+    int32_t box[4];                     /* x0, y0, x1, y1: every pixel it can touch, inside the bird image, half open; zeros: none */
+    int32_t len;                        /* characters of text; 0: not drawn */
+    int32_t skipped;                    /* 1: |value| >= 2^30 */
+    char text[32];
+} adas_overlay_readout_string;
+typedef struct {
+    int32_t drawn, flags;               /* R0's gate; ADAS_OVERLAY_READOUT_* */
+    adas_overlay_track_mark arrows[2];  /* kind ADAS_TRACK_MARK_ARROW, track 0 / 1: at veh_pos, at the centre */
+    adas_overlay_readout_string strings[2]; /* the offset, the radius */
+} adas_overlay_readout_record;
+/* What the device laid out for frame `frame` of the last run with the readouts stage.  Synchronises. */
+int adas_overlay_fetch_readout(adas_overlay* h, int frame, adas_overlay_readout_record* rec);
 
 /* The demo's three UI panels on frames that sit in HBM (ControlPanel.DisplayBirdViewPanel / DisplaySignsPanel / DisplayCollisionPanel,
  * demo.py:101-214, painted in that order as at demo.py:307-309), without their putText lines (ADAS_TEXT_PANELS and ADAS_TEXT_LINES of the text block below): the bird-view image
@@ -1295,6 +1353,11 @@ int adas_pipeline_set_overlay_panels(adas_pipeline* p, int panels);
  * all stages.  Needs adas_overlay_set_font on the attached handle; TRACKS and TRACK_IDS need micro_batch <= 1; a bit without its handle is
  * refused at the step, by name.  Cached graphs are dropped. */
 int adas_pipeline_set_overlay_text(adas_pipeline* p, int mask);
+/* on != 0: the step draws the bird view's readouts (ADAS_OVERLAY_READOUTS) on the attached warp's image, inside the capture and ahead of the
+ * bird stage's discs -- two more launches; 0 (the default): none, the step is what it was.  The bit has this entry of its own because
+ * adas_pipeline_set_overlay_stages keeps its mask.  Needs a font in the readout style's slot on the attached overlay handle (checked
+ * here) and a bird view with its warp (ADAS_ERR_INVALID at the step, by name).  The bird panel then shows them.  Cached graphs are dropped. */
+int adas_pipeline_set_overlay_readouts(adas_pipeline* p, int on);
 /* Optional encoding stage, the step's last launch group on the pipeline's main stream and inside the capture: adas_jpeg_run on all
  * n_streams x micro_batch frames of the step (frames are independent: any micro_batch).  source ADAS_JPEG_SRC_OVERLAY: the attached
  * overlay's own buffer, behind its stages and panels (needs adas_pipeline_attach_overlay first); ADAS_JPEG_SRC_FRAMES: the camera frames

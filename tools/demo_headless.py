@@ -7,6 +7,7 @@ No window, no video codec: frames come from a seeded synthetic 1280x720 clip (mo
 
     python tools/demo_headless.py [--frames 30] [--det yolov8n.onnx|.hipm] [--det-type yolov8|efficientdet] [--lane culane_res18.onnx|.hipm] [--video clip.npy]
                                   [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg] [--from-yuv in.yuv --yuv-format nv12 --yuv-size 1280x720]
+                                  [--readout-font FONT.npz [--readout-zoom 2] [--bird-out bird.npy]]
 
 Without model paths, seeded random-weight models are built (their detections are noise: the point is the data flow)."""
 import argparse, importlib, os, sys, tempfile, time
@@ -62,6 +63,13 @@ def main():
                          "adas_overlay_text_style: 0 / 1 the label's size and text, 2 the tracker's label, 3 / 4 'ID:' and its shadow, 5 / 6 / 7 the "
                          "distance's size, text and shadow).  The three Draw*OnFrame calls then run on the staged frame in HBM -- boxes, "
                          "trajectories, discs and text -- and --mjpeg encodes the drawn frames")
+    ap.add_argument("--readout-font", default=None, metavar="FONT.npz",
+                    help="demo.py:292 with its drawing: calcCurveAndOffset also paints the arrow at the vehicle's position, the arrow at the "
+                         "centre, 'Offset: %%.1f m' and 'R : %%.1f m' on the bird-view image, on the device, in this glyph atlas "
+                         "(tools/make_font_atlas.py --scale 3 / zoom, e.g. --scale 1.5 for zoom 2); DrawDetectedOnBirdView's discs (demo.py:299) "
+                         "then go on top.  The summary line counts the pixels they changed; --bird-out keeps the last image")
+    ap.add_argument("--readout-zoom", type=int, default=2, help="the integer magnification of --readout-font's glyphs, 1 .. 4")
+    ap.add_argument("--bird-out", default=None, metavar="PATH.npy", help="save the last frame's bird-view image (H, W, 3) uint8 as drawn")
     ap.add_argument("--yuv-format", default="nv12", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
     ap.add_argument("--yuv-size", default="1280x720", metavar="WxH")
     ap.add_argument("--yuv-matrix", default="video", choices=["video", "full"])
@@ -129,6 +137,8 @@ def main():
     if fonts:
         for task in (objectDetector, objectTracker, distanceDetector):
             task.set_text_fonts(fonts)
+    if a.readout_font:
+        transformView.set_readout_font({k: (v if v.ndim else v.item()) for k, v in np.load(a.readout_font).items()}, a.readout_zoom)
     analyzeMsg = A.TaskConditions()
 
     encoder = PP.JpegEncoder(width, height, quality=90, capacity=PP.JpegEncoder.bound(width, height)) if a.mjpeg else None
@@ -156,10 +166,15 @@ def main():
         bird = laneDetector.birdview_lanes_points                                         # demo.py:291, left by the device geometry
         # demo.py:292 calls calcCurveAndOffset on the warped image, so this loop does too; laneDetector.curve_and_offset holds the same
         # three values from the device geometry (the two agree to 1e-7 relative, test_lane_detector_device_geometry: the same points, an fp64 fit on either side)
+        bird_before = birdview_show.copy() if a.readout_font else None
         if min(len(bird[1]), len(bird[2])) >= 3:                                          # a parabola needs three points per ego lane
             (vehicle_direction, vehicle_curvature), vehicle_offset = transformView.calcCurveAndOffset(birdview_show, *bird[1:3])
         else:
             (vehicle_direction, vehicle_curvature), vehicle_offset = (None, None), None
+        if a.readout_font:                                                                # demo.py:299, over the readouts
+            readout_px = int((birdview_show != bird_before).any(axis=2).sum())
+            transformView.DrawDetectedOnBirdView(birdview_show, bird, analyzeMsg.offset_msg)
+            print("frame %3d: bird view: readouts changed %d pixels" % (n, readout_px))
         analyzeMsg.UpdateCollisionStatus(vehicle_distance, laneDetector.lane_info.area_status)
         analyzeMsg.UpdateOffsetStatus(vehicle_offset)
         analyzeMsg.UpdateRouteStatus(vehicle_direction, vehicle_curvature)
@@ -179,6 +194,8 @@ def main():
             written += vout.write(encoder.fetch(0))
         n += 1
     dt = time.perf_counter() - t0
+    if a.bird_out and n:
+        np.save(a.bird_out, birdview_show)
     if encoder is not None:
         vout.close(); encoder.close()
         print("%s: %d JPEG streams, %d bytes (%.0f per frame, 1 / %.1f of the raw frames)" % (a.mjpeg, n, written, written / max(n, 1),

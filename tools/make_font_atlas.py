@@ -89,7 +89,10 @@ def main(argv=None):
     ap.add_argument("--cv2", action="store_true")
     ap.add_argument("--face", type=int, default=0)
     ap.add_argument("--thickness", type=int, default=1)
-    ap.add_argument("--scale", type=float, default=1.0, help="the fontScale this atlas stands for (ladders pick by it)")
+    ap.add_argument("--scale", type=float, default=1.0,
+                    help="the fontScale this atlas stands for (ladders pick by it).  The bird view's readouts ('Offset: ...', 'R : ...') are "
+                         "fontScale 3, thickness 5, drawn at an integer zoom: render their atlas at 3 / zoom -- --scale 1.5 for the default zoom 2 "
+                         "(with --cv2: --face 0 --thickness 3 or so; a cell is at most 64 rows)")
     a = ap.parse_args(argv)
     if bool(a.ttf) == bool(a.cv2):
         ap.error("give --ttf FILE or --cv2")

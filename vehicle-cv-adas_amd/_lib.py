@@ -147,7 +147,25 @@ TRACK_MARK_DTYPE = np.dtype([("kind", "i4"), ("track", "i4"), ("x1", "i4"), ("y1
                              ("thickness", "i4"), ("tip", "i4", (4,)), ("color", "u1", (3,)), ("skipped", "u1")])   # adas_overlay_track_mark
 
 
-PANEL_BIRD, PANEL_SIGNS, PANEL_COLLISION = 1, 2, 4                           # adas_overlay_run_panels' mask (no stage bits: a mask of their own)
+OVERLAY_READOUTS = 256                                                       # adas_overlay_run_readouts / _run_arrays_readouts / adas_pipeline_set_overlay_readouts only
+OVERLAY_STAGES["readouts"] = OVERLAY_READOUTS
+OVERLAY_READOUT_RANGE = 1                                                    # the readout flags of a frame
+
+
+class OverlayReadoutStyle(C.Structure):                                      # adas_overlay_readout_style
+    _fields_ = [("slot", C.c_int32), ("zoom", C.c_int32), ("offset_x", C.c_int32), ("offset_y", C.c_int32), ("radius_x", C.c_int32), ("radius_y", C.c_int32),
+                ("text_color", C.c_uint8 * 3), ("arrow_a_color", C.c_uint8 * 3), ("arrow_b_color", C.c_uint8 * 3), ("pad", C.c_uint8 * 3)]
+
+
+class OverlayReadoutArrays(C.Structure):                                     # adas_overlay_readout_arrays
+    _fields_ = [(n, C.c_void_p) for n in ("d_direction", "d_veh_pos", "d_curvature", "d_offset")]
+
+
+READOUT_STRING_DTYPE = np.dtype([("x", "i4"), ("y", "i4"), ("box", "i4", (4,)), ("len", "i4"), ("skipped", "i4"), ("text", "S32")])   # adas_overlay_readout_string
+READOUT_RECORD_DTYPE = np.dtype([("drawn", "i4"), ("flags", "i4"), ("arrows", TRACK_MARK_DTYPE, (2,)), ("strings", READOUT_STRING_DTYPE, (2,))])   # adas_overlay_readout_record
+
+
+PANEL_BIRD, PANEL_SIGNS, PANEL_COLLISION = 1, 2, 4                        # adas_overlay_run_panels' mask (no stage bits: a mask of their own)
 PANELS = {"bird": PANEL_BIRD, "signs": PANEL_SIGNS, "collision": PANEL_COLLISION}
 PANEL_SPRITES = ("fcws_warning", "fcws_prompt", "fcws_normal", "left", "right", "straight", "warn", "lta_left", "lta_right")   # ADAS_PANEL_SPRITE_*
 PANEL_LATCHES = (None, "Left", "Right", "Straight")                          # ADAS_PANEL_LATCH_*: ControlPanel.curve_status
@@ -420,6 +438,13 @@ _SIGS = {
     "adas_pipeline_set_overlay_text": (C.c_int, [_P, C.c_int]),
     "adas_overlay_fetch_text_items": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32)]),
     "adas_overlay_fetch_text_flags": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "adas_overlay_default_readout_style": (C.c_int, [C.POINTER(OverlayReadoutStyle)]),
+    "adas_overlay_set_readout_style": (C.c_int, [_P, C.POINTER(OverlayReadoutStyle)]),
+    "adas_overlay_run_readouts": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "adas_overlay_run_arrays_readouts": (C.c_int, [_P, C.POINTER(OverlayArrays), C.POINTER(OverlayReadoutArrays)]),
+    "adas_overlay_fetch_readout": (C.c_int, [_P, C.c_int, _P]),
+    "adas_pipeline_set_overlay_readouts": (C.c_int, [_P, C.c_int]),
+    "adas_lane_geometry_fetch_veh_pos": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "adas_jpeg_default_params": (C.c_int, [C.POINTER(JpegParams)]),
     "adas_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
     "adas_jpeg_create": (C.c_int, [C.POINTER(JpegParams), C.c_int, C.POINTER(_P)]),

@@ -256,8 +256,12 @@ class PerspectiveTransformation:
 
     def calcCurveAndOffset(self, img, left_lanes, right_lanes):
         """((direction 'L'|'R'|'F', curvature radius in m), offset from the lane centre in m)  (:145-214).
-        `img` may be the bird-view image or just its (H, W[, C]) shape."""
-        shape = img if isinstance(img, (tuple, list)) else img.shape
+        `img` may be the bird-view image or just its (H, W[, C]) shape.  With an image (an ndarray or a StagedFrame) and a font given
+        through set_readout_font, the reference's drawing (:205-213) is done too, in place and on the device, from the values returned:
+        the white arrow at veh_pos, the grey arrow at the centre, 'Offset: %.1f m' and 'R : %.1f m' (postproc.OverlayPainter.readouts).
+        Without a font the image is not touched."""
+        staged = hasattr(img, "ptr") and not isinstance(img, np.ndarray)
+        shape = img if isinstance(img, (tuple, list)) else ((img.height, img.width, 3) if staged else img.shape)
         if left_lanes is None or right_lanes is None or len(left_lanes) == 0 or len(right_lanes) == 0:
             return (None, None), None
         L = np.squeeze(np.asarray(left_lanes))
@@ -283,7 +287,20 @@ class PerspectiveTransformation:
         lane_width = np.absolute(leftx[719] - rightx[719])        # row 719, as the reference hard-codes (:196-199)
         veh_pos = (leftx[719] + rightx[719]) / 2.
         offset = (veh_pos - shape[1] / 2.) * (3.7 / lane_width)
+        font = getattr(self, "_readout_font", None)
+        if font is not None and not isinstance(img, (tuple, list)):
+            from . import postproc            # lazy, as the warp
+            if getattr(self, "_painter", None) is None:
+                self._painter = postproc.OverlayPainter()
+            self._painter.readouts(img, "LRF".index(direction) + 1, float(veh_pos), float(curvature), float(offset), font, self._readout_zoom)
         return (direction, curvature), offset
+
+    def set_readout_font(self, atlas, zoom=2):
+        """The font calcCurveAndOffset draws its two strings in (None: it draws nothing, as before): an atlas as LaneOverlay.set_fonts
+        takes one (tools/make_font_atlas.py --scale 3 / zoom), magnified by the integer zoom 1 .. 4."""
+        if atlas is not None and not 1 <= int(zoom) <= 4:
+            raise ValueError("zoom %r is outside 1 .. 4" % (zoom,))
+        self._readout_font, self._readout_zoom = atlas, int(zoom)
 
 
 # =====================================================================================

@@ -27,6 +27,7 @@ UNITS = [
     ("overlay_kernels.hip", ["-ffp-contract=off"]),
     ("overlay_panels.hip", ["-ffp-contract=off"]),
     ("overlay_text.hip", ["-ffp-contract=off"]),
+    ("overlay_readout.hip", ["-ffp-contract=off"]),
     ("jpeg_kernels.hip", []),
     ("jpegdec_kernels.hip", []),
     ("yuv_kernels.hip", []),

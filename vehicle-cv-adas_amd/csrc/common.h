@@ -111,6 +111,26 @@ int overlay_run_text(const char* who, ::adas_overlay* h, uint8_t* d_frames_bgr, 
                      const ::adas_analysis* analysis, int mask, int draw_now, int n_streams, int n_frames, void* stream);
 int overlay_draw_text(const char* who, ::adas_overlay* h, int sources, int n_frames_total, void* stream);
 const double* analysis_points_d(const ::adas_analysis* h);
+// the bird view's readouts (overlay_readout.hip) keep their state -- style, half-width table, per-frame records -- behind one pointer of the
+// overlay handle as well (overlay_readout_slot; adas_overlay_destroy frees it through overlay_readout_free).  geometry_veh_pos: the geometry
+// handle's veh_pos array [B] (post_kernels.hip).  overlay_text_font_tables: the text state's font table on the device and its host copy
+// (TextFont[ADAS_TEXT_FONTS]; nulls while no font is set).  overlay_readout_sources: what frame q of a run reads -- direction at
+// dir[q * dir_stride], veh_pos at veh[q], curvature and offset at cur[q * val_stride] / off[q * val_stride].  overlay_readout_check: the
+// refusals of a run with the stage, under the caller's name; overlay_readout_launch: its two launches, in place on d_bird
+// [frames][bird_h][bird_w][3]; overlay_readout_reserve: the state, ahead of a captured step
+struct overlay_readout;
+overlay_readout** overlay_readout_slot(::adas_overlay* h);
+void overlay_readout_free(overlay_readout* s);
+const double* geometry_veh_pos(const ::adas_lane_geometry* h);
+void overlay_text_font_tables(::adas_overlay* h, const void** d_fonts, const void** h_fonts);
+struct overlay_readout_sources {
+    const int32_t* dir;
+    const double *veh, *cur, *off;
+    int dir_stride, val_stride;
+};
+int overlay_readout_reserve(::adas_overlay* h);
+int overlay_readout_check(const char* who, ::adas_overlay* h);
+int overlay_readout_launch(::adas_overlay* h, const overlay_readout_sources& s, uint8_t* d_bird, int frames, void* stream);
 }  // namespace adas
 // what adas_pipeline_attach_jpeg checks (jpeg_kernels.hip); zeros for a null handle
 struct adas_jpeg;

@@ -36,6 +36,7 @@ struct LaneGeomFrame {
     int* bird;            // [4][ADAS_LANE_MAXPTS][2]
     double* fx;           // [2][img_h] resampled x of both ego lanes (work area)
     int* idx;             // [2][img_h] kept sample indices (work area)
+    double* veh;          // [1]: the vehicle's bird-view column (lx + rx) / 2 of the offset, 0.0 without a curve; null: not kept
 };
 
 // rows of the least-squares work area one fit needs, and the LDS bytes of a frame (two fits side by side)
@@ -69,18 +70,41 @@ ADAS_DEV void lane_team_sync() {
 #endif
 }
 
+// The team's sum of term(i) over the rows first <= i < n.  A lane adds its own rows i = lane, lane + width, ... in that order and the lanes'
+// sums meet in lane_team_sum's balanced tree (lanes 2k | 2k + 1, then pairs of pairs, ...).  The host build is one lane; with
+// ADAS_LANE_HOST_TEAM defined (tests/hostemu/emu_overlay_readout.cpp) it walks the wave's 64 lanes one after another and adds their sums in
+// that tree, which gives the device's bits: a fit then differs from the device's in nothing.
+template <class Term>
+ADAS_DEV double lane_team_reduce(const LaneTeam& tm, int n, int first, Term term) {
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(ADAS_LANE_HOST_TEAM)
+    (void)tm;
+    double part[64];
+    for (int l = 0; l < 64; ++l) {
+        double s = 0.0;
+        for (int i = l; i < n; i += 64)
+            if (i >= first) s += term(i);
+        part[l] = s;
+    }
+    for (int s = 1; s < 64; s *= 2)
+        for (int l = 0; l < 64; l += 2 * s) part[l] = part[l] + part[l + s];
+    return part[0];
+#else
+    double s = 0.0;
+    for (int i = tm.lane; i < n; i += tm.width)
+        if (i >= first) s += term(i);
+    return lane_team_sum(tm, s);
+#endif
+}
+
 // least-squares parabola v ~ c0 t^2 + c1 t + c2 through n >= 3 points (np.polyfit(t, v, 2)); W: 4n doubles (LDS)
 template <class GetT, class GetV>
 ADAS_DEV void lane_polyfit2(const LaneTeam& tm, int n, GetT t_of, GetV v_of, double* W, double c[3]) {
-    double part[3] = {0.0, 0.0, 0.0};
-    for (int i = tm.lane; i < n; i += tm.width) {  // scale = sqrt((lhs * lhs).sum(axis=0))
-        const double t = t_of(i), t2 = t * t;
-        part[0] += t2 * t2;
-        part[1] += t * t;
-        part[2] += 1.0;
-    }
+    double part[3];  // scale = sqrt((lhs * lhs).sum(axis=0))
+    part[0] = lane_team_reduce(tm, n, 0, [&](int i) { const double t = t_of(i), t2 = t * t; return t2 * t2; });
+    part[1] = lane_team_reduce(tm, n, 0, [&](int i) { const double t = t_of(i); return t * t; });
+    part[2] = lane_team_reduce(tm, n, 0, [&](int) { return 1.0; });
     double sc[3];
-    for (int k = 0; k < 3; ++k) sc[k] = sqrt(lane_team_sum(tm, part[k]));
+    for (int k = 0; k < 3; ++k) sc[k] = sqrt(part[k]);
     for (int i = tm.lane; i < n; i += tm.width) {
         const double t = t_of(i);
         W[4 * i + 0] = (t * t) / sc[0];
@@ -91,10 +115,7 @@ ADAS_DEV void lane_polyfit2(const LaneTeam& tm, int n, GetT t_of, GetV v_of, dou
     lane_team_sync();
     double R[3][4];  // rows of the triangular factor and the transformed right-hand side, identical in every lane
     for (int k = 0; k < 3; ++k) {  // Householder reflections, applied to the trailing columns and the right-hand side
-        double tail = 0.0;
-        for (int i = tm.lane; i < n; i += tm.width)
-            if (i > k) tail += W[4 * i + k] * W[4 * i + k];
-        tail = lane_team_sum(tm, tail);
+        const double tail = lane_team_reduce(tm, n, k + 1, [&](int i) { return W[4 * i + k] * W[4 * i + k]; });
         const double akk = W[4 * k + k];
         const double norm = sqrt(akk * akk + tail);
         const double alpha = akk > 0.0 ? -norm : norm;
@@ -102,10 +123,7 @@ ADAS_DEV void lane_polyfit2(const LaneTeam& tm, int n, GetT t_of, GetV v_of, dou
         const double vn2 = v0 * v0 + tail;
         R[k][k] = alpha;
         for (int j = k + 1; j < 4; ++j) {
-            double dot = 0.0;
-            for (int i = tm.lane; i < n; i += tm.width)
-                if (i > k) dot += W[4 * i + k] * W[4 * i + j];
-            dot = lane_team_sum(tm, dot) + v0 * W[4 * k + j];
+            const double dot = lane_team_reduce(tm, n, k + 1, [&](int i) { return W[4 * i + k] * W[4 * i + j]; }) + v0 * W[4 * k + j];
             const double f = vn2 > 0.0 ? 2.0 * dot / vn2 : 0.0;
             R[k][j] = W[4 * k + j] - f * v0;
             for (int i = tm.lane; i < n; i += tm.width)
@@ -276,9 +294,11 @@ ADAS_DEV void lane_geometry_frame(const Ctx& c, const LaneGeomCfg& cfg, const La
             const double veh_pos = (lx + rx) / 2.;
             f.vals[0] = (fit[12] + fit[13]) / 2;
             f.vals[1] = (veh_pos - (double)cfg.bird_w / 2.) * (3.7 / lane_width);
+            if (f.veh) *f.veh = veh_pos;
         } else {
             f.vals[0] = 0.0;
             f.vals[1] = 0.0;
+            if (f.veh) *f.veh = 0.0;
         }
         f.hdr[0] = area_ok ? 1 : 0;
         f.hdr[1] = n_left;

@@ -846,6 +846,7 @@ struct adas_overlay {
     int trj_run_cap = 0, trj_run_frames = 0;                // the last run with the stage: its trk_cap and frames (0: none yet)
     adas::overlay_panels* panels = nullptr;                 // the UI panels' state (overlay_panels.hip), after adas_overlay_set_panels
     adas::overlay_text* text = nullptr;                     // the text's state (overlay_text.hip), after the first adas_overlay_set_font / _set_text_*
+    adas::overlay_readout* readout = nullptr;               // the bird view's readouts (overlay_readout.hip), after the first style or run with the stage
     size_t frame_bytes() const { return (size_t)p.src_h * p.src_w * 3; }
 };
 
@@ -857,6 +858,7 @@ int overlay_geometry(const ::adas_overlay* h, int* src_h, int* src_w, int* bird_
 }
 overlay_panels** overlay_panel_slot(::adas_overlay* h) { return &h->panels; }
 overlay_text** overlay_text_slot(::adas_overlay* h) { return &h->text; }
+overlay_readout** overlay_readout_slot(::adas_overlay* h) { return &h->readout; }
 void overlay_class_colors(const ::adas_overlay* h, int which, const uint32_t** table, int* n) { *table = h->colors[which]; *n = h->n_colors[which]; }
 void overlay_note_stream(::adas_overlay* h, void* stream) { h->last = (hipStream_t)stream; }
 }  // namespace adas
@@ -1007,6 +1009,7 @@ struct OvRun {                      // one run as overlay_launch takes it; what 
     uint8_t* d_bird;
     OvObjects obj;                  // the boxes (stages 16 / 32)
     OvTracks trk;                   // the tracks (stage 128)
+    adas::overlay_readout_sources ro;   // the readouts (stage 256)
     int stages, frames;
     hipStream_t st;
 };
@@ -1101,6 +1104,10 @@ static int overlay_launch(adas_overlay* h, const OvRun& r) {
         if (!r.dst && frames > h->dst_frames) h->dst_frames = frames;
         h->run_frames = frames;
     }
+    if (stages & ADAS_OVERLAY_READOUTS) {   // two launches of its own, ahead of the discs; without it neither
+        int rc = adas::overlay_readout_launch(h, r.ro, r.d_bird, frames, (void*)st);
+        if (rc) return rc;
+    }
     if (stages & ADAS_OVERLAY_BIRD) {
         OvDev d;
         memset(&d, 0, sizeof(d));
@@ -1132,9 +1139,11 @@ static int overlay_check_run(const char* who, int mask, const adas_overlay* h, l
     ADAS_REQUIRE(h && frames > 0 && frames <= h->max_batch, ADAS_ERR_INVALID, "%s: bad argument (%d frames, the handle holds %d)", who, (int)frames,
                  h ? h->max_batch : 0);
     ADAS_REQUIRE(!(stages & ~mask), ADAS_ERR_INVALID, "%s: unknown stage bits 0x%x", who, stages);
-    ADAS_REQUIRE(!(stages & mask & ~ADAS_OVERLAY_BIRD) || d_src_bgr, ADAS_ERR_INVALID, "%s: the frame stages need source frames", who);
+    ADAS_REQUIRE(!(stages & mask & ~(ADAS_OVERLAY_BIRD | ADAS_OVERLAY_READOUTS)) || d_src_bgr, ADAS_ERR_INVALID, "%s: the frame stages need source frames", who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || (h->p.bird_h > 0 && d_bird_bgr), ADAS_ERR_INVALID,
                  "%s: the bird stage needs a handle created with a bird-view size and a bird-view image", who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_READOUTS) || (h->p.bird_h > 0 && d_bird_bgr), ADAS_ERR_INVALID,
+                 "%s: the readouts stage needs a handle created with a bird-view size and a bird-view image", who);
     return ADAS_OK;
 }
 
@@ -1151,6 +1160,8 @@ int adas::overlay_run_handles(const char* who, int mask, adas_overlay* h, const 
                  adas::decode_num_lanes(a.decode));
     ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_AREA | ADAS_OVERLAY_BIRD)) || a.geometry, ADAS_ERR_INVALID, "%s: the area and bird stages need a geometry handle",
                  who);
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_READOUTS) || a.geometry, ADAS_ERR_INVALID,
+                 "%s: the readouts stage needs a geometry handle (its direction, curvature, offset and veh_pos)", who);
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || a.analysis, ADAS_ERR_INVALID, "%s: the distance stage needs an analysis handle", who);
     ADAS_REQUIRE((!a.decode || frames <= adas::handle_max_batch(a.decode)) && (!a.geometry || frames <= adas::handle_max_batch(a.geometry)),
                  ADAS_ERR_INVALID, "%s: %d frames, the decode handle holds %d, the geometry handle %d", who, (int)frames, adas::handle_max_batch(a.decode),
@@ -1199,6 +1210,13 @@ int adas::overlay_run_handles(const char* who, int mask, adas_overlay* h, const 
         s.poly_n0 = hdr + 1; s.poly_n1 = hdr + 2; s.poly_n_stride = 8;   // area_points = the left points, then the reversed right points
         s.area_on = hdr; s.area_on_stride = 8;
         r.bird_pts = adas::geometry_bird_points(a.geometry); r.bird_cnt = hdr + 4;
+        if (stages & ADAS_OVERLAY_READOUTS) {
+            rc = adas::overlay_readout_check(who, h);
+            if (rc) return rc;
+            r.ro.dir = hdr + 3; r.ro.dir_stride = 8;
+            r.ro.veh = adas::geometry_veh_pos(a.geometry);
+            r.ro.cur = vals; r.ro.off = vals + 1; r.ro.val_stride = 2;
+        }
     }
     if (a.analysis) {
         const int *fr, *pts;
@@ -1215,10 +1233,16 @@ int adas::overlay_run_handles(const char* who, int mask, adas_overlay* h, const 
 }
 
 // every run from raw device arrays: the three adas_overlay_run_arrays* entry points are masks over it
-static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const adas_overlay_arrays& a) {
+static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const adas_overlay_arrays& a, const adas_overlay_readout_arrays* ra = nullptr) {
     const int stages = a.stages;
     int rc = overlay_check_run(who, mask, h, a.n_frames, stages, a.d_src_bgr, a.d_bird_bgr);
     if (rc) return rc;
+    ADAS_REQUIRE(!(stages & ADAS_OVERLAY_READOUTS) || (ra && ra->d_direction && ra->d_veh_pos && ra->d_curvature && ra->d_offset), ADAS_ERR_INVALID,
+                 "%s: the readouts stage needs the direction, veh_pos, curvature and offset arrays", who);
+    if (stages & ADAS_OVERLAY_READOUTS) {
+        rc = adas::overlay_readout_check(who, h);
+        if (rc) return rc;
+    }
     const bool rows_given = a.d_trk_tlwh && a.trk_cap > 0 && a.d_trk_cls && a.d_trk_counts;
     ADAS_REQUIRE(!(stages & ADAS_OVERLAY_TRAJECTORIES) || (rows_given && a.d_traj_tlbr && a.d_traj_len), ADAS_ERR_INVALID,
                  "%s: the trajectories stage needs the tracks' boxes, classes and counts, and their trajectories and lengths", who);
@@ -1258,6 +1282,10 @@ static int overlay_run_raw(const char* who, int mask, adas_overlay* h, const ada
     }
     r.src = a.d_src_bgr; r.dst = a.d_dst_bgr; r.d_bird = a.d_bird_bgr;
     r.bird_pts = a.d_bird_points; r.bird_cnt = a.d_bird_counts; r.bird_cnt_stride = 4;
+    if (stages & ADAS_OVERLAY_READOUTS) {
+        r.ro.dir = ra->d_direction; r.ro.dir_stride = 1;
+        r.ro.veh = ra->d_veh_pos; r.ro.cur = ra->d_curvature; r.ro.off = ra->d_offset; r.ro.val_stride = 1;
+    }
     r.stages = stages; r.frames = a.n_frames; r.st = (hipStream_t)a.stream;
     return overlay_launch(h, r);
 }
@@ -1325,6 +1353,7 @@ int adas_overlay_destroy(adas_overlay* h) {
         if (q) (void)hipFree(q);
     adas::overlay_panels_free(h->panels);
     adas::overlay_text_free(h->text);
+    adas::overlay_readout_free(h->readout);
     delete h;
     return ADAS_OK;
 }
@@ -1394,6 +1423,18 @@ int adas_overlay_run_arrays(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* 
 int adas_overlay_run_arrays_trajectories(adas_overlay* h, const adas_overlay_arrays* a) {
     ADAS_REQUIRE(a, ADAS_ERR_INVALID, "adas_overlay_run_arrays_trajectories: null argument");
     return overlay_run_raw("adas_overlay_run_arrays_trajectories", 63 | ADAS_OVERLAY_TRAJECTORIES, h, *a);
+}
+
+int adas_overlay_run_readouts(adas_overlay* h, const uint8_t* d_src_bgr, uint8_t* d_dst_bgr, const adas_ufld_decode* decode, adas_lane_geometry* geometry,
+                              adas_analysis* analysis, adas_yolo_post* post, adas_bytetrack* tracker, uint8_t* d_bird_bgr, int stages, int n_streams, int n_frames,
+                              void* stream) {
+    return adas::overlay_run_handles("adas_overlay_run_readouts", 63 | ADAS_OVERLAY_TRAJECTORIES | ADAS_OVERLAY_READOUTS, h,
+                                     {d_src_bgr, d_dst_bgr, decode, geometry, analysis, post, tracker, d_bird_bgr, stages, n_streams, n_frames, stream});
+}
+
+int adas_overlay_run_arrays_readouts(adas_overlay* h, const adas_overlay_arrays* a, const adas_overlay_readout_arrays* r) {
+    ADAS_REQUIRE(a, ADAS_ERR_INVALID, "adas_overlay_run_arrays_readouts: null argument");
+    return overlay_run_raw("adas_overlay_run_arrays_readouts", 63 | ADAS_OVERLAY_TRAJECTORIES | ADAS_OVERLAY_READOUTS, h, *a, r);
 }
 
 int adas_overlay_fetch_track_marks(adas_overlay* h, int frame, adas_overlay_track_mark* marks, int max_marks, int32_t* n_marks) {

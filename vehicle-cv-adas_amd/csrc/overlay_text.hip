@@ -360,6 +360,12 @@ static int text_launch(const char* who, adas_overlay* h, uint8_t* d_frames_bgr, 
     return text_draw(s, d_frames_bgr, mask & draw_now, (int)frames, strm);
 }
 
+void adas::overlay_text_font_tables(adas_overlay* h, const void** d_fonts, const void** h_fonts) {
+    adas::overlay_text* s = h ? *adas::overlay_text_slot(h) : nullptr;
+    *d_fonts = s ? s->d_fonts : nullptr;
+    *h_fonts = s ? s->fonts : nullptr;
+}
+
 bool adas::overlay_text_ready(adas_overlay* h) { return h && *adas::overlay_text_slot(h) && (*adas::overlay_text_slot(h))->n_fonts > 0; }
 
 // the run of adas_overlay_run_text under the caller's name: the sources where the handles keep them

@@ -20,6 +20,7 @@ struct adas_pipeline {
     int overlay_stages = -1;   // ADAS_OVERLAY_*; -1: everything the attached handles allow
     int overlay_panels = 0;    // ADAS_PANEL_* painted behind the overlay's run (adas_pipeline_set_overlay_panels); 0: none
     int overlay_text = 0;      // ADAS_TEXT_* painted over the overlay's frames (adas_pipeline_set_overlay_text); 0: none
+    int overlay_readouts = 0;  // ADAS_OVERLAY_READOUTS or 0 (adas_pipeline_set_overlay_readouts): the bird view's arrows and strings
     // optional encoding stage, the step's last launch group (adas_pipeline_attach_jpeg): one baseline JPEG stream per frame
     adas_jpeg* jpeg = nullptr;
     int jpeg_source = ADAS_JPEG_SRC_OVERLAY;
@@ -194,8 +195,10 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             stages = ADAS_OVERLAY_LANES | ADAS_OVERLAY_AREA | (p->analysis ? ADAS_OVERLAY_DISTANCE : 0) | (p->bird_warp ? ADAS_OVERLAY_BIRD : 0);
         ADAS_REQUIRE(!(stages & ADAS_OVERLAY_DISTANCE) || p->analysis, ADAS_ERR_INVALID, "the overlay's distance stage needs an attached analysis handle");
         ADAS_REQUIRE(!(stages & ADAS_OVERLAY_BIRD) || p->bird_warp, ADAS_ERR_INVALID, "the overlay's bird stage needs an attached bird view with its warp");
+        ADAS_REQUIRE(!p->overlay_readouts || p->bird_warp, ADAS_ERR_INVALID, "the overlay's readouts stage needs an attached bird view with its warp");
+        stages |= p->overlay_readouts;
         const uint8_t* bird_img = nullptr;
-        if (stages & ADAS_OVERLAY_BIRD) {
+        if (stages & (ADAS_OVERLAY_BIRD | ADAS_OVERLAY_READOUTS)) {
             int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0, wh = 0, ww = 0;
             (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
             adas::warp_dst_geometry(p->bird_warp, &wh, &ww);
@@ -214,7 +217,7 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
         ADAS_REQUIRE(!(stages & (ADAS_OVERLAY_TRACKS | ADAS_OVERLAY_TRAJECTORIES)) || B <= 1, ADAS_ERR_INVALID,
                      "the overlay's %s stage needs micro_batch <= 1 (got %d): the tracker's live table holds only the last frame of a step",
                      (stages & ADAS_OVERLAY_TRACKS) ? "tracks" : "trajectories", B);
-        rc = adas::overlay_run_handles("adas_pipeline_step (overlay)", 63 | ADAS_OVERLAY_TRAJECTORIES, p->overlay,
+        rc = adas::overlay_run_handles("adas_pipeline_step (overlay)", 63 | ADAS_OVERLAY_TRAJECTORIES | ADAS_OVERLAY_READOUTS, p->overlay,
                                        {p->fsrc.frames, nullptr, p->d.decode, p->d.geometry, p->analysis, p->d.post, p->d.tracker,
                                         const_cast<uint8_t*>(bird_img), stages, NS, B, st});
         if (rc) return rc;
@@ -426,6 +429,7 @@ int adas_pipeline_attach_overlay(adas_pipeline* p, adas_overlay* overlay) {
     p->overlay_stages = -1;
     p->overlay_panels = 0;
     p->overlay_text = 0;
+    p->overlay_readouts = 0;
     return ADAS_OK;
 }
 
@@ -476,6 +480,19 @@ int adas_pipeline_set_overlay_text(adas_pipeline* p, int mask) {
     ADAS_HIP_TRY(hipStreamSynchronize(p->st));
     drop_graphs(p);
     p->overlay_text = mask;
+    return ADAS_OK;
+}
+
+int adas_pipeline_set_overlay_readouts(adas_pipeline* p, int on) {
+    ADAS_REQUIRE(p && p->overlay, ADAS_ERR_INVALID, "adas_pipeline_set_overlay_readouts: no overlay handle attached");
+    if (on) {   // the records are allocated now (a captured step cannot), and the font must be there
+        int rc = adas::overlay_readout_reserve(p->overlay);
+        if (!rc) rc = adas::overlay_readout_check("adas_pipeline_set_overlay_readouts", p->overlay);
+        if (rc) return rc;
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->overlay_readouts = on ? ADAS_OVERLAY_READOUTS : 0;
     return ADAS_OK;
 }
 

@@ -223,6 +223,7 @@ struct LaneGeomDev {
     int* bird;      // [B][4][MAXPTS][2]
     double* fx;     // [B][2*img_h]
     int* idx;       // [B][2*img_h]
+    double* veh;    // [B]: the offset's veh_pos (adas_lane_geometry_fetch_veh_pos)
 };
 
 __global__ __launch_bounds__(256) void lane_geometry_kernel(LaneGeomDev d) {
@@ -238,6 +239,7 @@ __global__ __launch_bounds__(256) void lane_geometry_kernel(LaneGeomDev d) {
     f.bird = d.bird + b * 4 * ADAS_LANE_MAXPTS * 2;
     f.fx = d.fx + b * 2 * H;
     f.idx = d.idx + b * 2 * H;
+    f.veh = d.veh + b;
     Ctx c{(int)threadIdx.x, (int)blockDim.x};
     lane_geometry_frame(c, d.cfg, f, smem);
 }
@@ -258,6 +260,7 @@ __global__ __launch_bounds__(256) void lane_geometry_matrices_kernel(LaneGeomDev
     f.bird = d.bird + b * 4 * ADAS_LANE_MAXPTS * 2;
     f.fx = d.fx + b * 2 * H;
     f.idx = d.idx + b * 2 * H;
+    f.veh = d.veh + b;
     Ctx c{(int)threadIdx.x, (int)blockDim.x};
     lane_geometry_frame(c, cfg, f, smem);
 }
@@ -514,6 +517,7 @@ int handle_max_batch(const ::adas_ufld_decode* h) { return h ? h->max_batch : 0;
 int handle_max_batch(const ::adas_lane_geometry* h) { return h ? h->max_batch : 0; }
 int decode_num_lanes(const ::adas_ufld_decode* h) { return !h ? 0 : (h->v1 ? 4 : h->p.num_lanes); }
 const int* geometry_bird_points(const ::adas_lane_geometry* h) { return h->dev.bird; }
+const double* geometry_veh_pos(const ::adas_lane_geometry* h) { return h->dev.veh; }
 void post_survivor_views(const ::adas_yolo_post* h, const int** xyxy_int, const int** cls, const int** counts, int* cap) {
     *xyxy_int = h->dev.det_xyxy_i;
     *cls = h->dev.det_cls;
@@ -1188,7 +1192,7 @@ int adas_lane_geometry_create(const adas_lane_geometry_params* p, int max_batch,
     h->max_batch = max_batch;
     h->last = 0;
     const size_t B = max_batch, H = p->img_h;
-    size_t bytes = B * (8 * 4 + 2 * 8 + 4 * H * 4 + 4 * ADAS_LANE_MAXPTS * 2 * 4 + 2 * H * 8 + 2 * H * 4) + 16 * 256;
+    size_t bytes = B * (8 * 4 + 2 * 8 + 4 * H * 4 + 4 * ADAS_LANE_MAXPTS * 2 * 4 + 2 * H * 8 + 2 * H * 4 + 8) + 16 * 256;
     if (hipMalloc(&h->arena, bytes) != hipSuccess) {
         delete h;
         return hip_fail(hipGetLastError(), "hipMalloc(lane geometry arena)", __FILE__, __LINE__);
@@ -1204,6 +1208,7 @@ int adas_lane_geometry_create(const adas_lane_geometry_params* p, int max_batch,
     d.area = carve<int>(q, B * 4 * H);
     d.bird = carve<int>(q, B * 4 * ADAS_LANE_MAXPTS * 2);
     d.idx = carve<int>(q, B * 2 * H);
+    d.veh = carve<double>(q, B);
     if (hipFuncSetAttribute((const void*)lane_geometry_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
         hipFuncSetAttribute((const void*)lane_geometry_matrices_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
         hipFree(h->arena);
@@ -1275,6 +1280,12 @@ int adas_lane_geometry_fetch(adas_lane_geometry* h, int frame, adas_lane_geometr
     if (area_points && hdr[1] + hdr[2] > 0)
         ADAS_HIP_TRY(hipMemcpy(area_points, d.area + (size_t)frame * 4 * H, (size_t)(hdr[1] + hdr[2]) * 8, hipMemcpyDeviceToHost));
     if (bird_points) memcpy(bird_points, h->h_msg + 12, 4 * ADAS_LANE_MAXPTS * 2 * 4);
+    return ADAS_OK;
+}
+int adas_lane_geometry_fetch_veh_pos(adas_lane_geometry* h, int frame, double* veh_pos) {
+    ADAS_REQUIRE(h && veh_pos && frame >= 0 && frame < h->max_batch, ADAS_ERR_INVALID, "adas_lane_geometry_fetch_veh_pos: bad argument");
+    ADAS_HIP_TRY(hipStreamSynchronize(h->last));
+    ADAS_HIP_TRY(hipMemcpy(veh_pos, h->dev.veh + frame, 8, hipMemcpyDeviceToHost));
     return ADAS_OK;
 }
 int adas_lane_geometry_device_views(adas_lane_geometry* h, const int32_t** d_header, const double** d_values, const int32_t** d_area, int32_t* area_stride) {

@@ -57,6 +57,11 @@ class AdasPipeline:
         offsets), overlay["detection_names"] / ["track_names"] (class names by id; colours are detection_colors / track_colors) and
         overlay["text_lines"] = [(x, y, slot, colour, text)] (at most 8: FPS and the like).  The scene's text lies over every stage and
         under the panels, the panel strings and the lines over the panels.  self.overlay.text_items(frame) is what was placed.
+        Also only by name: the stage "readouts" -- what calcCurveAndOffset draws on the bird-view image (the white arrow at the vehicle's
+        position, the grey arrow at the centre, 'Offset: %.1f m' and 'R : %.1f m'), under the "bird" stage's discs, with
+        overlay["readout"] = dict(slot=10, zoom=2, ...) (LaneOverlay.set_readout_style) and a font in that slot of overlay["fonts"] rendered
+        at fontScale 3 / zoom.  It needs birdview=dict(image=True); birdview_image(frame) and the bird panel then show the readouts, and
+        self.overlay.readout_record(frame) is what was laid out.  A frame without a curve (direction None) is not drawn on.
         jpeg: None, or dict(quality=90, source="overlay" | "frames", capacity=None): every frame of the step as a baseline JPEG stream
         (postproc.JpegEncoder), the step's last launch group -- what the demo's vout.write(frame_show) gets, without the uncompressed frame
         leaving the device: jpeg(frame) -> bytes after sync(), jpeg_lengths() -> (lengths, flags).  source="overlay" (the default) encodes
@@ -117,11 +122,17 @@ class AdasPipeline:
                 raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
             ov_stages = dict(overlay).get("stages")
             ov_mask = None if ov_stages is None else LaneOverlay.stage_mask(ov_stages)
+            ro_on = bool(ov_mask is not None and ov_mask & L.OVERLAY_READOUTS)      # only by name; a switch of its own behind the stage mask
+            ro_style = dict(dict(overlay).get("readout") or {})
+            ro_slot = int(ro_style.get("slot", 10))
             has_bird = birdview is not None and dict(birdview).get("image", False)
             live = "the tracker's live table holds only the last frame of a step"
             for bits, ok, msg in (      # (stage bits, what they need, the refusal), in the order they are checked
                     (L.OVERLAY_DISTANCE, analysis is not None, "distance stage needs analysis= (the distance points it draws)"),
                     (L.OVERLAY_BIRD, has_bird, "bird stage needs birdview=dict(image=True) (the bird-view image it draws on)"),
+                    (L.OVERLAY_READOUTS, has_bird, "readouts stage needs birdview=dict(image=True) (the bird-view image it draws on)"),
+                    (L.OVERLAY_READOUTS, ro_slot in dict(dict(overlay).get("fonts") or {}),
+                     "readouts stage needs fonts={%d: atlas}: a font in its slot (readout=dict(slot=...))" % ro_slot),
                     (L.OVERLAY_DETECTIONS, det_model, "detections stage needs det_model= (the survivors it draws)"),
                     (L.OVERLAY_TRACKS, det_model and track, "tracks stage needs det_model= and track=True (the tracked tracks it draws)"),
                     (L.OVERLAY_TRACKS, self.B <= 1, "tracks stage needs micro_batch=1: " + live),
@@ -204,14 +215,14 @@ class AdasPipeline:
         if overlay is not None:
             style = {k: v for k, v in dict(overlay).items() if k not in ("stages", "detection_colors", "track_colors", "panels", "panel_sprites",
                                                                          "panel_params", "text", "fonts", "text_style", "text_lines", "detection_names",
-                                                                         "track_names")}
+                                                                         "track_names", "readout")}
             self.overlay = LaneOverlay(src_hw, self.warp.dst_hw if self.warp else None, n_streams, **style)
             for key, which in (("detection_colors", "detections"), ("track_colors", "tracks")):
                 if dict(overlay).get(key) is not None:
                     self.overlay.set_class_colors(which, overlay[key])
             L.check(L.lib().adas_pipeline_attach_overlay(self.h, self.overlay.h))
             if ov_mask is not None:
-                L.check(L.lib().adas_pipeline_set_overlay_stages(self.h, ov_mask))
+                L.check(L.lib().adas_pipeline_set_overlay_stages(self.h, ov_mask & ~L.OVERLAY_READOUTS))
             if pn_mask:
                 self.overlay.set_panels(overlay["panel_sprites"], **dict(dict(overlay).get("panel_params") or {}))
                 L.check(L.lib().adas_pipeline_set_overlay_panels(self.h, pn_mask))
@@ -226,6 +237,9 @@ class AdasPipeline:
                 self.overlay.set_text_lines(overlay["text_lines"])
             if tx_mask:
                 L.check(L.lib().adas_pipeline_set_overlay_text(self.h, tx_mask))
+            if ro_on:
+                self.overlay.set_readout_style(**ro_style)
+                L.check(L.lib().adas_pipeline_set_overlay_readouts(self.h, 1))
         if jpeg is not None:
             self.jpeg_encoder = JpegEncoder(src_hw[1], src_hw[0], int(dict(jpeg).get("quality", 90)), n_streams, dict(jpeg).get("capacity"))
             L.check(L.lib().adas_pipeline_attach_jpeg(self.h, self.jpeg_encoder.h, L.JPEG_SOURCES[jpeg_source]))

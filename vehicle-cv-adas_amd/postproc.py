@@ -309,6 +309,12 @@ class LaneGeometry:
                     direction=self.DIRECTIONS[res.direction], curvature=res.curvature if res.direction else None,
                     offset=res.offset if res.direction else None)
 
+    def fetch_veh_pos(self, frame=0):
+        """veh_pos of the frame: the bird-view column (lx + rx) / 2 the offset is measured from; 0.0 when the frame has no curve."""
+        v = C.c_double()
+        L.check(L.lib().adas_lane_geometry_fetch_veh_pos(self.h, int(frame), C.byref(v)))
+        return float(v.value)
+
     def close(self):
         if getattr(self, "h", None):
             L.lib().adas_lane_geometry_destroy(self.h)
@@ -630,22 +636,26 @@ class LaneOverlay:
             stages = ((L.OVERLAY_LANES if decode else 0) | (L.OVERLAY_AREA if geometry else 0) | (L.OVERLAY_DISTANCE if analysis else 0) |
                       (L.OVERLAY_BIRD if (geometry and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if post else 0) | (L.OVERLAY_TRACKS if tracker else 0))
         h = lambda x: x.h if x else None     # the widest entry of its family: the narrower ones are masks over the same path
-        L.check(L.lib().adas_overlay_run_trajectories(self.h, src_ptr, dst_ptr, h(decode), h(geometry), h(analysis), h(post), h(tracker), bird_ptr,
-                                                      self.stage_mask(stages), int(n_streams), int(n_frames), stream))
+        mask = self.stage_mask(stages)       # "readouts" (only by name) has entries of its own: the others keep refusing its bit
+        run = L.lib().adas_overlay_run_readouts if mask & L.OVERLAY_READOUTS else L.lib().adas_overlay_run_trajectories
+        L.check(run(self.h, src_ptr, dst_ptr, h(decode), h(geometry), h(analysis), h(post), h(tracker), bird_ptr, mask, int(n_streams), int(n_frames), stream))
 
     def run_arrays(self, src_ptr, n_frames=1, lane_points=None, lane_counts=None, poly=None, poly_cap=0, poly_counts=None, area_status=None,
                    offset_type=None, area_bgr=None, dist_points=None, dist_cap=0, dist_counts=None, bird_points=None, bird_counts=None,
                    bird_ptr=None, stages=None, dst_ptr=None, stream=None, det_xyxy=None, det_cap=0, det_cls=None, det_counts=None, trk_tlwh=None,
-                   trk_cap=0, trk_cls=None, trk_counts=None, trajectories=None):
+                   trk_cap=0, trk_cls=None, trk_counts=None, trajectories=None, readouts=None):
         """The same kernels on raw device pointers (adas_overlay_run_arrays; with boxes adas_overlay_run_arrays_objects: det_xyxy
         [frames][det_cap][4] int32 + det_cls + det_counts, trk_tlwh [frames][trk_cap][4] fp64 + trk_cls + trk_counts, rows of activated
         tracked tracks).  trajectories=(traj_tlbr, traj_len): device pointers to the rows' trajectories [frames][trk_cap][30][4] fp64, oldest
         first, and their lengths [frames][trk_cap] -- the "trajectories" stage (adas_overlay_run_arrays_trajectories), which also needs the
-        four trk_ arrays.  stages=None: every stage whose arrays are given ("tracks" not by the trk_ arrays alone when trajectories= is)."""
+        four trk_ arrays.  stages=None: every stage whose arrays are given ("tracks" not by the trk_ arrays alone when trajectories= is).
+        readouts=(direction, veh_pos, curvature, offset): device pointers to [frames] int32 and three [frames] fp64 -- the "readouts" stage
+        (adas_overlay_run_arrays_readouts), drawn on bird_ptr ahead of the bird stage's discs."""
         if stages is None:
             stages = ((L.OVERLAY_LANES if lane_points else 0) | (L.OVERLAY_AREA if poly else 0) | (L.OVERLAY_DISTANCE if dist_points else 0) |
                       (L.OVERLAY_BIRD if (bird_points and bird_ptr) else 0) | (L.OVERLAY_DETECTIONS if det_xyxy else 0) |
-                      (L.OVERLAY_TRACKS if (trk_tlwh and trajectories is None) else 0) | (L.OVERLAY_TRAJECTORIES if trajectories is not None else 0))
+                      (L.OVERLAY_TRACKS if (trk_tlwh and trajectories is None) else 0) | (L.OVERLAY_TRAJECTORIES if trajectories is not None else 0) |
+                      (L.OVERLAY_READOUTS if readouts is not None else 0))
         tr = trajectories if trajectories is not None else (None, None)
         a = L.OverlayArrays(                # the widest entry of its family: the narrower ones are masks over the same path
             d_src_bgr=src_ptr, d_dst_bgr=dst_ptr, d_lane_points=lane_points, d_lane_counts=lane_counts, d_poly=poly, d_poly_counts=poly_counts,
@@ -653,7 +663,42 @@ class LaneOverlay:
             d_bird_points=bird_points, d_bird_counts=bird_counts, d_bird_bgr=bird_ptr, d_det_xyxy=det_xyxy, d_det_cls=det_cls, d_det_counts=det_counts,
             d_trk_tlwh=trk_tlwh, d_trk_cls=trk_cls, d_trk_counts=trk_counts, d_traj_tlbr=tr[0], d_traj_len=tr[1], stream=stream, poly_cap=int(poly_cap),
             dist_cap=int(dist_cap), det_cap=int(det_cap), trk_cap=int(trk_cap), stages=self.stage_mask(stages), n_frames=int(n_frames))
-        L.check(L.lib().adas_overlay_run_arrays_trajectories(self.h, C.byref(a)))
+        if readouts is None and not a.stages & L.OVERLAY_READOUTS:
+            L.check(L.lib().adas_overlay_run_arrays_trajectories(self.h, C.byref(a)))
+            return
+        r = L.OverlayReadoutArrays(*(readouts if readouts is not None else (None,) * 4))
+        L.check(L.lib().adas_overlay_run_arrays_readouts(self.h, C.byref(a), C.byref(r)))
+
+    READOUT_STYLE = ("slot", "zoom", "offset_x", "offset_y", "radius_x", "radius_y", "text_color", "arrow_a_color", "arrow_b_color")
+
+    def set_readout_style(self, **style):
+        """The "readouts" stage's style from the next run on: slot (10: the font the strings are drawn in, set_fonts), zoom (2; 1 .. 4: the
+        atlas is rendered at fontScale 3 / zoom and magnified, nearest neighbour), offset_x / offset_y (20, 80) and radius_x / radius_y
+        (20, 180): the strings' origins, text_color (0, 0, 255), arrow_a_color (255, 255, 255), arrow_b_color (150, 150, 150)."""
+        if getattr(self, "rs", None) is None:
+            self.rs = L.OverlayReadoutStyle()
+            L.check(L.lib().adas_overlay_default_readout_style(C.byref(self.rs)))
+        rs = L.OverlayReadoutStyle.from_buffer_copy(self.rs)
+        for k, v in style.items():
+            if k not in self.READOUT_STYLE:
+                raise TypeError("unknown overlay readout style %r" % k)
+            if k.endswith("_color"):
+                getattr(rs, k)[:] = [int(c) for c in v]
+            else:
+                setattr(rs, k, int(v))
+        L.check(L.lib().adas_overlay_set_readout_style(self.h, C.byref(rs)))
+        self.rs = rs
+
+    def readout_record(self, frame=0):
+        """What the device laid out for the frame in the last run with the "readouts" stage: dict(drawn, flags (L.OVERLAY_READOUT_RANGE),
+        arrows: two marks in track_marks' layout (at veh_pos, at the centre), strings: two dicts (x, y, box, text, skipped): the offset,
+        the radius).  Synchronises."""
+        rec = np.zeros(1, L.READOUT_RECORD_DTYPE)
+        L.check(L.lib().adas_overlay_fetch_readout(self.h, int(frame), L.ptr(rec)))
+        r = rec[0]
+        return dict(drawn=bool(r["drawn"]), flags=int(r["flags"]), arrows=r["arrows"].copy(),
+                    strings=[dict(x=int(s["x"]), y=int(s["y"]), box=tuple(int(v) for v in s["box"]), skipped=bool(s["skipped"]),
+                                  text=bytes(s["text"])[:int(s["len"])].decode("latin-1")) for s in r["strings"]])
 
     def fetch(self, frame=0):
         out = np.empty((self.src_hw[0], self.src_hw[1], 3), np.uint8)
@@ -1237,6 +1282,27 @@ class OverlayPainter:
         finally:
             d_p.free()
             d_n.free()
+
+    def readouts(self, image, direction, veh_pos, curvature, offset, font, zoom=2, **style):
+        """calcCurveAndOffset's drawing on the bird-view image it is handed (LaneOverlay's "readouts" stage; rules R0-R6 of
+        csrc/overlay_readout_core.h): the arrow at veh_pos, the arrow at the centre, 'Offset: %.1f m' and 'R : %.1f m' in `font` (an
+        atlas rendered at fontScale 3 / zoom) magnified by `zoom`.  direction 0 (no curve) draws nothing."""
+        ptr, host = self._target(image)
+        if self._set.get("readout_font") is not font:      # the setters wait for the device: only when something changed
+            self.ov.set_fonts({10: font})
+            self._set["readout_font"] = font
+        st = tuple(sorted(dict(style, slot=10, zoom=int(zoom)).items()))
+        if self._set.get("readout_style") != st:
+            self.ov.set_readout_style(**dict(st))
+            self._set["readout_style"] = st
+        d_dir = L.DeviceBuffer.from_array(np.array([int(direction)], np.int32))
+        d_val = L.DeviceBuffer.from_array(np.array([veh_pos, curvature, offset], np.float64))
+        try:
+            self.ov.run_arrays(None, 1, bird_ptr=ptr, stages=L.OVERLAY_READOUTS, readouts=(d_dir.ptr, d_val.ptr, d_val.ptr + 8, d_val.ptr + 16))
+            self._finish(ptr, host)
+        finally:
+            d_dir.free()
+            d_val.free()
 
     def text(self, image, kinds, fonts, style=None, det_boxes=(), det_names=(), det_colors=(), tlwhs=(), trk_names=(), trk_colors=(), trk_ids=(),
              trajectories=(), points=(), types=(0, 0, 0)):
