@@ -1213,6 +1213,53 @@ int adas_yuv_fetch(adas_yuv* h, int frame, uint8_t* h_bgr);
 int adas_yuv_device_view(adas_yuv* h, const uint8_t** d_frames_bgr);
 
 /* ===================================================================================
+ * BGR frames into uncompressed video formats on the device: the way out that mirrors the way in above.  What cv2.VideoWriter.write(frame_show)
+ * (demo.py:314) does in front of its encoder, for every encoder that is not MJPEG (x264, SVT, `ffmpeg -f rawvideo -pix_fmt yuv420p`, a
+ * V4L2 loopback, a hardware encoder on another box): the frame leaves the device as 1.5 or 2 bytes per pixel instead of 3, a whole step's
+ * frames in one copy.  The same five formats, the same description of pitches and plane offsets -- adas_yuv_params now describes a
+ * destination.  The rules E1-E7 are csrc/yuvout_core.h: BT.601 limited range in OpenCV's 20-bit integers (ADAS_YUV_MATRIX_VIDEO) or JFIF full
+ * range (ADAS_YUV_MATRIX_FULL, the JPEG encoder's rule J2); a chroma sample is the rounded mean of its cell's pixels
+ * (ADAS_YUVOUT_CHROMA_MEAN, what encoders' scalers do) or its first pixel's (ADAS_YUVOUT_CHROMA_FIRST).  One plain launch: capturable, no
+ * allocation and no host synchronisation in adas_yuvout_run.
+ * =================================================================================== */
+typedef struct adas_yuvout adas_yuvout;
+#define ADAS_YUVOUT_CHROMA_MEAN 0    /* (a + b + c + d + 2) >> 2 over a 2x2 cell (4:2:0), (a + b + 1) >> 1 over a 2x1 cell (4:2:2) */
+#define ADAS_YUVOUT_CHROMA_FIRST 1   /* U and V of the cell's first pixel */
+#define ADAS_YUVOUT_SRC_OVERLAY 0    /* adas_pipeline_attach_yuvout: the attached overlay's own buffer, behind its stages, text and panels */
+#define ADAS_YUVOUT_SRC_FRAMES 1     /* the u8 frames adas_pipeline_step_frames* was given */
+typedef struct {                  /* adas_yuv_params, then chroma */
+    int32_t format, matrix;
+    int32_t width, height;
+    int64_t frame_stride;
+    int64_t y_offset, y_pitch;
+    int64_t u_offset, u_pitch;
+    int64_t v_offset, v_pitch;
+    int32_t chroma;
+} adas_yuvout_params;
+/* The tight layout of a width x height frame, matrix VIDEO, chroma MEAN. */
+int adas_yuvout_default_params(adas_yuvout_params* p, int format, int width, int height);
+/* Bytes of one destination frame up to the end of its last plane; a batch ends (batch - 1) * frame_stride + this behind its start.  0 for
+ * parameters adas_yuvout_create would refuse. */
+int64_t adas_yuvout_frame_bytes(const adas_yuvout_params* p);
+/* ADAS_ERR_INVALID by name, with adas_yuv_create's words: odd width, odd height for a 4:2:0 format, pitch shorter than a row, plane
+ * outside the frame, planes overlap, max_batch < 1; and unknown chroma mode.  Allocates (max_batch - 1) * frame_stride + frame_bytes bytes,
+ * zeroed. */
+int adas_yuvout_create(const adas_yuvout_params* p, int max_batch, adas_yuvout** out);
+int adas_yuvout_destroy(adas_yuvout* h);
+/* d_bgr [batch][height][width][3] u8 on the device, any alignment.  d_dst: frame f at d_dst + f * frame_stride, any alignment; NULL: the
+ * handle's own buffer.  Every byte of every plane row is written and no other byte: pitch padding and the gaps between planes and frames
+ * keep what they held.  When width, the pitches, the offsets, frame_stride and both pointers are multiples of 16 every access is 16 (I420's
+ * chroma: 8) bytes wide; any other geometry goes byte by byte and gives the same bytes.  Asynchronous on `stream`. */
+int adas_yuvout_run(adas_yuvout* h, const uint8_t* d_bgr, int batch, uint8_t* d_dst, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_dst [frame_bytes], after the last run's stream has drained.  ADAS_ERR_INVALID for a frame
+ * the last run did not write there. */
+int adas_yuvout_fetch(adas_yuvout* h, int frame, uint8_t* h_dst);
+/* The first `batch` frames of the last run in ONE copy: (batch - 1) * frame_stride + frame_bytes bytes, frame f at h_dst + f * frame_stride.
+ * Meant for a pinned buffer (adas_host_alloc). */
+int adas_yuvout_fetch_all(adas_yuvout* h, int batch, uint8_t* h_dst);
+int adas_yuvout_device_view(adas_yuvout* h, const uint8_t** d_frames);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1366,6 +1413,14 @@ int adas_pipeline_set_overlay_readouts(adas_pipeline* p, int on);
  * jpeg == NULL detaches.  Cached graphs are dropped.  Without it the step, its graph and its launch count are unchanged.  The handle
  * stays the caller's; adas_jpeg_fetch after adas_pipeline_sync. */
 int adas_pipeline_attach_jpeg(adas_pipeline* p, adas_jpeg* jpeg, int source);
+/* Optional raw-video stage on the pipeline's main stream and inside the capture, behind the overlay's stages, text and panels: adas_yuvout_run
+ * on all n_streams x micro_batch frames of the step into the handle's own buffer -- one more launch.  source ADAS_YUVOUT_SRC_OVERLAY: the
+ * attached overlay's own buffer (needs adas_pipeline_attach_overlay first); ADAS_YUVOUT_SRC_FRAMES: the camera frames the step was given.
+ * Independent of an attached JPEG stage: both may be on.  Needs adas_pipeline_step_frames* (the seam-tensor step is then
+ * ADAS_ERR_INVALID).  The handle must hold n_streams x micro_batch frames; its size must be the overlay's (checked here) and the step's
+ * camera geometry (checked at the step).  yuvout == NULL detaches.  Cached graphs are dropped.  Without it the step, its graph and its
+ * launch count are unchanged.  The handle stays the caller's; adas_yuvout_fetch / _fetch_all after adas_pipeline_sync. */
+int adas_pipeline_attach_yuvout(adas_pipeline* p, adas_yuvout* yuvout, int source);
 /* Kernel nodes of the captured step the last graph-mode step replayed.  ADAS_ERR_INVALID before the first such step. */
 int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */

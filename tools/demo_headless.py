@@ -7,6 +7,7 @@ No window, no video codec: frames come from a seeded synthetic 1280x720 clip (mo
 
     python tools/demo_headless.py [--frames 30] [--det yolov8n.onnx|.hipm] [--det-type yolov8|efficientdet] [--lane culane_res18.onnx|.hipm] [--video clip.npy]
                                   [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg] [--from-yuv in.yuv --yuv-format nv12 --yuv-size 1280x720]
+                                  [--yuv-out out.yuv --yuv-out-format i420]
                                   [--readout-font FONT.npz [--readout-zoom 2] [--bird-out bird.npy]]
 
 Without model paths, seeded random-weight models are built (their detections are noise: the point is the data flow)."""
@@ -73,6 +74,12 @@ def main():
     ap.add_argument("--yuv-format", default="nv12", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
     ap.add_argument("--yuv-size", default="1280x720", metavar="WxH")
     ap.add_argument("--yuv-matrix", default="video", choices=["video", "full"])
+    ap.add_argument("--yuv-out", default=None, metavar="PATH",
+                    help="demo.py:314 (vout.write) for an encoder that is not MJPEG: convert every frame on the device (postproc.YuvWriter, BT.601 "
+                         "limited range, chroma by the mean of a cell) from the staged frame in HBM -- the drawn frame with --fonts -- and append it "
+                         "raw to PATH in --yuv-out-format, tightly packed: `ffmpeg -f rawvideo -pix_fmt yuv420p -s WxH -i PATH` reads an i420 file "
+                         "(nv12, nv21, yuyv422, uyvy422 for the others)")
+    ap.add_argument("--yuv-out-format", default="i420", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
     a = ap.parse_args()
     work = tempfile.mkdtemp(prefix="adas_demo_")
     effdet = a.det_type == "efficientdet"
@@ -143,7 +150,9 @@ def main():
 
     encoder = PP.JpegEncoder(width, height, quality=90, capacity=PP.JpegEncoder.bound(width, height)) if a.mjpeg else None
     vout = open(a.mjpeg, "wb") if a.mjpeg else None
-    written = 0
+    writer = PP.YuvWriter(a.yuv_out_format, width, height) if a.yuv_out else None
+    yout = open(a.yuv_out, "ab") if a.yuv_out else None
+    written = raw_written = 0
     src = iter(frames) if frames is not None else synthetic_clip(a.frames)
     t0 = time.perf_counter()
     n = 0
@@ -192,6 +201,9 @@ def main():
         if encoder is not None:                                                           # demo.py:314
             encoder.run(objectDetector.staged_frame.ptr, 1)
             written += vout.write(encoder.fetch(0))
+        if writer is not None:                                                            # demo.py:314, for any other encoder
+            writer.run_device(objectDetector.staged_frame.ptr, 1)
+            raw_written += yout.write(writer.frame(0).tobytes())
         n += 1
     dt = time.perf_counter() - t0
     if a.bird_out and n:
@@ -200,6 +212,10 @@ def main():
         vout.close(); encoder.close()
         print("%s: %d JPEG streams, %d bytes (%.0f per frame, 1 / %.1f of the raw frames)" % (a.mjpeg, n, written, written / max(n, 1),
                                                                                             n * height * width * 3 / max(written, 1)))
+    if writer is not None:
+        yout.close(); writer.close()
+        print("%s: %d %s frames of %dx%d appended, %d bytes (%d per frame, 1 / %.1f of the BGR frames)"
+              % (a.yuv_out, n, a.yuv_out_format, width, height, raw_written, raw_written // max(n, 1), n * height * width * 3 / max(raw_written, 1)))
     print("%d frames in %.2f s (%.1f frames/s, single stream, host frames: upload + 2 nets + post-processing + fetch per frame)" % (n, dt, n / dt))
     transformView.close(); objectDetector.close(); laneDetector.close(); objectTracker.close()
     if decoder is not None:

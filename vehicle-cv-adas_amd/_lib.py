@@ -250,6 +250,14 @@ YUV_MATRICES = {"video": 0, "full": 1}                                       # A
 YUV_LAYOUT_FIELDS = ("frame_stride", "y_offset", "y_pitch", "u_offset", "u_pitch", "v_offset", "v_pitch")
 
 
+class YuvOutParams(C.Structure):                                             # adas_yuvout_params: adas_yuv_params, then chroma
+    _fields_ = list(YuvParams._fields_) + [("chroma", C.c_int32)]
+
+
+YUVOUT_CHROMA = {"mean": 0, "first": 1}                                      # ADAS_YUVOUT_CHROMA_*
+YUVOUT_SOURCES = {"overlay": 0, "frames": 1}                                 # ADAS_YUVOUT_SRC_*
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -472,6 +480,15 @@ _SIGS = {
     "adas_yuv_run_host": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "adas_yuv_fetch": (C.c_int, [_P, C.c_int, _P]),
     "adas_yuv_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_yuvout_default_params": (C.c_int, [C.POINTER(YuvOutParams), C.c_int, C.c_int, C.c_int]),
+    "adas_yuvout_frame_bytes": (C.c_int64, [C.POINTER(YuvOutParams)]),
+    "adas_yuvout_create": (C.c_int, [C.POINTER(YuvOutParams), C.c_int, C.POINTER(_P)]),
+    "adas_yuvout_destroy": (C.c_int, [_P]),
+    "adas_yuvout_run": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "adas_yuvout_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_yuvout_fetch_all": (C.c_int, [_P, C.c_int, _P]),
+    "adas_yuvout_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_pipeline_attach_yuvout": (C.c_int, [_P, _P, C.c_int]),
     "adas_pipeline_attach_yuv": (C.c_int, [_P, _P]),
     "adas_pipeline_step_yuv": (C.c_int, [_P, _P, C.c_double]),
     "adas_pipeline_step_yuv_host": (C.c_int, [_P, _P, C.c_double]),

@@ -31,6 +31,7 @@ UNITS = [
     ("jpeg_kernels.hip", []),
     ("jpegdec_kernels.hip", []),
     ("yuv_kernels.hip", []),
+    ("yuvout_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

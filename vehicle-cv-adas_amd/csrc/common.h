@@ -157,6 +157,11 @@ void yuv_geometry_of(const ::adas_yuv* h, int* width, int* height, int* max_batc
 uint8_t* yuv_frames(::adas_yuv* h);
 long long yuv_extent_of(const ::adas_yuv* h);   // bytes of a source frame that are read (adas_yuv_frame_bytes)
 }  // namespace adas
+// what adas_pipeline_attach_yuvout checks (yuvout_kernels.hip); zeros for a null handle
+struct adas_yuvout;
+namespace adas {
+void yuvout_geometry_of(const ::adas_yuvout* h, int* width, int* height, int* max_batch);
+}  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \

@@ -24,6 +24,9 @@ struct adas_pipeline {
     // optional encoding stage, the step's last launch group (adas_pipeline_attach_jpeg): one baseline JPEG stream per frame
     adas_jpeg* jpeg = nullptr;
     int jpeg_source = ADAS_JPEG_SRC_OVERLAY;
+    // optional raw-video stage behind the overlay (adas_pipeline_attach_yuvout): every frame as NV12 / NV21 / I420 / YUYV / UYVY
+    adas_yuvout* yuvout = nullptr;
+    int yuvout_source = ADAS_YUVOUT_SRC_OVERLAY;
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -256,6 +259,17 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
             if (rc) return rc;
         }
         rc = adas_jpeg_run(p->jpeg, src, S, st);
+        if (rc) return rc;
+    }
+    if (p->yuvout) {   // and as raw video: reads the same finished frames, writes its own buffer
+        ADAS_REQUIRE(p->fsrc.frames, ADAS_ERR_INVALID, "the YUV output stage needs camera frames: use adas_pipeline_step_frames");
+        const uint8_t* src = p->fsrc.frames;
+        if (p->yuvout_source == ADAS_YUVOUT_SRC_OVERLAY) {
+            ADAS_REQUIRE(p->overlay, ADAS_ERR_INVALID, "the YUV output stage's overlay source needs an attached overlay handle");
+            rc = adas_overlay_device_view(p->overlay, &src);
+            if (rc) return rc;
+        }
+        rc = adas_yuvout_run(p->yuvout, src, S, nullptr, st);
         if (rc) return rc;
     }
     if (events) ADAS_HIP_TRY(hipEventRecord(p->ev[5], st));
@@ -521,6 +535,32 @@ int adas_pipeline_attach_jpeg(adas_pipeline* p, adas_jpeg* jpeg, int source) {
     return ADAS_OK;
 }
 
+int adas_pipeline_attach_yuvout(adas_pipeline* p, adas_yuvout* yuvout, int source) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_yuvout: null pipeline");
+    if (yuvout) {
+        ADAS_REQUIRE(source == ADAS_YUVOUT_SRC_OVERLAY || source == ADAS_YUVOUT_SRC_FRAMES, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_yuvout: unknown source %d", source);
+        ADAS_REQUIRE(source != ADAS_YUVOUT_SRC_OVERLAY || p->overlay, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_yuvout: the overlay source needs an attached overlay handle (adas_pipeline_attach_overlay first)");
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int yw = 0, yh = 0, yb = 0;
+        adas::yuvout_geometry_of(yuvout, &yw, &yh, &yb);
+        ADAS_REQUIRE(yb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_yuvout: the YUV output handle holds %d frames, a step has %d", yb, frames);
+        if (source == ADAS_YUVOUT_SRC_OVERLAY) {
+            int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0;
+            (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
+            ADAS_REQUIRE(oh == yh && ow == yw, ADAS_ERR_INVALID,
+                         "adas_pipeline_attach_yuvout: the YUV output handle was created for %dx%d frames, the attached overlay draws %dx%d", yw, yh, ow,
+                         oh);
+        }
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->yuvout = yuvout;
+    p->yuvout_source = source;
+    return ADAS_OK;
+}
+
 int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels) {
     ADAS_REQUIRE(p && n_kernels, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: bad argument");
     ADAS_REQUIRE(p->last_graph, ADAS_ERR_INVALID, "adas_pipeline_graph_kernels: no captured step has been replayed yet");
@@ -629,6 +669,8 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
     ADAS_REQUIRE(!p->bird_warp, ADAS_ERR_INVALID, "a bird-view image warp is attached: seam tensors carry no frame to warp, use adas_pipeline_step_frames");
     ADAS_REQUIRE(!p->overlay, ADAS_ERR_INVALID, "an overlay is attached: seam tensors carry no frame to draw on, use adas_pipeline_step_frames");
     ADAS_REQUIRE(!p->jpeg, ADAS_ERR_INVALID, "a JPEG stage is attached: seam tensors carry no frame to encode, use adas_pipeline_step_frames");
+    ADAS_REQUIRE(!p->yuvout, ADAS_ERR_INVALID,
+                 "a YUV output stage is attached: seam tensors carry no frame to convert, use adas_pipeline_step_frames");
     if (!(p->d.use_graph & 1)) {
         p->timed = true;
         return record_step(p, d_det, d_lane, true);
@@ -656,6 +698,12 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
         adas::jpeg_geometry_of(p->jpeg, &jw, &jh, &jb);
         ADAS_REQUIRE(jh == src_h && jw == src_w, ADAS_ERR_INVALID, "the attached JPEG handle was created for %dx%d frames, the step has %dx%d", jw, jh, src_w,
                      src_h);
+    }
+    if (p->yuvout) {   // and the YUV output stage
+        int yw = 0, yh = 0, yb = 0;
+        adas::yuvout_geometry_of(p->yuvout, &yw, &yh, &yb);
+        ADAS_REQUIRE(yh == src_h && yw == src_w, ADAS_ERR_INVALID, "the attached YUV output handle was created for %dx%d frames, the step has %dx%d", yw, yh,
+                     src_w, src_h);
     }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
     if (!p->det_in && !p->lane_in) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, host_streams, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, YuvWriter, yuv_output_args, host_streams, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None, yuv_output=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -80,14 +80,20 @@ class AdasPipeline:
         converts them on the device and runs the step on the result; step_yuv(d_ptr) takes frames already on the device, such as a
         decoder's surface.  matrix: "video" (BT.601 limited range, cv2's; the default) or "full" (JFIF).  layout: None for tightly packed
         frames, or YuvConverter's dict of byte strides and plane offsets.  Not together with jpeg_input=.  Nothing inside the captured step
-        changes."""
+        changes.
+        yuv_output: None, or dict(format="i420", matrix="video" | "full", chroma="mean" | "first", source="overlay" | "frames", layout=None):
+        every frame of the step as raw video (postproc.YuvWriter) for an encoder that is not MJPEG -- x264, `ffmpeg -f rawvideo -pix_fmt
+        yuv420p`, a V4L2 loopback -- behind the overlay's stages, text and panels, one more launch inside the captured step: yuv(frame) ->
+        uint8 [frame_bytes] after sync(), yuv_all() -> all of the step's frames in one copy.  source="overlay" (the default) converts the
+        drawn frames and needs overlay=; source="frames" converts the camera frames the step was given.  Either needs step_frames /
+        step_frames_host.  Independent of jpeg=: both may be on.  Any micro_batch: frames are independent."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
         n_tracks = n_streams
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
-        self.overlay = self.jpeg_encoder = self.jpeg_decoder = self.yuv_converter = None
+        self.overlay = self.jpeg_encoder = self.jpeg_decoder = self.yuv_converter = self.yuv_writer = None
         if jpeg_input is not None and jpeg_input is not False:
             jpeg_input = {} if jpeg_input is True else dict(jpeg_input)
             unknown = set(jpeg_input) - {"capacity"}
@@ -117,6 +123,20 @@ class AdasPipeline:
                 raise ValueError("jpeg= with source=\"overlay\" needs overlay= (the drawn frames it encodes); source=\"frames\" encodes the camera frames")
             if not 1 <= int(dict(jpeg).get("quality", 90)) <= 100:
                 raise ValueError("jpeg= quality %r is outside 1..100" % (dict(jpeg).get("quality"),))
+        if yuv_output is not None:
+            if not isinstance(yuv_output, dict):
+                raise ValueError("yuv_output= %r is neither None nor a dict (format, matrix, chroma, source, layout)" % (yuv_output,))
+            yuv_output = dict(yuv_output)
+            unknown = set(yuv_output) - {"format", "matrix", "chroma", "source", "layout"}
+            if unknown:
+                raise ValueError("yuv_output= holds unknown keys %s (format, matrix, chroma, source, layout)" % sorted(unknown))
+            yuv_output_args(yuv_output.get("format", "i420"), yuv_output.get("matrix", "video"), yuv_output.get("chroma", "mean"),
+                            yuv_output.get("layout"), what="yuv_output= ")
+            if yuv_output.get("source", "overlay") not in L.YUVOUT_SOURCES:
+                raise ValueError("yuv_output= source %r is neither \"overlay\" nor \"frames\"" % (yuv_output.get("source"),))
+            if yuv_output.get("source", "overlay") == "overlay" and overlay is None:
+                raise ValueError("yuv_output= with source=\"overlay\" needs overlay= (the drawn frames it converts); source=\"frames\" converts the "
+                                 "camera frames")
         if overlay is not None:
             if geometry is None or not lane_model:
                 raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
@@ -250,6 +270,10 @@ class AdasPipeline:
             self.yuv_converter = YuvConverter(yuv_input.get("format", "nv12"), src_hw[1], src_hw[0], yuv_input.get("matrix", "video"),
                                               yuv_input.get("layout"), n_streams)
             L.check(L.lib().adas_pipeline_attach_yuv(self.h, self.yuv_converter.h))
+        if yuv_output is not None:
+            self.yuv_writer = YuvWriter(yuv_output.get("format", "i420"), src_hw[1], src_hw[0], yuv_output.get("matrix", "video"),
+                                        yuv_output.get("chroma", "mean"), yuv_output.get("layout"), n_streams)
+            L.check(L.lib().adas_pipeline_attach_yuvout(self.h, self.yuv_writer.h, L.YUVOUT_SOURCES[yuv_output.get("source", "overlay")]))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -347,6 +371,19 @@ class AdasPipeline:
             raise ValueError("the pipeline was created without jpeg=")
         return self.jpeg_encoder.lengths(self.S * self.B)
 
+    def yuv(self, frame=0):
+        """Frame `frame` of the last step_frames (after sync()) in yuv_output's format: uint8 [yuv_writer.frame_bytes]."""
+        if self.yuv_writer is None:
+            raise ValueError("the pipeline was created without yuv_output=")
+        return self.yuv_writer.frame(frame)
+
+    def yuv_all(self, out=None):
+        """All n_streams x micro_batch frames of the last step (after sync()) in one copy: uint8 [yuv_writer.batch_bytes(frames)], frame f at
+        f * yuv_writer.p.frame_stride.  out: a uint8 array to fill (pinned: _lib.PinnedBuffer(...).array)."""
+        if self.yuv_writer is None:
+            raise ValueError("the pipeline was created without yuv_output=")
+        return self.yuv_writer.fetch_all(self.S * self.B, out)
+
     def graph_kernels(self):
         """Kernel launches of the captured step the last step replayed (use_graph=True)."""
         n = C.c_int32()
@@ -376,7 +413,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (getattr(self, "yuv_writer", None), getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

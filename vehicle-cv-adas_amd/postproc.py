@@ -1155,6 +1155,101 @@ class YuvConverter:
     __del__ = close
 
 
+def yuv_output_args(format="i420", matrix="video", chroma="mean", layout=None, what=""):
+    """YuvWriter's argument checks without a handle (so without a GPU): ValueError naming the key."""
+    if format not in L.YUV_FORMATS:
+        raise ValueError("%sformat %r is none of %s" % (what, format, sorted(L.YUV_FORMATS)))
+    if matrix not in L.YUV_MATRICES:
+        raise ValueError("%smatrix %r is neither \"video\" nor \"full\"" % (what, matrix))
+    if chroma not in L.YUVOUT_CHROMA:
+        raise ValueError("%schroma %r is neither \"mean\" nor \"first\"" % (what, chroma))
+    if layout is not None and not isinstance(layout, dict):
+        raise ValueError("%slayout %r is neither None nor a dict out of %s" % (what, layout, ", ".join(L.YUV_LAYOUT_FIELDS)))
+    unknown = set(layout or {}) - set(L.YUV_LAYOUT_FIELDS)
+    if unknown:
+        raise ValueError("%slayout= holds unknown keys %s (%s)" % (what, sorted(unknown), ", ".join(L.YUV_LAYOUT_FIELDS)))
+
+
+class YuvWriter:
+    """BGR frames on the device into uncompressed video formats (adas_yuvout_*), the inverse of YuvConverter: "nv12", "nv21", "i420", "yuyv" or
+    "uyvy" frames out, 1.5 or 2 bytes per pixel in place of 3, for any encoder that is not MJPEG (x264, `ffmpeg -f rawvideo -pix_fmt
+    yuv420p`, a V4L2 loopback): what cv2.VideoWriter.write or a caller's cv2.cvtColor(frame, cv2.COLOR_BGR2YUV_I420) does on host cores.  The
+    rules E1-E7 are csrc/yuvout_core.h.  matrix: "video" (BT.601 limited range) or "full" (JFIF, the JPEG encoder's).  chroma: "mean" (a
+    chroma sample is the rounded mean of its cell, what encoders' scalers do) or "first" (its first pixel's).  layout: as YuvConverter's, now
+    the destination's -- bytes no plane row owns are never written; YV12 is "i420" with u_offset and v_offset exchanged.  frame_bytes: the
+    bytes of a frame up to the end of its last plane; n frames are (n - 1) * params.frame_stride + frame_bytes bytes."""
+
+    def __init__(self, format, width, height, matrix="video", chroma="mean", layout=None, max_batch=1):
+        yuv_output_args(format, matrix, chroma, layout)
+        self.p = L.YuvOutParams()
+        L.check(L.lib().adas_yuvout_default_params(C.byref(self.p), L.YUV_FORMATS[format], int(width), int(height)))
+        self.p.matrix = L.YUV_MATRICES[matrix]
+        self.p.chroma = L.YUVOUT_CHROMA[chroma]
+        for k, v in (layout or {}).items():
+            setattr(self.p, k, int(v))
+        self.format, self.matrix, self.chroma, self.width, self.height, self.max_batch = format, matrix, chroma, int(width), int(height), int(max_batch)
+        h = C.c_void_p()
+        L.check(L.lib().adas_yuvout_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        self.frame_bytes = int(L.lib().adas_yuvout_frame_bytes(C.byref(self.p)))
+
+    def batch_bytes(self, n):
+        return (int(n) - 1) * int(self.p.frame_stride) + self.frame_bytes
+
+    def run_device(self, d_bgr, n, d_dst=None, stream=None):
+        """n BGR frames [n][height][width][3] u8 on the device (any byte).  Asynchronous on `stream`.  d_dst: device pointer of batch_bytes(n)
+        bytes, frame f at d_dst + f * frame_stride (None: the handle's own buffer)."""
+        L.check(L.lib().adas_yuvout_run(self.h, d_bgr, int(n), d_dst, stream))
+
+    def frame(self, i=0):
+        """Frame i of the last run into the handle's own buffer: uint8 [frame_bytes].  Waits for that run."""
+        out = np.empty(self.frame_bytes, np.uint8)
+        L.check(L.lib().adas_yuvout_fetch(self.h, int(i), L.ptr(out)))
+        return out
+
+    def planes_of(self, buf):
+        """Views of a frame's bytes: (Y [h][w], U [h/2][w/2], V [h/2][w/2]) for "i420", (Y, UV [h/2][w/2][2]) for "nv12" (VU for "nv21")."""
+        if self.format in ("yuyv", "uyvy"):
+            raise ValueError("format %r is packed: it has no planes" % (self.format,))
+        as_strided = np.lib.stride_tricks.as_strided
+        w, h, p = self.width, self.height, self.p
+        y = as_strided(buf[p.y_offset:], (h, w), (p.y_pitch, 1), writeable=False)
+        if self.format == "i420":
+            return (y, as_strided(buf[p.u_offset:], (h // 2, w // 2), (p.u_pitch, 1), writeable=False),
+                    as_strided(buf[p.v_offset:], (h // 2, w // 2), (p.v_pitch, 1), writeable=False))
+        return y, as_strided(buf[p.u_offset:], (h // 2, w // 2, 2), (p.u_pitch, 2, 1), writeable=False)
+
+    def planes(self, i=0):
+        """planes_of(frame(i))"""
+        if self.format in ("yuyv", "uyvy"):
+            raise ValueError("format %r is packed: it has no planes" % (self.format,))
+        return self.planes_of(self.frame(i))
+
+    def fetch_all(self, n, out=None):
+        """The first n frames of the last run in ONE copy: uint8 [batch_bytes(n)], frame f at f * frame_stride.  out: a uint8 array of at least
+        that size to fill (_lib.PinnedBuffer(...).array for the fastest copy); the filled part is returned."""
+        need = self.batch_bytes(n)
+        if out is None:
+            out = np.empty(need, np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise ValueError("fetch_all needs a contiguous uint8 array of at least %d bytes" % need)
+        L.check(L.lib().adas_yuvout_fetch_all(self.h, int(n), L.ptr(out)))
+        return out.reshape(-1)[:need]
+
+    def device_view(self):
+        """Device pointer of the handle's own frames, frame f at f * frame_stride."""
+        d = C.c_void_p()
+        L.check(L.lib().adas_yuvout_device_view(self.h, C.byref(d)))
+        return d.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_yuvout_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
