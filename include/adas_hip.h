@@ -1260,6 +1260,54 @@ int adas_yuvout_fetch_all(adas_yuvout* h, int batch, uint8_t* h_dst);
 int adas_yuvout_device_view(adas_yuvout* h, const uint8_t** d_frames);
 
 /* ===================================================================================
+ * Finished BGR frames reduced on the device: a preview per frame, or a mosaic in which every frame of a step is a tile -- a video wall.  What
+ * a caller's cv2.resize(frame_show, size) and NumPy slice assignments do on host cores after fetching every full frame: here one canvas, or a
+ * reduced frame per stream, leaves instead.  The rules S1-S8 are csrc/scale_core.h: a tile is dst_w x dst_h, a canvas is cols x rows tiles,
+ * frame f goes to canvas f / (cols * rows), cell f % (cols * rows) in row-major order; ADAS_SCALE_AREA is an exact integer box filter
+ * (reduction only, round to nearest with ties up, (a + b + c + d + 2) >> 2 at a ratio of 2), ADAS_SCALE_LINEAR the project's 8-bit
+ * INTER_LINEAR (the bird panel's rule P5).  A tile can wear its frame's collision state as a border.  One plain launch: capturable, no
+ * allocation and no host synchronisation in adas_scale_run.
+ * =================================================================================== */
+typedef struct adas_scale adas_scale;
+#define ADAS_SCALE_AREA 0          /* exact box filter, dst <= src on both axes */
+#define ADAS_SCALE_LINEAR 1        /* rule P5, any sizes */
+#define ADAS_SCALE_SRC_OVERLAY 0   /* adas_pipeline_attach_scale: the attached overlay's own buffer, behind its stages, text and panels */
+#define ADAS_SCALE_SRC_FRAMES 1    /* the u8 frames adas_pipeline_step_frames* was given */
+typedef struct {
+    int32_t src_w, src_h;           /* a source frame */
+    int32_t dst_w, dst_h;           /* a tile */
+    int32_t mode;                   /* ADAS_SCALE_* */
+    int32_t cols, rows;             /* tiles of a canvas; 1, 1: one reduced frame per frame */
+    int32_t border;                 /* pixel rings that take border_bgr[state]; 0: none */
+    uint8_t background[4];          /* B, G, R of a cell without a frame; [3] unused */
+    uint8_t border_bgr[4][4];       /* [ANA_COLLISION_*] B, G, R; [3] unused */
+} adas_scale_params;
+/* mode AREA, one tile per canvas, no border, a black background, border colours demo.py's ControlPanel.CollisionDict: UNKNOWN (0,255,255),
+ * NORMAL (0,255,0), PROMPT (0,102,255), WARNING (0,0,255). */
+int adas_scale_default_params(adas_scale_params* p, int src_w, int src_h, int dst_w, int dst_h);
+/* Bytes of one canvas, rows * dst_h * cols * dst_w * 3, and the canvases a run of `batch` frames writes, ceil(batch / (cols * rows)); 0
+ * for parameters adas_scale_create would refuse. */
+int64_t adas_scale_canvas_bytes(const adas_scale_params* p);
+int adas_scale_canvases(const adas_scale_params* p, int batch);
+/* ADAS_ERR_INVALID by name: unknown mode; source and tile sides must be in 1..16383; mosaic columns and rows must be in 1..16383; area does
+ * not enlarge; area needs src_w * src_h <= 8388608; border must be >= 0 and 2 * border < min(dst_w, dst_h); a canvas must stay below 2^31
+ * bytes; max_batch < 1.  Allocates adas_scale_canvases(max_batch) canvases, zeroed. */
+int adas_scale_create(const adas_scale_params* p, int max_batch, adas_scale** out);
+int adas_scale_destroy(adas_scale* h);
+/* d_bgr [batch][src_h][src_w][3] u8 on the device, any alignment.  d_state: NULL, or frame f's int32 state (ANA_COLLISION_*; anything else
+ * counts as UNKNOWN) at d_state + f * state_stride bytes, read only when border > 0.  d_dst: canvas k at d_dst + k * canvas_bytes, any
+ * alignment; NULL: the handle's own buffer.  Every byte of the adas_scale_canvases(batch) canvases is written exactly once, cells without a
+ * frame with `background`, and no other byte.  When dst_w * 3 and both pointers are multiples of 16 every store is 16 bytes wide; anything
+ * else goes byte by byte and gives the same bytes.  ADAS_ERR_INVALID for batch > max_batch.  Asynchronous on `stream`. */
+int adas_scale_run(adas_scale* h, const uint8_t* d_bgr, int batch, const void* d_state, int64_t state_stride, uint8_t* d_dst, void* stream);
+/* Canvas `canvas` of the handle's own buffer -> h_dst [canvas_bytes], after the last run's stream has drained.  ADAS_ERR_INVALID for a
+ * canvas the last run did not write there. */
+int adas_scale_fetch(adas_scale* h, int canvas, uint8_t* h_dst);
+/* The first `canvases` canvases of the last run in ONE copy.  Meant for a pinned buffer (adas_host_alloc). */
+int adas_scale_fetch_all(adas_scale* h, int canvases, uint8_t* h_dst);
+int adas_scale_device_view(adas_scale* h, const uint8_t** d_canvases);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1421,6 +1469,22 @@ int adas_pipeline_attach_jpeg(adas_pipeline* p, adas_jpeg* jpeg, int source);
  * camera geometry (checked at the step).  yuvout == NULL detaches.  Cached graphs are dropped.  Without it the step, its graph and its
  * launch count are unchanged.  The handle stays the caller's; adas_yuvout_fetch / _fetch_all after adas_pipeline_sync. */
 int adas_pipeline_attach_yuvout(adas_pipeline* p, adas_yuvout* yuvout, int source);
+/* Optional scaling stage on the pipeline's main stream and inside the capture, behind the overlay's stages, text and panels and in front of
+ * the JPEG and YUV stages: adas_scale_run on all n_streams x micro_batch frames of the step, in frame-index order, into the handle's own
+ * canvases -- one more launch.  source as for adas_pipeline_attach_yuvout, with the same checks: the overlay source needs an attached overlay
+ * whose frame geometry equals the handle's source, the handle must hold a step's frames.  With border > 0 the step passes the attached
+ * analysis handle's collision column as the states; the attach is refused when border > 0 and no analysis handle is attached.  The stage
+ * needs adas_pipeline_step_frames*.  scale == NULL detaches.  Every call detaches the two consumers below, which were checked against the
+ * handle that leaves: attach them again behind a new one.  Cached graphs are dropped.  Without it the step, its graph and its launch count
+ * are unchanged. */
+int adas_pipeline_attach_scale(adas_pipeline* p, adas_scale* scale, int source);
+/* A second JPEG encoder and a second YUV writer, created by the caller at the canvas size (cols * dst_w x rows * dst_h) for at least the
+ * step's canvas count, that consume the scaling stage's canvases directly behind it: adas_jpeg_run's launches, one launch of
+ * adas_yuvout_run.  Independent of adas_pipeline_attach_jpeg / _yuvout, so the full-size feed and the preview can leave the same step.
+ * Refused by name: no scale handle attached first, a handle of another width or height than the canvas, a handle that holds fewer frames
+ * than the step has canvases.  NULL detaches.  Cached graphs are dropped. */
+int adas_pipeline_attach_scale_jpeg(adas_pipeline* p, adas_jpeg* jpeg);
+int adas_pipeline_attach_scale_yuvout(adas_pipeline* p, adas_yuvout* yuvout);
 /* Kernel nodes of the captured step the last graph-mode step replayed.  ADAS_ERR_INVALID before the first such step. */
 int adas_pipeline_graph_kernels(adas_pipeline* p, int32_t* n_kernels);
 /* One step = one frame of every stream (micro_batch frames with temporal micro-batching).  Asynchronous; adas_pipeline_sync() waits. */

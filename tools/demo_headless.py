@@ -7,7 +7,7 @@ No window, no video codec: frames come from a seeded synthetic 1280x720 clip (mo
 
     python tools/demo_headless.py [--frames 30] [--det yolov8n.onnx|.hipm] [--det-type yolov8|efficientdet] [--lane culane_res18.onnx|.hipm] [--video clip.npy]
                                   [--mjpeg out.mjpeg] [--from-mjpeg in.mjpeg] [--from-yuv in.yuv --yuv-format nv12 --yuv-size 1280x720]
-                                  [--yuv-out out.yuv --yuv-out-format i420]
+                                  [--yuv-out out.yuv --yuv-out-format i420] [--preview-mjpeg small.mjpeg --preview-size 320x180]
                                   [--readout-font FONT.npz [--readout-zoom 2] [--bird-out bird.npy]]
 
 Without model paths, seeded random-weight models are built (their detections are noise: the point is the data flow)."""
@@ -80,6 +80,12 @@ def main():
                          "raw to PATH in --yuv-out-format, tightly packed: `ffmpeg -f rawvideo -pix_fmt yuv420p -s WxH -i PATH` reads an i420 file "
                          "(nv12, nv21, yuyv422, uyvy422 for the others)")
     ap.add_argument("--yuv-out-format", default="i420", choices=["nv12", "nv21", "i420", "yuyv", "uyvy"])
+    ap.add_argument("--preview-mjpeg", default=None, metavar="PATH",
+                    help="a low-rate preview next to the full-size outputs: reduce every frame on the device (postproc.FrameScaler, the exact "
+                         "box filter) from the staged frame in HBM -- the drawn frame with --fonts -- to --preview-size, encode the reduced frame "
+                         "(postproc.JpegEncoder, quality 90) and append its stream to PATH as raw MJPEG; the border of 2 pixels shows the frame's "
+                         "FCWS state")
+    ap.add_argument("--preview-size", default="320x180", metavar="WxH")
     a = ap.parse_args()
     work = tempfile.mkdtemp(prefix="adas_demo_")
     effdet = a.det_type == "efficientdet"
@@ -152,7 +158,14 @@ def main():
     vout = open(a.mjpeg, "wb") if a.mjpeg else None
     writer = PP.YuvWriter(a.yuv_out_format, width, height) if a.yuv_out else None
     yout = open(a.yuv_out, "ab") if a.yuv_out else None
-    written = raw_written = 0
+    scaler = pv_encoder = pout = d_state = None
+    if a.preview_mjpeg:
+        pw, ph = (int(v) for v in a.preview_size.lower().split("x"))
+        scaler = PP.FrameScaler((width, height), (pw, ph), "area", border=2 if min(pw, ph) > 4 else 0)
+        pv_encoder = PP.JpegEncoder(pw, ph, quality=90, capacity=PP.JpegEncoder.bound(pw, ph))
+        pout = open(a.preview_mjpeg, "ab")
+        d_state = PP.L.DeviceBuffer(4)
+    written = raw_written = pv_written = 0
     src = iter(frames) if frames is not None else synthetic_clip(a.frames)
     t0 = time.perf_counter()
     n = 0
@@ -204,6 +217,12 @@ def main():
         if writer is not None:                                                            # demo.py:314, for any other encoder
             writer.run_device(objectDetector.staged_frame.ptr, 1)
             raw_written += yout.write(writer.frame(0).tobytes())
+        if scaler is not None:                                                            # the reduced frame of the same finished frame
+            state = np.array([("UNKNOWN", "NORMAL", "PROMPT", "WARNING").index(analyzeMsg.collision_msg.name)], np.int32)
+            PP.L.check(PP.L.lib().adas_memcpy_h2d(d_state.ptr, PP.L.ptr(state), 4))
+            scaler.run_device(objectDetector.staged_frame.ptr, 1, d_state=d_state.ptr)
+            pv_encoder.run(scaler.device_view(), 1)
+            pv_written += pout.write(pv_encoder.fetch(0))
         n += 1
     dt = time.perf_counter() - t0
     if a.bird_out and n:
@@ -216,6 +235,9 @@ def main():
         yout.close(); writer.close()
         print("%s: %d %s frames of %dx%d appended, %d bytes (%d per frame, 1 / %.1f of the BGR frames)"
               % (a.yuv_out, n, a.yuv_out_format, width, height, raw_written, raw_written // max(n, 1), n * height * width * 3 / max(raw_written, 1)))
+    if scaler is not None:
+        pout.close(); pv_encoder.close(); scaler.close(); d_state.free()
+        print("%s: %d JPEG streams of %s appended, %d bytes (%.0f per frame)" % (a.preview_mjpeg, n, a.preview_size, pv_written, pv_written / max(n, 1)))
     print("%d frames in %.2f s (%.1f frames/s, single stream, host frames: upload + 2 nets + post-processing + fetch per frame)" % (n, dt, n / dt))
     transformView.close(); objectDetector.close(); laneDetector.close(); objectTracker.close()
     if decoder is not None:

@@ -258,6 +258,15 @@ YUVOUT_CHROMA = {"mean": 0, "first": 1}                                      # A
 YUVOUT_SOURCES = {"overlay": 0, "frames": 1}                                 # ADAS_YUVOUT_SRC_*
 
 
+class ScaleParams(C.Structure):                                              # adas_scale_params
+    _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("dst_w", C.c_int32), ("dst_h", C.c_int32), ("mode", C.c_int32), ("cols", C.c_int32),
+                ("rows", C.c_int32), ("border", C.c_int32), ("background", C.c_uint8 * 4), ("border_bgr", (C.c_uint8 * 4) * 4)]
+
+
+SCALE_MODES = {"area": 0, "linear": 1}                                       # ADAS_SCALE_*
+SCALE_SOURCES = {"overlay": 0, "frames": 1}                                  # ADAS_SCALE_SRC_*
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -489,6 +498,18 @@ _SIGS = {
     "adas_yuvout_fetch_all": (C.c_int, [_P, C.c_int, _P]),
     "adas_yuvout_device_view": (C.c_int, [_P, C.POINTER(_P)]),
     "adas_pipeline_attach_yuvout": (C.c_int, [_P, _P, C.c_int]),
+    "adas_scale_default_params": (C.c_int, [C.POINTER(ScaleParams), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "adas_scale_canvas_bytes": (C.c_int64, [C.POINTER(ScaleParams)]),
+    "adas_scale_canvases": (C.c_int, [C.POINTER(ScaleParams), C.c_int]),
+    "adas_scale_create": (C.c_int, [C.POINTER(ScaleParams), C.c_int, C.POINTER(_P)]),
+    "adas_scale_destroy": (C.c_int, [_P]),
+    "adas_scale_run": (C.c_int, [_P, _P, C.c_int, _P, C.c_int64, _P, _P]),
+    "adas_scale_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_scale_fetch_all": (C.c_int, [_P, C.c_int, _P]),
+    "adas_scale_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_pipeline_attach_scale": (C.c_int, [_P, _P, C.c_int]),
+    "adas_pipeline_attach_scale_jpeg": (C.c_int, [_P, _P]),
+    "adas_pipeline_attach_scale_yuvout": (C.c_int, [_P, _P]),
     "adas_pipeline_attach_yuv": (C.c_int, [_P, _P]),
     "adas_pipeline_step_yuv": (C.c_int, [_P, _P, C.c_double]),
     "adas_pipeline_step_yuv_host": (C.c_int, [_P, _P, C.c_double]),

@@ -32,6 +32,7 @@ UNITS = [
     ("jpegdec_kernels.hip", []),
     ("yuv_kernels.hip", []),
     ("yuvout_kernels.hip", []),
+    ("scale_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

@@ -162,6 +162,11 @@ struct adas_yuvout;
 namespace adas {
 void yuvout_geometry_of(const ::adas_yuvout* h, int* width, int* height, int* max_batch);
 }  // namespace adas
+// what adas_pipeline_attach_scale and its two consumers check (scale_kernels.hip); zeros for a null handle
+struct adas_scale;
+namespace adas {
+void scale_geometry_of(const ::adas_scale* h, int* src_w, int* src_h, int* canvas_w, int* canvas_h, int* tiles, int* max_batch, int* border);
+}  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \

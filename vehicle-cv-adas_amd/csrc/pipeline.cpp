@@ -27,6 +27,11 @@ struct adas_pipeline {
     // optional raw-video stage behind the overlay (adas_pipeline_attach_yuvout): every frame as NV12 / NV21 / I420 / YUYV / UYVY
     adas_yuvout* yuvout = nullptr;
     int yuvout_source = ADAS_YUVOUT_SRC_OVERLAY;
+    // optional scaling stage behind the overlay (adas_pipeline_attach_scale): every frame a tile of a canvas, and the canvases' own encoders
+    adas_scale* scale = nullptr;
+    int scale_source = ADAS_SCALE_SRC_OVERLAY;
+    adas_jpeg* scale_jpeg = nullptr;
+    adas_yuvout* scale_yuvout = nullptr;
     hipStream_t st = nullptr;
     hipStream_t st_lane = nullptr;  // graph mode: the lane branch is captured on its own stream so the two nets overlap
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -247,6 +252,40 @@ static int record_step(adas_pipeline* p, const float* d_det, const float* d_lane
         }
         if (text & ~text_scene) {   // the panel strings and the caller's lines lie over the panels
             rc = adas::overlay_draw_text("adas_pipeline_step (overlay text)", p->overlay, text & ~text_scene, S, st);
+            if (rc) return rc;
+        }
+    }
+    if (p->scale) {   // the finished frames as tiles of canvases: behind everything that writes them, read once
+        ADAS_REQUIRE(p->fsrc.frames, ADAS_ERR_INVALID, "the scaling stage needs camera frames: use adas_pipeline_step_frames");
+        const uint8_t* src = p->fsrc.frames;
+        if (p->scale_source == ADAS_SCALE_SRC_OVERLAY) {
+            ADAS_REQUIRE(p->overlay, ADAS_ERR_INVALID, "the scaling stage's overlay source needs an attached overlay handle");
+            rc = adas_overlay_device_view(p->overlay, &src);
+            if (rc) return rc;
+        }
+        int sw = 0, sh = 0, cw = 0, ch = 0, tiles = 0, sb = 0, border = 0;
+        adas::scale_geometry_of(p->scale, &sw, &sh, &cw, &ch, &tiles, &sb, &border);
+        const int* col = nullptr;
+        int stride = 0;
+        if (border > 0) {   // the tiles wear their frames' collision state
+            ADAS_REQUIRE(p->analysis, ADAS_ERR_INVALID, "the scaling stage's border needs an attached analysis handle");
+            const int *fr, *pts;
+            int maxp = 0;
+            adas::analysis_frame_views(p->analysis, &fr, &stride, &pts, &maxp);
+            col = fr + offsetof(adas_analysis_frame, collision_msg) / 4;
+        }
+        rc = adas_scale_run(p->scale, src, S, col, (int64_t)stride * 4, nullptr, st);
+        if (rc) return rc;
+        const uint8_t* canvases = nullptr;
+        rc = adas_scale_device_view(p->scale, &canvases);
+        if (rc) return rc;
+        const int n = (S + tiles - 1) / tiles;
+        if (p->scale_jpeg) {
+            rc = adas_jpeg_run(p->scale_jpeg, canvases, n, st);
+            if (rc) return rc;
+        }
+        if (p->scale_yuvout) {
+            rc = adas_yuvout_run(p->scale_yuvout, canvases, n, nullptr, st);
             if (rc) return rc;
         }
     }
@@ -671,6 +710,7 @@ int adas_pipeline_step(adas_pipeline* p, const float* d_det, const float* d_lane
     ADAS_REQUIRE(!p->jpeg, ADAS_ERR_INVALID, "a JPEG stage is attached: seam tensors carry no frame to encode, use adas_pipeline_step_frames");
     ADAS_REQUIRE(!p->yuvout, ADAS_ERR_INVALID,
                  "a YUV output stage is attached: seam tensors carry no frame to convert, use adas_pipeline_step_frames");
+    ADAS_REQUIRE(!p->scale, ADAS_ERR_INVALID, "a scaling stage is attached: seam tensors carry no frame to scale, use adas_pipeline_step_frames");
     if (!(p->d.use_graph & 1)) {
         p->timed = true;
         return record_step(p, d_det, d_lane, true);
@@ -704,6 +744,12 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
         adas::yuvout_geometry_of(p->yuvout, &yw, &yh, &yb);
         ADAS_REQUIRE(yh == src_h && yw == src_w, ADAS_ERR_INVALID, "the attached YUV output handle was created for %dx%d frames, the step has %dx%d", yw, yh,
                      src_w, src_h);
+    }
+    if (p->scale) {   // and the scaling stage
+        int sw = 0, sh = 0, cw = 0, ch = 0, tiles = 0, sb = 0, border = 0;
+        adas::scale_geometry_of(p->scale, &sw, &sh, &cw, &ch, &tiles, &sb, &border);
+        ADAS_REQUIRE(sh == src_h && sw == src_w, ADAS_ERR_INVALID, "the attached scale handle was created for %dx%d frames, the step has %dx%d", sw, sh, src_w,
+                     src_h);
     }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
     if (!p->det_in && !p->lane_in) {
@@ -769,6 +815,81 @@ int adas_pipeline_step_frames_host(adas_pipeline* p, const uint8_t* h_frames_bgr
 int adas_pipeline_wait_upload(adas_pipeline* p) {
     ADAS_REQUIRE(p, ADAS_ERR_INVALID, "null pipeline");
     if (p->st_copy) ADAS_HIP_TRY(hipStreamSynchronize(p->st_copy));
+    return ADAS_OK;
+}
+
+int adas_pipeline_attach_scale(adas_pipeline* p, adas_scale* scale, int source) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_scale: null pipeline");
+    if (scale) {
+        ADAS_REQUIRE(source == ADAS_SCALE_SRC_OVERLAY || source == ADAS_SCALE_SRC_FRAMES, ADAS_ERR_INVALID, "adas_pipeline_attach_scale: unknown source %d",
+                     source);
+        ADAS_REQUIRE(source != ADAS_SCALE_SRC_OVERLAY || p->overlay, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_scale: the overlay source needs an attached overlay handle (adas_pipeline_attach_overlay first)");
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int sw = 0, sh = 0, cw = 0, ch = 0, tiles = 0, sb = 0, border = 0;
+        adas::scale_geometry_of(scale, &sw, &sh, &cw, &ch, &tiles, &sb, &border);
+        ADAS_REQUIRE(sb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_scale: the scale handle holds %d frames, a step has %d", sb, frames);
+        ADAS_REQUIRE(border == 0 || p->analysis, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_scale: a border of %d pixels needs an attached analysis handle (adas_pipeline_attach_analysis first)", border);
+        if (border > 0) {
+            int af = 0;
+            ADAS_REQUIRE(adas::analysis_capacity(p->analysis, nullptr, &af) && frames <= af, ADAS_ERR_INVALID,
+                         "adas_pipeline_attach_scale: a step has %d frames, the analysis handle holds %d", frames, af);
+        }
+        if (source == ADAS_SCALE_SRC_OVERLAY) {
+            int oh = 0, ow = 0, obh = 0, obw = 0, ob = 0;
+            (void)adas::overlay_geometry(p->overlay, &oh, &ow, &obh, &obw, &ob);
+            ADAS_REQUIRE(oh == sh && ow == sw, ADAS_ERR_INVALID,
+                         "adas_pipeline_attach_scale: the scale handle was created for %dx%d frames, the attached overlay draws %dx%d", sw, sh, ow, oh);
+        }
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->scale = scale;
+    p->scale_source = source;
+    p->scale_jpeg = nullptr;   // the canvases' encoders were checked against the handle that leaves: they are attached again behind a new one
+    p->scale_yuvout = nullptr;
+    return ADAS_OK;
+}
+
+// what both consumers of the canvases check: a handle for `held` frames of w x h against the attached scale handle
+static int scale_consumer_check(const char* who, const char* what, adas_pipeline* p, int w, int h, int held) {
+    ADAS_REQUIRE(p->scale, ADAS_ERR_INVALID, "%s: no scale handle is attached (adas_pipeline_attach_scale first)", who);
+    const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    int sw = 0, sh = 0, cw = 0, ch = 0, tiles = 0, sb = 0, border = 0;
+    adas::scale_geometry_of(p->scale, &sw, &sh, &cw, &ch, &tiles, &sb, &border);
+    ADAS_REQUIRE(w == cw && h == ch, ADAS_ERR_INVALID, "%s: the %s handle was created for %dx%d frames, the scale handle's canvas is %dx%d", who, what, w, h,
+                 cw, ch);
+    const int canvases = (frames + tiles - 1) / tiles;
+    ADAS_REQUIRE(held >= canvases, ADAS_ERR_INVALID, "%s: the %s handle holds %d frames, a step has %d canvases", who, what, held, canvases);
+    return ADAS_OK;
+}
+
+int adas_pipeline_attach_scale_jpeg(adas_pipeline* p, adas_jpeg* jpeg) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_scale_jpeg: null pipeline");
+    if (jpeg) {
+        int jw = 0, jh = 0, jb = 0;
+        adas::jpeg_geometry_of(jpeg, &jw, &jh, &jb);
+        const int rc = scale_consumer_check("adas_pipeline_attach_scale_jpeg", "JPEG", p, jw, jh, jb);
+        if (rc) return rc;
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->scale_jpeg = jpeg;
+    return ADAS_OK;
+}
+
+int adas_pipeline_attach_scale_yuvout(adas_pipeline* p, adas_yuvout* yuvout) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_scale_yuvout: null pipeline");
+    if (yuvout) {
+        int yw = 0, yh = 0, yb = 0;
+        adas::yuvout_geometry_of(yuvout, &yw, &yh, &yb);
+        const int rc = scale_consumer_check("adas_pipeline_attach_scale_yuvout", "YUV output", p, yw, yh, yb);
+        if (rc) return rc;
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    p->scale_yuvout = yuvout;
     return ADAS_OK;
 }
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, YuvWriter, yuv_output_args, host_streams, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, YuvWriter, yuv_output_args, FrameScaler, scale_args, host_streams, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None, yuv_output=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None, yuv_output=None, scale=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -86,7 +86,16 @@ class AdasPipeline:
         yuv420p`, a V4L2 loopback -- behind the overlay's stages, text and panels, one more launch inside the captured step: yuv(frame) ->
         uint8 [frame_bytes] after sync(), yuv_all() -> all of the step's frames in one copy.  source="overlay" (the default) converts the
         drawn frames and needs overlay=; source="frames" converts the camera frames the step was given.  Either needs step_frames /
-        step_frames_host.  Independent of jpeg=: both may be on.  Any micro_batch: frames are independent."""
+        step_frames_host.  Independent of jpeg=: both may be on.  Any micro_batch: frames are independent.
+        scale: None, or dict(size=(w, h), mode="area" | "linear", mosaic=(cols, rows), source="overlay" | "frames", border=0,
+        background=(0, 0, 0), border_colors=None, jpeg=None | dict(quality, capacity), yuv=None | dict(format, matrix, chroma, layout)): every
+        frame of the step reduced to a tile of `size`, mosaic tiles to a canvas (postproc.FrameScaler) -- a preview per stream with
+        mosaic=(1, 1), a video wall of the whole step otherwise -- behind the overlay's stages, text and panels, one more launch inside the
+        captured step: scaled_image(canvas) -> uint8 [rows * h][cols * w][3] after sync().  Frame f (index b * n_streams + s) is cell
+        f % (cols * rows) of canvas f // (cols * rows), so any micro_batch works.  border > 0 draws each tile's collision state as a frame of
+        border_colors[state] and needs analysis=.  jpeg= and yuv= add a second JpegEncoder and a second YuvWriter at the canvas size that
+        consume the canvases inside the same step: scaled_jpeg(canvas), scaled_jpeg_lengths(), scaled_yuv(canvas), scaled_yuv_all().
+        source="overlay" (the default) needs overlay=.  Independent of jpeg= and yuv_output=, which keep encoding the full frames."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
@@ -94,6 +103,7 @@ class AdasPipeline:
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
         self.overlay = self.jpeg_encoder = self.jpeg_decoder = self.yuv_converter = self.yuv_writer = None
+        self.scaler = self.scaled_jpeg_encoder = self.scaled_yuv_writer = None
         if jpeg_input is not None and jpeg_input is not False:
             jpeg_input = {} if jpeg_input is True else dict(jpeg_input)
             unknown = set(jpeg_input) - {"capacity"}
@@ -137,6 +147,39 @@ class AdasPipeline:
             if yuv_output.get("source", "overlay") == "overlay" and overlay is None:
                 raise ValueError("yuv_output= with source=\"overlay\" needs overlay= (the drawn frames it converts); source=\"frames\" converts the "
                                  "camera frames")
+        if scale is not None:
+            if not isinstance(scale, dict):
+                raise ValueError("scale= %r is neither None nor a dict (size, mode, mosaic, source, border, background, border_colors, jpeg, yuv)" % (scale,))
+            scale = dict(scale)
+            unknown = set(scale) - {"size", "mode", "mosaic", "source", "border", "background", "border_colors", "jpeg", "yuv"}
+            if unknown:
+                raise ValueError("scale= holds unknown keys %s (size, mode, mosaic, source, border, background, border_colors, jpeg, yuv)" % sorted(unknown))
+            if "size" not in scale:
+                raise ValueError("scale= needs size=(w, h), the tile every frame is reduced to")
+            scale_checked = scale_args((src_hw[1], src_hw[0]), scale["size"], scale.get("mode", "area"), scale.get("mosaic", (1, 1)), scale.get("border", 0),
+                                       scale.get("background", (0, 0, 0)), scale.get("border_colors"), what="scale= ")
+            if scale.get("source", "overlay") not in L.SCALE_SOURCES:
+                raise ValueError("scale= source %r is neither \"overlay\" nor \"frames\"" % (scale.get("source"),))
+            if scale.get("source", "overlay") == "overlay" and overlay is None:
+                raise ValueError("scale= with source=\"overlay\" needs overlay= (the drawn frames it reduces); source=\"frames\" reduces the camera frames")
+            if scale_checked["border"] > 0 and analysis is None:
+                raise ValueError("scale= with border > 0 needs analysis= (the collision state a tile's border shows)")
+            if scale.get("jpeg") is not None:
+                if not isinstance(scale["jpeg"], dict):
+                    raise ValueError("scale= jpeg %r is neither None nor a dict (quality, capacity)" % (scale["jpeg"],))
+                unknown = set(scale["jpeg"]) - {"quality", "capacity"}
+                if unknown:
+                    raise ValueError("scale= jpeg holds unknown keys %s (quality, capacity)" % sorted(unknown))
+                if not 1 <= int(scale["jpeg"].get("quality", 90)) <= 100:
+                    raise ValueError("scale= jpeg quality %r is outside 1..100" % (scale["jpeg"].get("quality"),))
+            if scale.get("yuv") is not None:
+                if not isinstance(scale["yuv"], dict):
+                    raise ValueError("scale= yuv %r is neither None nor a dict (format, matrix, chroma, layout)" % (scale["yuv"],))
+                unknown = set(scale["yuv"]) - {"format", "matrix", "chroma", "layout"}
+                if unknown:
+                    raise ValueError("scale= yuv holds unknown keys %s (format, matrix, chroma, layout)" % sorted(unknown))
+                yuv_output_args(scale["yuv"].get("format", "i420"), scale["yuv"].get("matrix", "video"), scale["yuv"].get("chroma", "mean"),
+                                scale["yuv"].get("layout"), what="scale= yuv ")
         if overlay is not None:
             if geometry is None or not lane_model:
                 raise ValueError("overlay= needs lane_model= and geometry= (the lane points and the ego-lane polygon it draws)")
@@ -274,6 +317,20 @@ class AdasPipeline:
             self.yuv_writer = YuvWriter(yuv_output.get("format", "i420"), src_hw[1], src_hw[0], yuv_output.get("matrix", "video"),
                                         yuv_output.get("chroma", "mean"), yuv_output.get("layout"), n_streams)
             L.check(L.lib().adas_pipeline_attach_yuvout(self.h, self.yuv_writer.h, L.YUVOUT_SOURCES[yuv_output.get("source", "overlay")]))
+        if scale is not None:
+            self.scaler = FrameScaler(scale_checked["src_wh"], scale_checked["size"], scale_checked["mode"], scale_checked["mosaic"], scale_checked["border"],
+                                      scale_checked["background"], scale_checked["border_colors"], n_streams)
+            L.check(L.lib().adas_pipeline_attach_scale(self.h, self.scaler.h, L.SCALE_SOURCES[scale.get("source", "overlay")]))
+            ch, cw = self.scaler.canvas_hw
+            if scale.get("jpeg") is not None:
+                self.scaled_jpeg_encoder = JpegEncoder(cw, ch, int(scale["jpeg"].get("quality", 90)), self.scaler.canvases(n_streams),
+                                                       scale["jpeg"].get("capacity"))
+                L.check(L.lib().adas_pipeline_attach_scale_jpeg(self.h, self.scaled_jpeg_encoder.h))
+            if scale.get("yuv") is not None:
+                y = scale["yuv"]
+                self.scaled_yuv_writer = YuvWriter(y.get("format", "i420"), cw, ch, y.get("matrix", "video"), y.get("chroma", "mean"), y.get("layout"),
+                                                   self.scaler.canvases(n_streams))
+                L.check(L.lib().adas_pipeline_attach_scale_yuvout(self.h, self.scaled_yuv_writer.h))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
@@ -377,6 +434,37 @@ class AdasPipeline:
             raise ValueError("the pipeline was created without yuv_output=")
         return self.yuv_writer.frame(frame)
 
+    def scaled_image(self, canvas=0):
+        """Canvas `canvas` of the last step_frames (after sync()): uint8 [rows * h][cols * w][3] BGR, frame f in cell f % (cols * rows) of
+        canvas f // (cols * rows)."""
+        if self.scaler is None:
+            raise ValueError("the pipeline was created without scale=")
+        return self.scaler.canvas(canvas)
+
+    def scaled_jpeg(self, canvas=0):
+        """Canvas `canvas` of the last step (after sync()) as a baseline JPEG stream: uint8 [length]."""
+        if self.scaled_jpeg_encoder is None:
+            raise ValueError("the pipeline was created without scale= jpeg")
+        return self.scaled_jpeg_encoder.fetch(canvas)
+
+    def scaled_jpeg_lengths(self):
+        """The stream lengths of the last step's canvases."""
+        if self.scaled_jpeg_encoder is None:
+            raise ValueError("the pipeline was created without scale= jpeg")
+        return self.scaled_jpeg_encoder.lengths(self.scaler.canvases(self.S * self.B))
+
+    def scaled_yuv(self, canvas=0):
+        """Canvas `canvas` of the last step (after sync()) in scale= yuv's format: uint8 [scaled_yuv_writer.frame_bytes]."""
+        if self.scaled_yuv_writer is None:
+            raise ValueError("the pipeline was created without scale= yuv")
+        return self.scaled_yuv_writer.frame(canvas)
+
+    def scaled_yuv_all(self, out=None):
+        """All canvases of the last step (after sync()) in one copy, canvas k at k * scaled_yuv_writer.p.frame_stride."""
+        if self.scaled_yuv_writer is None:
+            raise ValueError("the pipeline was created without scale= yuv")
+        return self.scaled_yuv_writer.fetch_all(self.scaler.canvases(self.S * self.B), out)
+
     def yuv_all(self, out=None):
         """All n_streams x micro_batch frames of the last step (after sync()) in one copy: uint8 [yuv_writer.batch_bytes(frames)], frame f at
         f * yuv_writer.p.frame_stride.  out: a uint8 array to fill (pinned: _lib.PinnedBuffer(...).array)."""
@@ -413,7 +501,8 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (getattr(self, "yuv_writer", None), getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
+        for o in (getattr(self, "scaled_yuv_writer", None), getattr(self, "scaled_jpeg_encoder", None), getattr(self, "scaler", None),
+                  getattr(self, "yuv_writer", None), getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()
 

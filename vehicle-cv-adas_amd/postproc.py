@@ -1250,6 +1250,127 @@ class YuvWriter:
     __del__ = close
 
 
+SCALE_DEFAULT_BORDER_COLORS = ((0, 255, 255), (0, 255, 0), (0, 102, 255), (0, 0, 255))   # demo.py's ControlPanel.CollisionDict, BGR
+
+
+def _bgr(v, what):
+    try:
+        c = tuple(int(x) for x in v)
+    except (TypeError, ValueError):
+        c = ()
+    if len(c) != 3 or any(x < 0 or x > 255 for x in c) or any(int(x) != x for x in v):
+        raise ValueError("%s %r is no (B, G, R) of integers in 0..255" % (what, v))
+    return c
+
+
+def _pair(v, what, lo=1):
+    try:
+        a, b = v
+        ok = int(a) == a and int(b) == b and a >= lo and b >= lo
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s %r is no pair of integers >= %d" % (what, v, lo))
+    return int(a), int(b)
+
+
+def scale_args(src_wh, size, mode="area", mosaic=(1, 1), border=0, background=(0, 0, 0), border_colors=None, what=""):
+    """FrameScaler's argument checks without a handle (so without a GPU): ValueError naming the key.  Returns the checked values as a dict."""
+    if mode not in L.SCALE_MODES:
+        raise ValueError("%smode %r is neither \"area\" nor \"linear\"" % (what, mode))
+    sw, sh = _pair(src_wh, what + "src_wh")
+    dw, dh = _pair(size, what + "size")
+    cols, rows = _pair(mosaic, what + "mosaic")
+    if max(sw, sh, dw, dh, cols, rows) > 16383:
+        raise ValueError("%ssides and mosaic counts must stay within 16383 (src_wh %r, size %r, mosaic %r)" % (what, src_wh, size, mosaic))
+    if mode == "area" and (dw > sw or dh > sh):
+        raise ValueError("%smode \"area\" does not enlarge: size %r from %r" % (what, (dw, dh), (sw, sh)))
+    if mode == "area" and sw * sh > 1 << 23:
+        raise ValueError("%smode \"area\" needs src_w * src_h <= 8388608, got %r" % (what, (sw, sh)))
+    if isinstance(border, bool) or not isinstance(border, int) or border < 0 or 2 * border >= min(dw, dh):
+        raise ValueError("%sborder %r must be an integer >= 0 with 2 * border < min(size)" % (what, border))
+    if cols * dw * 3 * rows * dh > 0x7fffffff:
+        raise ValueError("%sa canvas of %dx%d tiles of %r must stay below 2^31 bytes" % (what, cols, rows, (dw, dh)))
+    colors = SCALE_DEFAULT_BORDER_COLORS if border_colors is None else border_colors
+    try:
+        n = len(colors)
+    except TypeError:
+        n = -1
+    if n != 4:
+        raise ValueError("%sborder_colors %r is no list of four (B, G, R): UNKNOWN, NORMAL, PROMPT, WARNING" % (what, border_colors))
+    return dict(src_wh=(sw, sh), size=(dw, dh), mode=mode, mosaic=(cols, rows), border=border, background=_bgr(background, what + "background"),
+                border_colors=tuple(_bgr(c, what + "border_colors[%d]" % i) for i, c in enumerate(colors)))
+
+
+class FrameScaler:
+    """Finished BGR frames on the device reduced to previews or a mosaic (adas_scale_*): every frame becomes a tile of `size` (w, h), a canvas
+    is mosaic = (cols, rows) tiles, frame f goes to canvas f // (cols * rows) and cell f % (cols * rows) in row-major order; (1, 1) is one
+    reduced frame per frame.  What a caller's cv2.resize per frame and NumPy slice assignments do on host cores after fetching every full
+    frame.  The rules S1-S8 are csrc/scale_core.h.  mode: "area" (an exact integer box filter, reduction only) or "linear" (8-bit
+    INTER_LINEAR, the bird panel's rule).  border: pixel rings of a tile that take border_colors[state] when a run is given states
+    (ANA_COLLISION_*: UNKNOWN, NORMAL, PROMPT, WARNING).  background: the (B, G, R) of a cell without a frame.  canvas_hw: (rows * h,
+    cols * w)."""
+
+    def __init__(self, src_wh, size, mode="area", mosaic=(1, 1), border=0, background=(0, 0, 0), border_colors=None, max_batch=1):
+        a = scale_args(src_wh, size, mode, mosaic, border, background, border_colors)
+        self.p = L.ScaleParams()
+        L.check(L.lib().adas_scale_default_params(C.byref(self.p), a["src_wh"][0], a["src_wh"][1], a["size"][0], a["size"][1]))
+        self.p.mode = L.SCALE_MODES[mode]
+        self.p.cols, self.p.rows = a["mosaic"]
+        self.p.border = a["border"]
+        for c in range(3):
+            self.p.background[c] = a["background"][c]
+            for k in range(4):
+                self.p.border_bgr[k][c] = a["border_colors"][k][c]
+        self.src_wh, self.size, self.mode, self.mosaic, self.border, self.max_batch = a["src_wh"], a["size"], mode, a["mosaic"], a["border"], int(max_batch)
+        self.canvas_hw = (self.mosaic[1] * self.size[1], self.mosaic[0] * self.size[0])
+        h = C.c_void_p()
+        L.check(L.lib().adas_scale_create(C.byref(self.p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        self.canvas_bytes = int(L.lib().adas_scale_canvas_bytes(C.byref(self.p)))
+
+    def canvases(self, n):
+        """Canvases a run of n frames writes."""
+        return -(-int(n) // (self.mosaic[0] * self.mosaic[1]))
+
+    def run_device(self, d_ptr, n, d_state=None, state_stride=4, d_dst=None, stream=None):
+        """n BGR frames [n][src_h][src_w][3] u8 on the device (any byte).  d_state: frame f's int32 state at d_state + f * state_stride bytes
+        (None: no border is drawn).  d_dst: device pointer of canvases(n) * canvas_bytes bytes (None: the handle's own buffer).  Asynchronous
+        on `stream`."""
+        L.check(L.lib().adas_scale_run(self.h, d_ptr, int(n), d_state, int(state_stride), d_dst, stream))
+
+    def canvas(self, i=0):
+        """Canvas i of the last run into the handle's own buffer: uint8 [rows * h][cols * w][3].  Waits for that run."""
+        out = np.empty(self.canvas_hw + (3,), np.uint8)
+        L.check(L.lib().adas_scale_fetch(self.h, int(i), L.ptr(out)))
+        return out
+
+    def fetch_all(self, n, out=None):
+        """The canvases of the last run's first n frames in ONE copy: uint8 [canvases(n)][rows * h][cols * w][3].  out: a uint8 array of at
+        least that size to fill (_lib.PinnedBuffer(...).array for the fastest copy); the filled part is returned."""
+        k = self.canvases(n)
+        need = k * self.canvas_bytes
+        if out is None:
+            out = np.empty(need, np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.nbytes < need:
+            raise ValueError("fetch_all needs a contiguous uint8 array of at least %d bytes" % need)
+        L.check(L.lib().adas_scale_fetch_all(self.h, k, L.ptr(out)))
+        return out.reshape(-1)[:need].reshape((k,) + self.canvas_hw + (3,))
+
+    def device_view(self):
+        """Device pointer of the handle's own canvases, canvas k at k * canvas_bytes."""
+        d = C.c_void_p()
+        L.check(L.lib().adas_scale_device_view(self.h, C.byref(d)))
+        return d.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_scale_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
