@@ -1308,6 +1308,51 @@ int adas_scale_fetch_all(adas_scale* h, int canvases, uint8_t* h_dst);
 int adas_scale_device_view(adas_scale* h, const uint8_t** d_canvases);
 
 /* ===================================================================================
+ * Camera frames rectified on the device, in FRONT of the step: cv2.remap(frame, map1, map2, INTER_LINEAR, BORDER_CONSTANT 0) of BGR u8 frames
+ * in HBM through a fixed-point map per stream -- what a caller's cv2.undistort / cv2.remap does on host cores before the upload.  A map is
+ * cv2's CV_16SC2 + CV_16UC1 pair: (sx, sy) int16 per destination pixel and a fraction word ay * 32 + ax (ax, ay in 0..31; the top 6 bits are
+ * ignored).  It is either built here from a lens model as cv2.initUndistortRectifyMap(K, D, R, new_K, size, CV_16SC2) writes it (Brown-Conrady
+ * / rational: k1 k2 p1 p2 k3 k4 k5 k6), or the caller's own table, which covers fisheye lenses, stereo rectification and anything else cv2
+ * can tabulate.  The rules U1-U6 are csrc/remap_core.h; OpenCV's arithmetic restated, parity with a real cv2 build unpinned.  Frame f of a
+ * batch belongs to stream f % n_streams and reads the map assigned to that stream; several streams may share one map.
+ * =================================================================================== */
+typedef struct adas_remap adas_remap;
+typedef struct {
+    int src_h, src_w;               /* a camera frame */
+    int dst_h, dst_w;               /* a rectified frame: rectification often crops */
+    int n_streams, n_maps;          /* streams of a batch; maps the handle holds */
+} adas_remap_params;
+typedef struct {
+    double K[4];                    /* fx, fy, cx, cy of the camera */
+    double D[8];                    /* k1, k2, p1, p2, k3, k4, k5, k6; a shorter list is zero-padded */
+    double new_K[4];                /* fx, fy, cx, cy of the rectified image (cv2.undistort's default: K) */
+    double R[9];                    /* rectifying rotation, row-major (default: identity) */
+} adas_remap_camera;
+/* ADAS_ERR_INVALID by name: "size outside 1..4320 rows x 1..16384 columns"; n_streams, n_maps or max_batch outside 1..65535.  The handle is
+ * host state until the first set call (or adas_remap_device_view) allocates n_maps maps and max_batch BGR frames. */
+int adas_remap_create(const adas_remap_params* p, int max_batch, adas_remap** out);
+int adas_remap_destroy(adas_remap* h);
+/* Builds map `map` (-1: every map) from a lens model on the device.  ADAS_ERR_INVALID by name: "non-finite parameter", "zero focal length"
+ * (fx, fy of K or new_K), "singular new_K * R", "map index outside the handle's table".  Ordered behind the handle's last run on that run's
+ * stream, and finished on return. */
+int adas_remap_set_camera(adas_remap* h, int map, const adas_remap_camera* cam);
+/* Map `map` from the caller: h_xy [dst_h][dst_w][2] int16, h_frac [dst_h][dst_w] uint16.  Ordered as adas_remap_set_camera. */
+int adas_remap_set_map(adas_remap* h, int map, const int16_t* h_xy, const uint16_t* h_frac);
+/* Stream `stream` reads map `map` from the next run on.  Default: stream s reads map min(s, n_maps - 1). */
+int adas_remap_assign(adas_remap* h, int stream, int map);
+/* Map `map` as the runs read it, in adas_remap_set_map's layout.  ADAS_ERR_INVALID for a map that was never set. */
+int adas_remap_fetch_map(adas_remap* h, int map, int16_t* h_xy, uint16_t* h_frac);
+/* d_src_bgr [batch][src_h][src_w][3] u8 on the device, any alignment.  d_dst_bgr [batch][dst_h][dst_w][3], any alignment; NULL: the handle's
+ * own buffer.  Every byte of frames [0, batch) is written exactly once and no other byte.  ADAS_ERR_INVALID for batch > max_batch and for a
+ * stream whose map was never set.  One plain launch, asynchronous on `stream`, capturable. */
+int adas_remap_run(adas_remap* h, const uint8_t* d_src_bgr, int batch, uint8_t* d_dst_bgr, void* stream);
+/* Frame `frame` of the handle's own buffer -> h_bgr [dst_h][dst_w][3], after the last run's stream has drained.  The set calls, the fetches and
+ * this call use the stream of the handle's last run: that stream must still exist (a caller who destroys it first runs the handle once more
+ * on another stream, or detaches it from its pipeline). */
+int adas_remap_fetch(adas_remap* h, int frame, uint8_t* h_bgr);
+int adas_remap_device_view(adas_remap* h, const uint8_t** d_frames_bgr);
+
+/* ===================================================================================
  * ByteTrack: replaces BYTETracker.__init__/update/reset (byteTracker.py:30-51,62-185,187-200)
  * with matching.py, kalman_filter.py, strack.py, base_track.py, byteTrack/utils.py underneath.
  * One independent tracker (own id counter) per stream; the whole update runs on the GPU.
@@ -1525,9 +1570,19 @@ int adas_pipeline_step_yuv(adas_pipeline* p, const uint8_t* d_src, double lane_c
  * of adas_pipeline_step_frames_host on 1.5 or 2 bytes per pixel -- the copy runs on the copy stream into one of two device buffers
  * while the previous step still computes, the conversion waits for it.  adas_pipeline_wait_upload keeps its meaning. */
 int adas_pipeline_step_yuv_host(adas_pipeline* p, const uint8_t* h_src, double lane_crop_ratio);
+/* Optional rectification stage in FRONT of the step, outside the capture, behind every way in (adas_pipeline_step_frames, _frames_host,
+ * _jpeg_host, _yuv, _yuv_host): adas_pipeline_step_frames first runs adas_remap_run on the main stream from the frames it was given into the
+ * handle's own buffer, and the whole step -- pre-processing, the bird-view warp, the overlay, the *_SRC_FRAMES sources -- reads that buffer:
+ * one address, so one captured step.  The handle's source and destination sizes must both equal the step's camera geometry (checked at the
+ * step), its n_streams the pipeline's, and it must hold n_streams x micro_batch frames.  remap == NULL detaches.  Cached graphs are dropped.
+ * Without it no line of the step's path changes.  The handle stays the caller's; adas_remap_fetch after adas_pipeline_sync.  The handle
+ * remembers the pipeline's stream as that of its last run; detaching it and adas_pipeline_destroy synchronise that stream and hand the
+ * handle back with no stream remembered, so it must outlive the pipeline or be detached first. */
+int adas_pipeline_attach_remap(adas_pipeline* p, adas_remap* remap);
 int adas_pipeline_sync(adas_pipeline* p);
 /* Device time of the last `n` steps' sections in ms (hipEvents on the pipeline stream):
- * [0] detector net, [1] yolo post, [2] lane net, [3] lane decode, [4] tracker, [5] whole step. */
+ * [0] detector net, [1] yolo post, [2] lane net, [3] lane decode, [4] tracker, [5] whole step.  The stages in FRONT of the step -- an attached
+ * decoder, converter or remap handle -- are launched before the step's first event and are not part of any of the six figures. */
 int adas_pipeline_timings(adas_pipeline* p, float ms[6]);
 
 #ifdef __cplusplus

@@ -86,6 +86,11 @@ def main():
                          "(postproc.JpegEncoder, quality 90) and append its stream to PATH as raw MJPEG; the border of 2 pixels shows the frame's "
                          "FCWS state")
     ap.add_argument("--preview-size", default="320x180", metavar="WxH")
+    ap.add_argument("--undistort", default=None, metavar="CAMERA.json",
+                    help="the cv2.undistort a caller with a wide-angle camera runs in front of demo.py's loop: CAMERA.json holds {\"K\": [fx, fy, cx, "
+                         "cy] or 3x3, \"D\": [k1, k2, p1, p2, (k3, (k4, k5, k6))], \"new_K\": optional}; the map is built on the device as "
+                         "cv2.initUndistortRectifyMap writes it and every frame, whichever way it came in, is resampled through it on the device "
+                         "(postproc.FrameRemapper) before the detectors see it")
     a = ap.parse_args()
     work = tempfile.mkdtemp(prefix="adas_demo_")
     effdet = a.det_type == "efficientdet"
@@ -167,6 +172,22 @@ def main():
         d_state = PP.L.DeviceBuffer(4)
     written = raw_written = pv_written = 0
     src = iter(frames) if frames is not None else synthetic_clip(a.frames)
+    remapper = None
+    if a.undistort:
+        import json
+        cam = json.load(open(a.undistort))
+        unknown = set(cam) - {"K", "D", "new_K"}
+        if unknown or "K" not in cam:
+            raise SystemExit("%s: a camera file holds K, D and optionally new_K (unknown: %s)" % (a.undistort, sorted(unknown)))
+        remapper = PP.FrameRemapper((height, width), 1, cameras=[cam])
+        d_cam = PP.L.DeviceBuffer(height * width * 3)
+
+        def rectified(it):
+            for f in it:
+                d_cam.upload(np.ascontiguousarray(f, np.uint8))
+                remapper.run(d_cam.ptr, 1)
+                yield remapper.fetch(0)
+        src = rectified(src)
     t0 = time.perf_counter()
     n = 0
     for frame in src:
@@ -242,6 +263,8 @@ def main():
     transformView.close(); objectDetector.close(); laneDetector.close(); objectTracker.close()
     if decoder is not None:
         decoder.close()
+    if remapper is not None:
+        remapper.close(); d_cam.free()
     return n
 
 

@@ -267,6 +267,14 @@ SCALE_MODES = {"area": 0, "linear": 1}                                       # A
 SCALE_SOURCES = {"overlay": 0, "frames": 1}                                  # ADAS_SCALE_SRC_*
 
 
+class RemapParams(C.Structure):                                              # adas_remap_params
+    _fields_ = [("src_h", C.c_int), ("src_w", C.c_int), ("dst_h", C.c_int), ("dst_w", C.c_int), ("n_streams", C.c_int), ("n_maps", C.c_int)]
+
+
+class RemapCamera(C.Structure):                                              # adas_remap_camera
+    _fields_ = [("K", C.c_double * 4), ("D", C.c_double * 8), ("new_K", C.c_double * 4), ("R", C.c_double * 9)]
+
+
 class BytetrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_double), ("match_thresh", C.c_double), ("frame_rate", C.c_double),
                 ("track_buffer", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("reserved", C.c_int32)]
@@ -510,6 +518,16 @@ _SIGS = {
     "adas_pipeline_attach_scale": (C.c_int, [_P, _P, C.c_int]),
     "adas_pipeline_attach_scale_jpeg": (C.c_int, [_P, _P]),
     "adas_pipeline_attach_scale_yuvout": (C.c_int, [_P, _P]),
+    "adas_remap_create": (C.c_int, [C.POINTER(RemapParams), C.c_int, C.POINTER(_P)]),
+    "adas_remap_destroy": (C.c_int, [_P]),
+    "adas_remap_set_camera": (C.c_int, [_P, C.c_int, C.POINTER(RemapCamera)]),
+    "adas_remap_set_map": (C.c_int, [_P, C.c_int, _P, _P]),
+    "adas_remap_assign": (C.c_int, [_P, C.c_int, C.c_int]),
+    "adas_remap_fetch_map": (C.c_int, [_P, C.c_int, _P, _P]),
+    "adas_remap_run": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "adas_remap_fetch": (C.c_int, [_P, C.c_int, _P]),
+    "adas_remap_device_view": (C.c_int, [_P, C.POINTER(_P)]),
+    "adas_pipeline_attach_remap": (C.c_int, [_P, _P]),
     "adas_pipeline_attach_yuv": (C.c_int, [_P, _P]),
     "adas_pipeline_step_yuv": (C.c_int, [_P, _P, C.c_double]),
     "adas_pipeline_step_yuv_host": (C.c_int, [_P, _P, C.c_double]),

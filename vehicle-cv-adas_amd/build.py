@@ -33,6 +33,7 @@ UNITS = [
     ("yuv_kernels.hip", []),
     ("yuvout_kernels.hip", []),
     ("scale_kernels.hip", ["-ffp-contract=off"]),
+    ("remap_kernels.hip", ["-ffp-contract=off"]),
     ("conv_kernels.hip", []),
     ("conv_x3.hip", []),
     ("conv_halo.hip", []),

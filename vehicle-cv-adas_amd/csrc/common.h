@@ -167,6 +167,14 @@ struct adas_scale;
 namespace adas {
 void scale_geometry_of(const ::adas_scale* h, int* src_w, int* src_h, int* canvas_w, int* canvas_h, int* tiles, int* max_batch, int* border);
 }  // namespace adas
+// what adas_pipeline_attach_remap checks and adas_pipeline_step_frames uses (remap_kernels.hip): the handle's geometry (zeros for a null
+// handle) and its own BGR frames (null until the handle has touched the device)
+struct adas_remap;
+namespace adas {
+void remap_geometry_of(const ::adas_remap* h, int* src_h, int* src_w, int* dst_h, int* dst_w, int* n_streams, int* max_batch);
+uint8_t* remap_frames(::adas_remap* h);
+void remap_forget_stream(::adas_remap* h);   // the handle's last run has drained and its stream goes away: later calls use the null stream
+}  // namespace adas
 
 #define ADAS_HIP_TRY(expr)                                                     \
     do {                                                                        \

@@ -84,6 +84,8 @@ struct adas_pipeline {
     size_t yuv_stage_bytes = 0;
     hipEvent_t ev_ycopied[2] = {nullptr, nullptr}, ev_yconsumed[2] = {nullptr, nullptr};
     unsigned long long yuv_steps = 0;
+    // step_frames: the rectification in front of the step (adas_pipeline_attach_remap), behind every way in; the step reads the handle's frames
+    adas_remap* remap = nullptr;
 };
 
 using namespace adas;
@@ -628,6 +630,10 @@ int adas_pipeline_destroy(adas_pipeline* p) {
     if (!p) return ADAS_OK;
     drop_graphs(p);
     if (p->analysis) (void)adas::analysis_bind_birdview(p->analysis, nullptr, 0, nullptr);   // its reset no longer queues on this pipeline's stream
+    if (p->remap) {   // nor do the remap handle's set calls and fetches
+        if (p->st) (void)hipStreamSynchronize(p->st);
+        adas::remap_forget_stream(p->remap);
+    }
     for (auto& e : p->ev)
         if (e) (void)hipEventDestroy(e);
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
@@ -752,6 +758,15 @@ int adas_pipeline_step_frames(adas_pipeline* p, const uint8_t* d_frames_bgr, int
                      src_h);
     }
     const size_t S = (size_t)p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+    if (p->remap) {   // outside the captured step, like the decoder and the converter: the step below reads the handle's own frames
+        int rsh = 0, rsw = 0, rdh = 0, rdw = 0, rns = 0, rb = 0;
+        adas::remap_geometry_of(p->remap, &rsh, &rsw, &rdh, &rdw, &rns, &rb);
+        ADAS_REQUIRE(rsh == src_h && rsw == src_w, ADAS_ERR_INVALID, "the attached remap handle was created for %dx%d frames, the step has %dx%d", rsw, rsh,
+                     src_w, src_h);
+        int rc = adas_remap_run(p->remap, d_frames_bgr, (int)S, nullptr, p->st);
+        if (rc) return rc;
+        d_frames_bgr = adas::remap_frames(p->remap);
+    }
     if (!p->det_in && !p->lane_in) {
         const char* env = getenv("ADAS_NO_PACKED_SEAM");
         p->packed = !(env && env[0] == '1') && (!p->d.detector || adas_engine_accepts_packed_input(p->d.detector)) &&
@@ -1001,6 +1016,28 @@ int adas_pipeline_step_yuv_host(adas_pipeline* p, const uint8_t* h_src, double l
     ADAS_HIP_TRY(hipEventRecord(p->ev_yconsumed[k], p->st));   // the conversion alone reads the buffer: the next copy into it need not wait for the step
     ++p->yuv_steps;
     return adas_pipeline_step_frames(p, adas::yuv_frames(p->yuv), yh, yw, lane_crop_ratio);
+}
+
+int adas_pipeline_attach_remap(adas_pipeline* p, adas_remap* remap) {
+    ADAS_REQUIRE(p, ADAS_ERR_INVALID, "adas_pipeline_attach_remap: null pipeline");
+    if (remap) {
+        const int frames = p->d.n_streams * (p->d.micro_batch > 1 ? p->d.micro_batch : 1);
+        int sh = 0, sw = 0, dh = 0, dw = 0, ns = 0, rb = 0;
+        adas::remap_geometry_of(remap, &sh, &sw, &dh, &dw, &ns, &rb);
+        ADAS_REQUIRE(sh == dh && sw == dw, ADAS_ERR_INVALID,
+                     "adas_pipeline_attach_remap: the step reads frames of the size it is given: the remap handle turns %dx%d into %dx%d", sw, sh, dw, dh);
+        ADAS_REQUIRE(ns == p->d.n_streams, ADAS_ERR_INVALID, "adas_pipeline_attach_remap: the remap handle was created for %d streams, the pipeline has %d", ns,
+                     p->d.n_streams);
+        ADAS_REQUIRE(rb >= frames, ADAS_ERR_INVALID, "adas_pipeline_attach_remap: the remap handle holds %d frames, a step has %d", rb, frames);
+        const uint8_t* own = nullptr;   // the buffer the captured step will read exists from here on
+        int rc = adas_remap_device_view(remap, &own);
+        if (rc) return rc;
+    }
+    ADAS_HIP_TRY(hipStreamSynchronize(p->st));
+    drop_graphs(p);
+    if (p->remap) adas::remap_forget_stream(p->remap);   // the handle that leaves has drained: its fetches no longer need this pipeline's stream
+    p->remap = remap;
+    return ADAS_OK;
 }
 
 int adas_pipeline_sync(adas_pipeline* p) {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib as L
 from .coreEngine import HipEngine
-from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, YuvWriter, yuv_output_args, FrameScaler, scale_args, host_streams, letterbox
+from .postproc import YoloPost, UfldDecode, Ufld1Decode, LaneGeometry, DeviceTracker, BirdView, PerspectiveWarp, Analysis, LaneOverlay, JpegEncoder, JpegDecoder, YuvConverter, YuvWriter, yuv_output_args, FrameScaler, scale_args, FrameRemapper, undistort_args, host_streams, letterbox
 from . import sharding
 
 CULANE = dict(grid_row=200, cls_row=72, grid_col=100, cls_col=81,
@@ -21,7 +21,7 @@ class AdasPipeline:
     def __init__(self, det_model=None, lane_model=None, n_streams=1, precision=None, src_hw=(720, 1280),
                  box_score=0.4, nms_iou=0.45, head_layout=L.HEAD_V8, num_classes=None, use_graph=True,
                  max_candidates=512, track=True, lane_cfg=None, nms_mode=L.NMS_REFERENCE, overlap=True, geometry=None, micro_batch=1,
-                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None, yuv_output=None, scale=None):
+                 birdview=None, analysis=None, overlay=None, jpeg=None, jpeg_input=None, yuv_input=None, yuv_output=None, scale=None, undistort=None):
         """geometry: None, or dict(bird_wh=(w, h), M=3x3, adjust_lanes=True) to run the lane-geometry kernel behind the decode.
         micro_batch B > 1: temporal micro-batching (adas_pipeline_desc.micro_batch) -- a step takes B consecutive frames of every
         stream, frame b of stream s at index b * n_streams + s of the input and of every per-frame fetch; the tracker consumes
@@ -95,7 +95,16 @@ class AdasPipeline:
         f % (cols * rows) of canvas f // (cols * rows), so any micro_batch works.  border > 0 draws each tile's collision state as a frame of
         border_colors[state] and needs analysis=.  jpeg= and yuv= add a second JpegEncoder and a second YuvWriter at the canvas size that
         consume the canvases inside the same step: scaled_jpeg(canvas), scaled_jpeg_lengths(), scaled_yuv(canvas), scaled_yuv_all().
-        source="overlay" (the default) needs overlay=.  Independent of jpeg= and yuv_output=, which keep encoding the full frames."""
+        source="overlay" (the default) needs overlay=.  Independent of jpeg= and yuv_output=, which keep encoding the full frames.
+        undistort: None, or dict(camera=dict(K=, D=, new_K=None, R=None)) | dict(cameras=[one such dict per stream]) | dict(maps=[(xy, frac),
+        ...], stream_map=[map of stream s, ...]): a rectification stage in FRONT of the step (postproc.FrameRemapper at src_hw) for cameras
+        whose frames are not pinhole images -- in place of the cv2.undistort / cv2.remap a caller's host code would run before the upload.
+        Every way in (step_frames, step_frames_host, step_jpeg_host, step_yuv, step_yuv_host) then resamples its frames on the device
+        through the stream's map, and the whole step -- both nets, the bird view, the overlay, source="frames" -- reads the rectified
+        frames: undistorted_image(frame) after sync().  camera / cameras: a Brown-Conrady / rational lens model as
+        cv2.initUndistortRectifyMap takes it (K and new_K as (fx, fy, cx, cy) or 3x3, D of 4, 5 or 8 coefficients); identical cameras share
+        one map.  maps: cv2's CV_16SC2 + CV_16UC1 pairs (int16 (h, w, 2), uint16 (h, w)), which covers fisheye lenses and stereo
+        rectification.  Composes with jpeg_input= and yuv_input=.  Nothing inside the captured step changes."""
         self.S = n_streams
         self.stream_ids = list(range(n_streams))      # job-wide ids of the local streams (for_rank overrides)
         self.B = max(1, int(micro_batch))
@@ -103,7 +112,9 @@ class AdasPipeline:
         n_streams = n_streams * self.B          # frames per step through the engines / post / decode handles
         self.det = self.lane = self.post = self.decode = self.tracker = self.geometry = self.birdview = self.warp = self.analysis = None
         self.overlay = self.jpeg_encoder = self.jpeg_decoder = self.yuv_converter = self.yuv_writer = None
-        self.scaler = self.scaled_jpeg_encoder = self.scaled_yuv_writer = None
+        self.scaler = self.scaled_jpeg_encoder = self.scaled_yuv_writer = self.remapper = None
+        if undistort is not None:
+            undistort_checked = undistort_args(undistort, n_tracks, src_hw)
         if jpeg_input is not None and jpeg_input is not False:
             jpeg_input = {} if jpeg_input is True else dict(jpeg_input)
             unknown = set(jpeg_input) - {"capacity"}
@@ -331,16 +342,26 @@ class AdasPipeline:
                 self.scaled_yuv_writer = YuvWriter(y.get("format", "i420"), cw, ch, y.get("matrix", "video"), y.get("chroma", "mean"), y.get("layout"),
                                                    self.scaler.canvases(n_streams))
                 L.check(L.lib().adas_pipeline_attach_scale_yuvout(self.h, self.scaled_yuv_writer.h))
+        if undistort is not None:
+            self.remapper = FrameRemapper(src_hw, n_tracks, max_batch=n_streams, **undistort_checked)
+            L.check(L.lib().adas_pipeline_attach_remap(self.h, self.remapper.h))
 
     @classmethod
     def for_rank(cls, det_model, lane_model, total_streams, env=None, **kw):
         """The pipeline of ONE rank of a `total_streams`-stream job (one process per GPU): the rank runs the streams
         sharding.streams_of_rank deals it (stream s -> rank s mod world); `.stream_ids[i]` is the job-wide id of local stream i.
-        Returns None for a rank that owns no stream (fewer streams than ranks)."""
+        Returns None for a rank that owns no stream (fewer streams than ranks).  undistort= may carry cameras= or stream_map= for the whole
+        job (total_streams entries, by job-wide stream id): each rank takes its own streams' entries; a list of the rank's own length is
+        taken as it is."""
         env = env or sharding.RankEnv.from_environ()
         ids = sharding.streams_of_rank(int(total_streams), env)
         if not ids:
             return None
+        und = kw.get("undistort")
+        if isinstance(und, dict) and und.get("cameras") is not None and len(und["cameras"]) == int(total_streams):
+            kw["undistort"] = dict(und, cameras=[und["cameras"][s] for s in ids])       # a job-wide list: this rank's streams, in local order
+        elif isinstance(und, dict) and und.get("stream_map") is not None and len(und["stream_map"]) == int(total_streams):
+            kw["undistort"] = dict(und, stream_map=[und["stream_map"][s] for s in ids])
         p = cls(det_model, lane_model, n_streams=len(ids), **kw)
         p.stream_ids = ids
         return p
@@ -434,6 +455,12 @@ class AdasPipeline:
             raise ValueError("the pipeline was created without yuv_output=")
         return self.yuv_writer.frame(frame)
 
+    def undistorted_image(self, frame=0):
+        """Frame `frame` of the last step (after sync()) as the step read it, rectified: uint8 (src_h, src_w, 3)."""
+        if self.remapper is None:
+            raise ValueError("the pipeline was created without undistort=")
+        return self.remapper.fetch(frame)
+
     def scaled_image(self, canvas=0):
         """Canvas `canvas` of the last step_frames (after sync()): uint8 [rows * h][cols * w][3] BGR, frame f in cell f % (cols * rows) of
         canvas f // (cols * rows)."""
@@ -501,7 +528,7 @@ class AdasPipeline:
         if getattr(self, "h", None):
             L.lib().adas_pipeline_destroy(self.h)
             self.h = None
-        for o in (getattr(self, "scaled_yuv_writer", None), getattr(self, "scaled_jpeg_encoder", None), getattr(self, "scaler", None),
+        for o in (getattr(self, "remapper", None), getattr(self, "scaled_yuv_writer", None), getattr(self, "scaled_jpeg_encoder", None), getattr(self, "scaler", None),
                   getattr(self, "yuv_writer", None), getattr(self, "yuv_converter", None), getattr(self, "jpeg_decoder", None), getattr(self, "jpeg_encoder", None), self.overlay, self.analysis, self.birdview, self.warp, self.geometry, self.post, self.decode, self.tracker, self.det, self.lane):
             if o:
                 o.close()

@@ -1371,6 +1371,194 @@ class FrameScaler:
     __del__ = close
 
 
+def remap_camera(cam, what=""):
+    """A lens model as FrameRemapper takes it, checked without a handle: dict(K=, D=, new_K=None, R=None).  K and new_K: (fx, fy, cx, cy) or
+    cv2's 3x3 camera matrix; D: 4, 5 or 8 of cv2's (k1, k2, p1, p2, k3, k4, k5, k6), zero-padded; new_K defaults to K (cv2.undistort's
+    default), R to the identity.  Returns dict(K, D, new_K, R) of float tuples; ValueError naming the key."""
+    if not isinstance(cam, dict):
+        raise ValueError("%scamera %r is no dict (K, D, new_K, R)" % (what, cam))
+    unknown = set(cam) - {"K", "D", "new_K", "R"}
+    if unknown:
+        raise ValueError("%scamera holds unknown keys %s (K, D, new_K, R)" % (what, sorted(unknown)))
+    if cam.get("K") is None:
+        raise ValueError("%scamera needs K: (fx, fy, cx, cy) or the 3x3 camera matrix" % what)
+
+    def numbers(key, v, sizes, camera_matrix=False):
+        try:
+            a = np.asarray(v, np.float64)
+        except (TypeError, ValueError):
+            a = np.zeros((2, 0))
+        if camera_matrix and a.shape == (3, 3):
+            a = np.array([a[0, 0], a[1, 1], a[0, 2], a[1, 2]])
+        a = a.reshape(-1)
+        if a.size not in sizes:
+            raise ValueError("%scamera %s %r has the wrong shape (%s numbers%s)" % (what, key, v, " or ".join(str(s) for s in sizes),
+                                                                                  " or a 3x3 matrix" if camera_matrix else ""))
+        if not np.isfinite(a).all():
+            raise ValueError("%scamera %s %r holds a non-finite parameter" % (what, key, v))
+        return a
+
+    K = numbers("K", cam["K"], (4,), True)
+    D = numbers("D", () if cam.get("D") is None else cam["D"], (0, 4, 5, 8))
+    new_K = K if cam.get("new_K") is None else numbers("new_K", cam["new_K"], (4,), True)
+    R = np.eye(3).reshape(9) if cam.get("R") is None else numbers("R", cam["R"], (9,))
+    return dict(K=tuple(map(float, K)), D=tuple(map(float, np.concatenate([D, np.zeros(8 - D.size)]))), new_K=tuple(map(float, new_K)),
+                R=tuple(map(float, R)))
+
+
+def remap_maps(maps, dst_hw, what=""):
+    """Caller maps as FrameRemapper takes them: a list of (xy, frac), xy (h, w, 2) int16 and frac (h, w) uint16 -- what
+    cv2.initUndistortRectifyMap(..., cv2.CV_16SC2) and cv2.convertMaps return.  ValueError naming the entry."""
+    try:
+        pairs = [tuple(m) for m in maps]
+    except TypeError:
+        pairs = None
+    if not pairs or any(len(m) != 2 for m in pairs):
+        raise ValueError("%smaps %r is no list of (xy, frac) pairs" % (what, type(maps).__name__))
+    h, w = int(dst_hw[0]), int(dst_hw[1])
+    out = []
+    for i, (xy, frac) in enumerate(pairs):
+        xy, frac = np.asarray(xy), np.asarray(frac)
+        if xy.dtype != np.int16 or xy.shape != (h, w, 2):
+            raise ValueError("%smaps[%d] xy is %s %s, not int16 (%d, %d, 2)" % (what, i, xy.dtype, xy.shape, h, w))
+        if frac.dtype != np.uint16 or frac.shape != (h, w):
+            raise ValueError("%smaps[%d] frac is %s %s, not uint16 (%d, %d)" % (what, i, frac.dtype, frac.shape, h, w))
+        out.append((np.ascontiguousarray(xy), np.ascontiguousarray(frac)))
+    return out
+
+
+def remap_stream_map(stream_map, n_streams, n_maps, what=""):
+    """The map of every stream: None is stream s -> map min(s, n_maps - 1).  ValueError naming the entry."""
+    if stream_map is None:
+        return [min(s, n_maps - 1) for s in range(n_streams)]
+    try:
+        sm = [int(v) for v in stream_map]
+        ok = all(int(v) == v for v in stream_map)
+    except (TypeError, ValueError):
+        sm, ok = [], False
+    if not ok or len(sm) != n_streams:
+        raise ValueError("%sstream_map %r is no list of %d map indices, one per stream" % (what, stream_map, n_streams))
+    for s, m in enumerate(sm):
+        if not 0 <= m < n_maps:
+            raise ValueError("%sstream_map[%d] = %d is outside the %d maps" % (what, s, m, n_maps))
+    return sm
+
+
+def undistort_args(undistort, n_streams, src_hw):
+    """AdasPipeline(undistort=)'s checks without a handle (so without a GPU): ValueError naming the key.  Returns dict(cameras= | maps=,
+    stream_map=) as FrameRemapper takes them; identical cameras share one map."""
+    keys = "camera, cameras, maps, stream_map"
+    if not isinstance(undistort, dict):
+        raise ValueError("undistort= %r is neither None nor a dict (%s)" % (undistort, keys))
+    unknown = set(undistort) - {"camera", "cameras", "maps", "stream_map"}
+    if unknown:
+        raise ValueError("undistort= holds unknown keys %s (%s)" % (sorted(unknown), keys))
+    given = [k for k in ("camera", "cameras", "maps") if undistort.get(k) is not None]
+    if len(given) != 1:
+        raise ValueError("undistort= needs exactly one of camera=, cameras= and maps= (got %s)" % (given or "none"))
+    if given[0] == "maps":
+        maps = remap_maps(undistort["maps"], src_hw, what="undistort= ")
+        return dict(maps=maps, stream_map=remap_stream_map(undistort.get("stream_map"), n_streams, len(maps), what="undistort= "))
+    if undistort.get("stream_map") is not None:
+        raise ValueError("undistort= stream_map goes with maps=; cameras= holds one camera per stream")
+    if given[0] == "camera":
+        return dict(cameras=[remap_camera(undistort["camera"], what="undistort= ")], stream_map=[0] * n_streams)
+    try:
+        cams = list(undistort["cameras"])
+    except TypeError:
+        cams = []
+    if len(cams) != n_streams:
+        raise ValueError("undistort= cameras holds %d cameras, the pipeline has %d streams (one per stream)" % (len(cams), n_streams))
+    cams = [remap_camera(c, what="undistort= cameras[%d] " % i) for i, c in enumerate(cams)]
+    distinct, stream_map = [], []
+    for c in cams:
+        key = (c["K"], c["D"], c["new_K"], c["R"])
+        if key not in [(d["K"], d["D"], d["new_K"], d["R"]) for d in distinct]:
+            distinct.append(c)
+        stream_map.append([(d["K"], d["D"], d["new_K"], d["R"]) for d in distinct].index(key))
+    return dict(cameras=distinct, stream_map=stream_map)
+
+
+class FrameRemapper:
+    """Camera frames rectified on the device (adas_remap_*): cv2.remap(frame, map1, map2, INTER_LINEAR, BORDER_CONSTANT 0) of BGR u8 frames in
+    HBM through one fixed-point map per stream -- cv2.undistort when the map comes from a lens model.  cameras: a list of lens models
+    (remap_camera's dict), one map each, built on the device as cv2.initUndistortRectifyMap writes it; or maps: a list of (xy int16 (h, w, 2),
+    frac uint16 (h, w)), cv2's CV_16SC2 + CV_16UC1 pair.  stream_map[s] is the map stream s reads (None: min(s, maps - 1)); frame f of a batch
+    belongs to stream f % n_streams.  dst_hw: the rectified size (None: src_hw).  The rules U1-U6 are csrc/remap_core.h; parity with a real
+    cv2 build unpinned."""
+
+    def __init__(self, src_hw, n_streams, cameras=None, maps=None, stream_map=None, dst_hw=None, max_batch=None):
+        if (cameras is None) == (maps is None):
+            raise ValueError("FrameRemapper needs cameras= or maps=, not both")
+        self.src_hw = (int(src_hw[0]), int(src_hw[1]))
+        self.dst_hw = self.src_hw if dst_hw is None else (int(dst_hw[0]), int(dst_hw[1]))
+        self.n_streams = int(n_streams)
+        cams = None if cameras is None else [remap_camera(c, what="cameras[%d] " % i) for i, c in enumerate(cameras)]
+        tables = None if maps is None else remap_maps(maps, self.dst_hw)
+        self.n_maps = len(cams if cams is not None else tables)
+        if self.n_maps < 1:
+            raise ValueError("FrameRemapper needs at least one camera or map")
+        sm = remap_stream_map(stream_map, self.n_streams, self.n_maps)
+        self.max_batch = self.n_streams if max_batch is None else int(max_batch)
+        self.h = None
+        p = L.RemapParams(self.src_hw[0], self.src_hw[1], self.dst_hw[0], self.dst_hw[1], self.n_streams, self.n_maps)
+        h = C.c_void_p()
+        L.check(L.lib().adas_remap_create(C.byref(p), self.max_batch, C.byref(h)))
+        self.h = h.value
+        for s, m in enumerate(sm):
+            if m != min(s, self.n_maps - 1):
+                L.check(L.lib().adas_remap_assign(self.h, s, m))
+        self.stream_map = sm
+        for i in range(self.n_maps):
+            if cams is not None:
+                self.set_camera(i, **cams[i])
+            else:
+                self.set_map(i, *tables[i])
+
+    def set_camera(self, map, K, D=(), new_K=None, R=None):
+        """Map `map` (-1: every map) from a lens model; finished on return."""
+        c = remap_camera(dict(K=K, D=D, new_K=new_K, R=R))
+        cam = L.RemapCamera()
+        for key in ("K", "D", "new_K", "R"):
+            for i, v in enumerate(c[key]):
+                getattr(cam, key)[i] = v
+        L.check(L.lib().adas_remap_set_camera(self.h, int(map), C.byref(cam)))
+
+    def set_map(self, map, xy, frac):
+        """Map `map` from the caller's tables."""
+        (xy, frac), = remap_maps([(xy, frac)], self.dst_hw)
+        L.check(L.lib().adas_remap_set_map(self.h, int(map), L.ptr(xy), L.ptr(frac)))
+
+    def fetch_map(self, map=0):
+        """(xy int16 (h, w, 2), frac uint16 (h, w)) of map `map` as the runs read it."""
+        xy, frac = np.empty(self.dst_hw + (2,), np.int16), np.empty(self.dst_hw, np.uint16)
+        L.check(L.lib().adas_remap_fetch_map(self.h, int(map), L.ptr(xy), L.ptr(frac)))
+        return xy, frac
+
+    def run(self, src_ptr, batch=None, dst_ptr=None, stream=None):
+        """src_ptr: device pointer of [batch][src_h][src_w][3] u8.  dst_ptr=None writes the handle's own buffer (fetch / device_view).
+        Asynchronous on `stream`."""
+        L.check(L.lib().adas_remap_run(self.h, src_ptr, int(self.max_batch if batch is None else batch), dst_ptr, stream))
+
+    def fetch(self, frame=0):
+        """Frame `frame` of the handle's own buffer: uint8 (dst_h, dst_w, 3).  Waits for the last run."""
+        out = np.empty(self.dst_hw + (3,), np.uint8)
+        L.check(L.lib().adas_remap_fetch(self.h, int(frame), L.ptr(out)))
+        return out
+
+    def device_view(self):
+        p = C.c_void_p()
+        L.check(L.lib().adas_remap_device_view(self.h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            L.lib().adas_remap_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 class OverlayPainter:
     """What the drop-in Draw* methods share (detectors.UltrafastLaneDetectorV2.DrawDetectedOnFrame / .DrawAreaOnFrame,
     analysis.PerspectiveTransformation.DrawDetectedOnBirdView): one LaneOverlay per image size, one stage per call on the caller's image.
